@@ -27,6 +27,12 @@ receiver over N ranks (strong scaling; the syncs all-gathered and the counters a
 after the per-phy chains).  churn is a single logical process: its ranks run independent replicas and
 their events add up.
 
+A plain run sets up, runs --warmup untimed and --steps timed steps and prints the line with the headline
+figures (`value`, `ms_per_step`, the run's counts).  --dump-outputs DIR also writes what the last timed step
+computed (the run's statistics and the counters / records a caller reads back) as DIR/<name>.npy, identical
+from run to run: the scenarios are fixed or seeded.  --full adds the figures below, each of which takes
+runs of its own, and for p2p-grid the `secondary` list (wifi-grid, wifi-loop, dumbbell).
+
 roofline: dominant kernel = the churn's persistent kernel, or for p2p-grid the window-pipeline
 kernel with the largest average launch time (per-kernel HIP events in a separate bracketed run);
 algorithmic bytes per event from SURVEY §8(d) (queue: 72 B/event; p2p hop: 208 B per hop = 104 B
@@ -66,6 +72,52 @@ def oracle():
     return nsref
 
 
+# ---------------------------------------------------------------- --dump-outputs
+DUMP_ROWS = 1 << 19  # rows kept of one output (4 MiB a float64 column; the largest workload writes 12 columns)
+DUMP_LIMIT = 64 << 20
+
+
+def stats_vector(st):
+    """A run's integer statistics (a ctypes struct, or (name, value) pairs) as one float64 vector in field order,
+    every value exact: `digest` (any 64 bits) takes two entries, its high and low 32 bits."""
+    import numpy as np
+    pairs = st if isinstance(st, list) else [(f, getattr(st, f)) for f, _ in st._fields_]
+    vals = []
+    for f, v in pairs:
+        v = int(v)
+        if f == "digest":
+            vals += [v >> 32, v & 0xFFFFFFFF]
+        elif v >= 1 << 53:
+            raise ValueError(f"--dump-outputs: {f} = {v} is more than float64 can represent")
+        else:
+            vals.append(v)
+    return np.array(vals, dtype=np.float64)
+
+
+def dump_outputs(path, outputs, prefix=""):
+    """Writes {name: array} as float64 .npy files under `path`.  A structured array becomes one file per field
+    (<name>.<field>.npy, padding fields left out).  Every value is written exactly (64-bit integers must lie
+    below 2^53).  An output of more than DUMP_ROWS rows is cut to a sorted sample of DUMP_ROWS row indices
+    drawn with a fixed seed: the same rows for every field, in every run and every build."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for name, a in outputs.items():
+        a = np.asarray(a)
+        if len(a) > DUMP_ROWS:
+            a = a[np.sort(np.random.default_rng(len(a)).choice(len(a), DUMP_ROWS, replace=False))]
+        cols = {name: a} if a.dtype.names is None else \
+            {f"{name}.{f}": a[f] for f in a.dtype.names if not f.startswith("pad")}
+        for cname, c in cols.items():
+            if c.dtype.kind in "iu" and c.dtype.itemsize == 8 and c.size and int(np.abs(c).max()) >= 1 << 53:
+                raise ValueError(f"--dump-outputs: {cname} holds a value float64 cannot represent")
+            c = np.ascontiguousarray(c, dtype=np.float64)
+            total += c.nbytes
+            if total > DUMP_LIMIT:
+                raise ValueError(f"--dump-outputs: more than {DUMP_LIMIT} bytes of outputs")
+            np.save(os.path.join(path, prefix + cname + ".npy"), c)
+
+
 # ---------------------------------------------------------------- workloads
 class Churn:
     bytes_per_event = 72
@@ -92,6 +144,10 @@ class Churn:
     def result(self):
         st, _, _ = self.run.result()
         return int(st.dispatched), int(st.digest), {"rounds_per_step": int(st.rounds), "max_batch": int(st.max_batch)}
+
+    def outputs(self):
+        st, _, _ = self.run.result()
+        return {"stats": stats_vector(st)}
 
     def cpu_baseline(self):
         """MapScheduler (the default, SchedulerType = ns3::MapScheduler) on the full run is the baseline value;
@@ -215,6 +271,10 @@ class P2PGrid:
             "cancelled_per_step": int(st.cancelled), "refits_per_step": int(st.refits),
             "delivered_packets": int(appc["rx_packets"].sum())}
 
+    def outputs(self):
+        st, devc, appc, _ = self.engine.results()
+        return {"stats": stats_vector(st), "dev": devc, "app": appc}
+
     def cpu_baseline(self):
         import numpy as np
         nsref = oracle()
@@ -334,6 +394,9 @@ class P2PGridDist:
             "windows_per_step": int(st.windows), "max_window": int(st.max_window),
             "ranks": self.world}
 
+    def outputs(self):
+        return P2PGrid.outputs(self)
+
 
 class P2PDumbbellDist(P2PGridDist):
     """Config 5 as BASELINE names it: simple-distributed.cc's 1,000,000-node dumbbell (2 x 499,999 leaves)
@@ -415,6 +478,12 @@ class WifiFanout:
         total = sum(len(r) for r in self.recs)
         return total, total, {"transmissions_per_step": self.n_tx}
 
+    def outputs(self):
+        import numpy as np
+        recs, _ = self.fo.results(self.n_tx)
+        # (every 16th transmission's receiver events: the whole step's are 40 B x 10 M)
+        return {"rx": np.concatenate(recs[::16])}
+
     def cpu_baseline(self):
         import numpy as np
         nsref = oracle()
@@ -486,6 +555,9 @@ class WifiGrid:
             "receive_events": int(st.rx), "syncs": int(st.sync), "cca_busy_switches": int(st.cca_switches),
             "end_receive_cancelled": int(st.end_cancelled), "ni_max": int(st.ni_max),
             "near_threshold": int(st.near_threshold)}
+
+    def outputs(self):
+        return {"stats": stats_vector(self.engine.stats()), "phy": self.engine.phys()}
 
     def cpu_baseline(self):
         import numpy as np
@@ -618,6 +690,7 @@ class WifiLoop:
         res = (int(sim.dispatched()), int(digest), {"sends": cnt[0], "busy_attempts": cnt[1],
                                                    "end_receives": int(len(ends)), "next_uid": int(sim.next_uid()),
                                                    "epochs": int(nh), "us_per_epoch": secs * 1e6 / max(int(nh), 1)})
+        self._ends = ends
         lp.close()
         return res
 
@@ -656,6 +729,7 @@ class WifiLoop:
                                                     "end_receives": int(len(ends)), "next_uid": int(sim.next_uid()),
                                                     "epochs": int(nh), "us_per_epoch": secs * 1e6 / max(int(nh), 1),
                                                     "mac": "C callbacks (scripts/macstub.cc)"})
+        self._ends = ends
         lp.close()
         return res
 
@@ -672,6 +746,12 @@ class WifiLoop:
 
     def result(self):
         return self._last
+
+    def outputs(self):
+        disp, digest, info = self._last
+        totals = [("dispatched", disp), ("digest", digest)] + \
+            [(f, info[f]) for f in ("sends", "busy_attempts", "end_receives", "next_uid")]
+        return {"stats": stats_vector(totals), "end": self._ends}
 
     def cpu_baseline(self):
         import time
@@ -745,9 +825,15 @@ def parser():
     ap.add_argument("--wifi-loop-stop", type=float, default=0.2, help="wifi-loop: Simulator::Stop (s)")
     ap.add_argument("--wifi-mac", choices=("native", "python"), default="native",
                     help="wifi-loop: the MAC stand-in as C callbacks (lib/libnsgpu_macstub.so) or Python closures")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what takes runs of its own: the roofline (per-kernel "
+                         "profile run), the CPU baseline with its digest check, and for p2p-grid the `secondary` "
+                         "workloads; a plain run prints the headline figures only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (float64; see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="p2p-grid: skip the wifi-grid / dumbbell entries of the `secondary` list")
+                    help="--full, p2p-grid: skip the wifi-grid / dumbbell entries of the `secondary` list")
     ap.add_argument("--secondary-steps", type=int, default=3, help="timed steps of each secondary workload")
     ap.add_argument("--partitioned", action="store_true",
                     help="p2p-grid / wifi-grid / dumbbell / wifi-loop through the partitioned engine even on one rank (RCCL "
@@ -756,7 +842,10 @@ def parser():
 
 
 def main():
-    args = parser().parse_args()
+    ap = parser()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -838,6 +927,8 @@ def main():
 
     elapsed, kernel_ms = measure(wl, args.steps, args.warmup)
     events_per_step, digest, extra = wl.result()
+    if args.dump_outputs:  # (before the roofline's profile run and the baselines' sample runs: the timed path's own)
+        dump_outputs(args.dump_outputs, wl.outputs(), f"rank{rank}_" if world > 1 else "")
 
     if tdist is not None:
         import torch
@@ -847,7 +938,7 @@ def main():
 
     # a partitioned run is ONE simulation: its (global) events once; replicas (churn) add up
     value = events_per_step * args.steps * (1 if partitioned else world) / elapsed
-    roofline = roofline_of(wl, args.workload, kernel_ms, events_per_step)
+    roofline = roofline_of(wl, args.workload, kernel_ms, events_per_step) if args.full else None
 
     if rank == 0:
         out = {
@@ -866,14 +957,18 @@ def main():
             "config": dict({"workload": wl.workload, "events_per_step": events_per_step,
                             "parallelism": (f"partitioned x{world} (RCCL)" if partitioned else
                                             "replicas" if world > 1 else "single")}, **extra),
-            "roofline": roofline,
         }
-        if not args.no_cpu_baseline and world == 1 and (not partitioned or hasattr(wl, "cpu_baseline")):
+        # a plain run ends here; --full adds the figures that take runs of their own
+        if args.full:
+            out["roofline"] = roofline
+        if (args.full and not args.no_cpu_baseline and world == 1
+                and (not partitioned or hasattr(wl, "cpu_baseline"))):
             out["cpu_baseline"], out["speedup_vs_cpu"] = cpu_baseline_of(wl, value, digest)
         # the north star's other GPU targets (configs 3 and 5) in the same line, on the same box: each a
         # whole run per step, digest-checked against the oracle like the primary
         secondary = []
-        if world == 1 and not partitioned and args.workload == "p2p-grid" and not args.no_secondary:
+        if (args.full and world == 1 and not partitioned and args.workload == "p2p-grid"
+                and not args.no_secondary):
             names = os.environ.get("NSGPU_BENCH_SECONDARIES", "wifi-grid,wifi-loop,dumbbell").split(",")
             wl.close()  # (each workload closed before the next: its streams and HBM released)
             for name in names:

@@ -12,8 +12,8 @@ shift 3 || shift $#
 mkdir -p $O
 cd $R
 for r in $(seq 1 $REPS); do
-  timeout -k 10 200 python bench.py --no-secondary --no-cpu-baseline "$@" > $O/a_$r.json 2> $O/a_$r.err
-  timeout -k 10 200 env $ENVS python bench.py --no-secondary --no-cpu-baseline "$@" > $O/b_$r.json 2> $O/b_$r.err
+  timeout -k 10 200 python bench.py --full --no-secondary --no-cpu-baseline "$@" > $O/a_$r.json 2> $O/a_$r.err
+  timeout -k 10 200 env $ENVS python bench.py --full --no-secondary --no-cpu-baseline "$@" > $O/b_$r.json 2> $O/b_$r.err
 done
 python - "$O" "$REPS" <<'EOF'
 import json, sys

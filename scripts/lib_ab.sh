@@ -13,7 +13,7 @@ cd $R
 for r in $(seq 1 $REPS); do
   i=0
   for L in "$@"; do
-    NSGPU_LIB=$R/$L timeout -k 10 200 python bench.py --no-secondary --no-cpu-baseline $BENCH_ARGS > $O/v${i}_$r.json 2> $O/v${i}_$r.err
+    NSGPU_LIB=$R/$L timeout -k 10 200 python bench.py --full --no-secondary --no-cpu-baseline $BENCH_ARGS > $O/v${i}_$r.json 2> $O/v${i}_$r.err
     i=$((i + 1))
   done
 done

@@ -40,15 +40,15 @@ for st in "$@"; do
     tests) step tests 1500 python -u -m pytest -x -q --timeout 300 --timeout-method thread -m gpu tests ;;
     tests:*) step tests_k 900 python -u -m pytest -x -v --timeout 300 --timeout-method thread -m gpu tests -k "${st#tests:}" ;;
     smoke) step smoke 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" ;;
-    bench) step bench 300 python bench.py ;;
-    bench:*) a=${st#bench:}; step bench_$(echo $a | tr -c 'a-zA-Z0-9\n' '_') 300 python bench.py ${a//,/ } ;;
+    bench) step bench 300 python bench.py --full ;;
+    bench:*) a=${st#bench:}; step bench_$(echo $a | tr -c 'a-zA-Z0-9\n' '_') 300 python bench.py --full ${a//,/ } ;;
     benches)
-      step bench_p2p_grid 300 python bench.py
-      step bench_dumbbell 300 python bench.py --workload dumbbell
-      step bench_dumbbell_partitioned 300 python bench.py --workload dumbbell --partitioned
-      step bench_p2p_grid_partitioned 300 python bench.py --partitioned --no-cpu-baseline
-      step bench_wifi_loop 300 python bench.py --workload wifi-loop
-      step bench_churn 300 python bench.py --workload churn ;;
+      step bench_p2p_grid 300 python bench.py --full
+      step bench_dumbbell 300 python bench.py --full --workload dumbbell
+      step bench_dumbbell_partitioned 300 python bench.py --full --workload dumbbell --partitioned
+      step bench_p2p_grid_partitioned 300 python bench.py --full --partitioned --no-cpu-baseline
+      step bench_wifi_loop 300 python bench.py --full --workload wifi-loop
+      step bench_churn 300 python bench.py --full --workload churn ;;
     rocprof_p2p)
       cd /tmp
       NSGPU_P2P_EAGER=1 step rocprof_p2p 240 rocprofv3 --kernel-trace --stats -d $O/rocprof_p2p -o run --output-format csv -- python3 $R/bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-secondary

@@ -7,7 +7,7 @@ export TMPDIR=/tmp PYTHONUNBUFFERED=1
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/$1
 shift
-ARGS="--partitioned --no-cpu-baseline"
+ARGS="--full --partitioned --no-cpu-baseline"
 VARS=()
 while [ $# -gt 0 ]; do
   if [ "$1" = "--" ]; then ARGS="${2//,/ }"; break; fi

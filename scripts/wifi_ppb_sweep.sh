@@ -11,7 +11,7 @@ mkdir -p $O
 cd $R
 for r in $(seq 1 $REPS); do
   for P in "$@"; do
-    NSGPU_WIFI_PHYS_PER_BLOCK=$P timeout -k 10 200 python bench.py --workload wifi-grid --no-secondary --no-cpu-baseline \
+    NSGPU_WIFI_PHYS_PER_BLOCK=$P timeout -k 10 200 python bench.py --workload wifi-grid --full --no-secondary --no-cpu-baseline \
       --steps 3 > $O/p${P}_$r.json 2> $O/p${P}_$r.err
   done
 done
