@@ -414,7 +414,7 @@ int nsgpu_p2p_last_run_ms(nsgpu_p2p *h, double *gpu_ms);
 /* 1: the engine runs wide windows — bounded by the cross-node lookahead (min over devices of the smallest
  * frame's tx time + channel delay), a same-node TransmitComplete before the window's end running inside
  * it.  Single engines whose nodes have at most 16 devices, unless NSGPU_P2P_NARROW=1 was
- * set when the engine was created. */
+ * set when the engine was created (the environment variables are listed after nsgpu_p2p_phase_read). */
 int nsgpu_p2p_get_wide(nsgpu_p2p *h, int *wide);
 /* Launch mode of nsgpu_p2p_run: 0 = hipGraph replays (default), 1 = the same kernels launched one by
  * one (also selected by the environment variable NSGPU_P2P_EAGER; used under rocprofv3). */
@@ -465,6 +465,22 @@ int nsgpu_p2p_pending(nsgpu_p2p *h, uint64_t *n, uint64_t *next_ts, int *stopped
 /* Diagnostic: in-kernel phase timers (s_memrealtime ticks, 100 MHz) of the pipeline kernels; only the
  * lib/libnsgpu_prof.so build (-DNSGPU_PHASE_PROF) records them, the product library returns ESTATE. */
 int nsgpu_p2p_phase_read(uint64_t *out, int n, int reset);
+/* Environment variables.  The library reads these and no others (tests/test_env_switches_cpu.py).
+ *   NSGPU_P2P_EAGER   (set to anything) the window pipeline's kernels are launched one by one instead of as
+ *                     hipGraph replays, as after nsgpu_p2p_set_eager (h, 1): rocprofv3's kernel tracer does not
+ *                     follow graphs.  An engine reads it at nsgpu_p2p_create, a loopback group at its first
+ *                     nsgpu_p2p_group_run.
+ *   NSGPU_P2P_POISON  (=1) nsgpu_p2p_create fills every device array with 0xa5 bytes when it allocates it,
+ *                     before initialising it: a deterministic stand-in for device memory that an earlier
+ *                     engine dirtied (create must zero whatever the kernels read).
+ *   NSGPU_P2P_NARROW  (=1, at nsgpu_p2p_create) the engine runs narrow windows where it would run wide ones
+ *                     (nsgpu_p2p_get_wide); the results are the same.
+ * Diagnostic build only (lib/libnsgpu_prof.so, -DNSGPU_PHASE_PROF; the product library ignores them):
+ *   NSGPU_P2P_DEBUG        =1 (eager launches) the stream is drained after every kernel and the engine's
+ *                          invariants are checked (pool, free stack, fresh buffer, window records, children);
+ *                          =2 (graph replays) the checks run as graph nodes after every kernel, and a broken
+ *                          invariant ends the run.
+ *   NSGPU_P2P_DEBUG_TRACE  (with NSGPU_P2P_DEBUG=1) the run control is printed window by window. */
 
 /* ---------------- global routing ----------------
  * Replaces GlobalRouteManager::PopulateRoutingTables (SPFCalculate, global-route-manager-impl.cc:

@@ -50,35 +50,25 @@ constexpr int NJT = WCAP / RJ;   // rank tile columns
 constexpr int RTR = 1;           // window keys (rows) per thread of a rank tile (4: same traffic, slower)
 constexpr int NRT = WCAP / (HB * RTR);  // rank tile rows
 constexpr int NRB = NRT * NJT;   // rank tile blocks (k2_handle)
-#ifndef GRID_POOL_N
-#define GRID_POOL_N 128  // (r06, with 128-record slot blocks: 128 against 256 blocks, config 4 +1.4 %: ab/p2p_knobs2.log)
-#endif
-#ifndef GRID_POOL_BIG_N
-#define GRID_POOL_BIG_N 256  // (config 5's 5 M-entry pool on one engine: 256 / 128 / 96 / 64 blocks 120.6 / 114.6 / 110.9 / 101.3 M
-#endif                       //  ev/s, ab/p2p_pool_blocks.log; config 4 flat from 64 to 128)
-constexpr int GRID_POOL_BIG = GRID_POOL_BIG_N;  // ... the single engine's, when the pool capacity is above 2^20 entries
-constexpr int GRID_POOL = GRID_POOL_N;
-#ifndef GRID_POOL_DIST_N
-#define GRID_POOL_DIST_N GRID_POOL_N
-#endif
-constexpr int GRID_POOL_DIST = GRID_POOL_DIST_N;  // k2_pa<DIST>'s whole grid (slot, remote, chunk and pool blocks)   // blocks of the pool sweep (grid-stride; r06: 1,024 measured slower on
-                                         // config 4 and on the dumbbell's 5 M-entry pool: per-block reductions)
-#ifndef PA_SLOT_LANES
-#define PA_SLOT_LANES 128        // k2_pa (single engine): last-window records per slot block (r06: 128 against 256,
-                                 // config 4 +0.7 %, k2_pa ~10.3 -> ~9.8 us; profiles/r06/ab/p2p_tail_replays_slot_lanes.log)
-#endif
+// blocks of the pool sweep (grid-stride; r06: 1,024 measured slower on config 4 and on the dumbbell's 5 M-entry
+// pool: per-block reductions; with 128-record slot blocks, 128 against 256 blocks: config 4 +1.4 %,
+// ab/p2p_knobs2.log)
+constexpr int GRID_POOL = 128;
+// ... the single engine's, when the pool capacity is above 2^20 entries (config 5's 5 M-entry pool on one engine:
+// 256 / 128 / 96 / 64 blocks 120.6 / 114.6 / 110.9 / 101.3 M ev/s, ab/p2p_pool_blocks.log; config 4 flat from 64
+// to 128)
+constexpr int GRID_POOL_BIG = 256;
+constexpr int GRID_POOL_DIST = GRID_POOL;  // k2_pa<DIST>'s whole grid (slot, remote, chunk and pool blocks)
+// k2_pa (single engine): last-window records per slot block (r06: 128 against 256, config 4 +0.7 %, k2_pa ~10.3 ->
+// ~9.8 us; profiles/r06/ab/p2p_tail_replays_slot_lanes.log)
+constexpr int PA_SLOT_LANES = 128;
 constexpr int SCAN_THREADS = 1024;
 constexpr int CH = 16;           // events of one node a handler thread sorts in LDS
 constexpr int NSLOT = 7;         // per-node slot table entries
 constexpr int NTAB = NSLOT + 1;  // words per node table record (count + slots)
-#ifndef NWIN_N
-#define NWIN_N 32
-#endif
-#ifndef NWIN_TAIL_N
-#define NWIN_TAIL_N 2  // (2 / 4 / 8 / none: 160.4 / 159.9 / 160.3 / 159.5 M ev/s on config 4, interleaved)
-#endif
-constexpr int NWIN = NWIN_N;     // windows per graph replay
-constexpr int NWIN_TAIL = NWIN_TAIL_N;  // ... near the end of a run (drive)
+constexpr int NWIN = 32;         // windows per graph replay
+constexpr int NWIN_TAIL = 2;     // ... near the end of a run (drive; 2 / 4 / 8 / none: 160.4 / 159.9 / 160.3 / 159.5 M
+                                 // ev/s on config 4, interleaved)
 constexpr uint32_t NOCTX = 0xffffffffu;
 constexpr uint32_t LOCALBIT = 0x80000000u;  // child record kind: run inside the window as a local record
 // a Receive whose node another rank owns (partitioned engines; set by the device step from its record, so
@@ -114,7 +104,7 @@ struct Red {
   uint64_t wendw;  // the wide bound: min over pending of ts + lookw (cross-node lookahead; wide engines)
 };
 
-// A deferred window's dispatch bases: what k2_sdef needs once the window's records are staged in rank order.
+// A deferred window's dispatch bases: what df_sdef needs once the window's records are staged in rank order.
 struct WInfo {
   uint64_t K0, tmin, ilim;  // dispatches before the window, its tmin and inline limit
   uint32_t uid0, N, W, Lt;  // the uid its first child takes; records (gen-0 W + local Lt)
@@ -122,9 +112,9 @@ struct WInfo {
 
 // A staged record of a deferred window, at its rank: key (rel ts << 32 | its uid — resolved at staging when it
 // was provisional; a local record's key has uid 0: its uid is its parent's child prefix + j, resolved by
-// k2_sdef), counts (children | inline children << 9 | the record's dense index << 18), and for a local record
+// df_sdef), counts (children | inline children << 9 | the record's dense index << 18), and for a local record
 // its parent (the parent's dense index | child index << 24), for a gen-0 record its first inline leaf (its
-// context | child index << 24; a local record has none).  Its context is kept beside it (stx).  Stage arrays (and the child prefixes cpt) are indexed by stg_pos(rank): k2_sdef's
+// context | child index << 24; a local record has none).  Its context is kept beside it (stx).  Stage arrays (and the child prefixes cpt) are indexed by stg_pos(rank): df_sdef's
 // thread t owns the 8 consecutive ranks 8t..8t+7 and loads its q-th one from q * 1024 + t, so every load and
 // store of a wave is coalesced.
 struct Stg {
@@ -132,7 +122,7 @@ struct Stg {
   uint32_t cnt, par;
 };
 static_assert(sizeof(Stg) == 16, "Stg");
-constexpr uint32_t STG_NT = 1024;  // k2_sdef's threads (its rank slices)
+constexpr uint32_t STG_NT = 1024;  // df_sdef's threads (its rank slices)
 // Provisional uids (deferred windows): child j of the record of rank r of window n, before window n's child
 // prefix is known, is PROV | (n & 1) << 30 | r << 8 | j — above every resolved uid (< UID_DF_LIMIT, checked), so
 // keys compare as the final uids do; resolved to uid0(n) + cpt[n & 1][r] + j.
@@ -194,8 +184,8 @@ struct Ctl {
   // ---- deferred dispatch accounting (single wide engine, nsgpu_p2p_win.h "deferred windows") ----
   uint64_t acc_tc, acc_tinl;  // this window's children / inline children (k2_handle accumulates)
   uint32_t pdf;               // the window the next k2_pa appends is staged (1) or appended from sinfo (0)
-  uint32_t sflag;             // k2_pa staged a window for k2_sdef: 1 | (its window index & 3) << 1 (k2_pa writes
-                              // it every window; k2_sdef's blocks only read it)
+  uint32_t sflag;             // k2_pa staged a window for df_sdef: 1 | (its window index & 3) << 1 (k2_pa writes
+                              // it every window; df_sdef's blocks only read it)
   uint32_t rk_W, rk_go;       // k2_handle's snapshot for k2_rank (window size; it was handled, normally)
   uint64_t rk_win, rk_lim;    //   (its window index, lim_rel): k2_rank's bookkeeping block rewrites C.W etc.
   WInfo winfo[4];             // window n's dispatch bases (k2_rank's bookkeeping), at n & 3
@@ -337,12 +327,11 @@ struct P2PDev {
                           // child counts (n | inline << 16), rel ts, parent (wpar)
   uint32_t *lrank;        // [LMAX] their rank accumulators (k2_rank; 0 between windows)
   // ---- deferred windows (wrank / lrank are then 2 x WTOT / 2 x LMAX: by window parity) ----
-  struct Stg *stage;      // [NMAX] a window's records by stg_pos(rank) (k2_pa stages, k2_sdef reads)
+  struct Stg *stage;      // [NMAX] a window's records by stg_pos(rank) (k2_pa stages, df_sdef reads)
   uint32_t *stx;          // [NMAX] their contexts (stg_pos)
   uint2 *sleaf;           // [NMAX][maxc] their further inline leaves: (context, child index) (by rank, entry 0 unused)
-  uint32_t *cpt;          // [2][NMAX] child prefix by rank (k2_sdef): provisional uids resolve through it
+  uint32_t *cpt;          // [2][NMAX] child prefix by rank (df_sdef): provisional uids resolve through it
   uint32_t *ldpd;         // [LMAX] the dense list's parents as dense indices | child index << 24 (k2_rank -> k2_pa)
-  uint32_t sdef_fold;     // df_sdef runs as k2_rank's blocks 1 .. NSDEF (1) or as its own kernel k2_sdef (0)
   // ---- partitioned sorted runs: this rank's candidates of the run window, in key order (runcap each) ----
   uint64_t *rn_key;
   uint32_t *rn_ctx, *rn_kind, *rn_a, *rn_src;
@@ -1464,19 +1453,11 @@ __global__ __launch_bounds__(TB) void k_drun_first(const P2PDev M) {
   }
 }
 
-#ifndef GT_CT
-#define GT_CT 1  // column tiles of one k_gtile work item (more: fewer atomics, but the compares bound it)
-#endif
-#ifndef GT_GJ
-#define GT_GJ 64  // columns of one k_gtile tile (smaller tiles, more waves a SIMD to interleave: 256 -> 64 columns
-                   // took a wide window's k_gtile from 25 to 17 us)
-#endif
-constexpr int GJ = GT_GJ;
+constexpr int GT_CT = 1;  // column tiles of one k_gtile work item (more: fewer atomics, but the compares bound it)
+constexpr int GJ = 64;    // columns of one k_gtile tile (smaller tiles, more waves a SIMD to interleave: 256 -> 64
+                          // columns took a wide window's k_gtile from 25 to 17 us)
 static_assert(GJ <= 64, "k_gtile's packed column counts (7-bit count field)");
-#ifndef GT_GTB
-#define GT_GTB 8192
-#endif
-constexpr int GTB = GT_GTB;  // blocks of k_gtile (grid-stride over tiles: a wide window's ~5,600 tiles in one round)
+constexpr int GTB = 8192;  // blocks of k_gtile (grid-stride over tiles: a wide window's ~5,600 tiles in one round)
 // The partitioned window's dispatch order, in three steps (r06; before, k_gtile compared every row with every
 // rank's records, so its work grew with the ranks: 12.6 / 19.6 / 40.6 / 52.8 us a window at 1 / 2 / 4 / 8
 // loopback partitions, profiles/r06/gtile_scale/):
@@ -2164,6 +2145,11 @@ extern "C" int nsgpu_comm_destroy(nsgpu_comm *c) {
   return NSGPU_OK;
 }
 
+// NSGPU_P2P_EAGER (set to anything): the replays' kernels launched one by one instead of as graph replays
+// (rocprofv3's kernel tracer does not follow graphs).  An engine reads it at create (nsgpu_p2p_set_eager
+// overrides it), a loopback group once a process.
+static bool env_eager() { return getenv("NSGPU_P2P_EAGER") != nullptr; }
+
 struct nsgpu_p2p {
   P2PDev M;
   nsgpu_p2p_scenario sc;  // (its host pointers are the caller's: not used after nsgpu_p2p_create)
@@ -2180,7 +2166,7 @@ struct nsgpu_p2p {
   uint32_t *done_host = nullptr;  // pinned, 2 slots
   Ctl *snap = nullptr;            // pinned, 2 run-control snapshots (single engine)
   float last_ms = 0.f;
-  bool eager = getenv("NSGPU_P2P_EAGER") != nullptr;  // kernels one by one instead of graph replays
+  bool eager = env_eager();  // kernels one by one instead of graph replays
   // NSGPU_P2P_POISON=1: every device array is filled with 0xa5 bytes when allocated, before create initialises
   // it (a deterministic stand-in for device memory a previous engine dirtied: create must zero what it reads)
   bool poison = [] {
@@ -2647,8 +2633,6 @@ static int create_engine(const nsgpu_p2p_scenario *sc, const uint32_t *owner, in
     TRY(dalloc(h, &M.stx, NMAX));
     TRY(dalloc(h, &M.cpt, 2 * (size_t)NMAX));
     TRY(dalloc(h, &M.ldpd, LMAX));
-    const char *e = getenv("NSGPU_P2P_SDEF_KERNEL");  // (diagnostic: the accounting as its own kernel)
-    M.sdef_fold = (e && e[0] == '1') ? 0u : 1u;
   }
   // (k2_pa loads lrec / ldat entries speculatively and follows their record index: zeroed, every entry
   // stays < WTOT; the deferred pipeline's arrays start zeroed too, so a stale entry is always in range)
@@ -2878,26 +2862,14 @@ extern "C" int nsgpu_p2p_reset(nsgpu_p2p *h, void *stream) {
 
 // The window pipeline, in launch order (graph capture, eager runs and the per-kernel profile).
 namespace {
-constexpr int NKERN = 6;
-const char *const KERNEL_NAMES[NKERN] = {"k2_pa", "k2_handle", "k2_rank", "k2_scan", "k_tpatch", "k2_sdef"};
+constexpr int NKERN = 5;
+const char *const KERNEL_NAMES[NKERN] = {"k2_pa", "k2_handle", "k2_rank", "k2_scan", "k_tpatch"};
 // ev0 / ev1: optional HIP events the command processor records at the kernel's start and end
 // (hipExtLaunchKernelGGL: no separate marker packets between the pipeline's kernels).
 // Kernel k of the single engine's window (KERNEL_NAMES); a wide engine places its local records after
 // its handlers (k2_rank) and, traced, patches their trace uids (k_tpatch).  Returns
 // whether kernel k is part of this engine's window.
-// (NSGPU_P2P_PLAIN_LAUNCH=1, diagnostic: plain launches instead of hipExtLaunchKernelGGL where no events are asked)
-bool plain_launch() {
-  static const bool p = [] {
-    const char *e = getenv("NSGPU_P2P_PLAIN_LAUNCH");
-    return e && e[0] == '1';
-  }();
-  return p;
-}
-#define NSGPU_KLAUNCH(K, G, B, S, E0, E1, ...)                         \
-  do {                                                                \
-    if (plain_launch() && !(E0)) hipLaunchKernelGGL(K, G, B, 0, S, __VA_ARGS__); \
-    else hipExtLaunchKernelGGL(K, G, B, 0, S, E0, E1, 0, __VA_ARGS__);  \
-  } while (0)
+#define NSGPU_KLAUNCH(K, G, B, S, E0, E1, ...) hipExtLaunchKernelGGL(K, G, B, 0, S, E0, E1, 0, __VA_ARGS__)
 bool launch_kernel(nsgpu_p2p *h, int k, hipStream_t s, bool df, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr) {
   const bool wide = h->M.wide != 0;
   switch (k) {
@@ -2916,24 +2888,21 @@ bool launch_kernel(nsgpu_p2p *h, int k, hipStream_t s, bool df, hipEvent_t ev0 =
       else NSGPU_KLAUNCH(k2_rank<false>, dim3(RK_GRID), dim3(RKT), s, ev0, ev1, h->M);
       return true;
     case 3:
-      if (df) return false;  // (the deferred pipeline: df_book in k2_rank, the accounting in k2_sdef)
+      if (df) return false;  // (the deferred pipeline: df_book and the accounting (df_sdef) in k2_rank)
       if (wide) NSGPU_KLAUNCH(k2_scan<true>, dim3(1), dim3(SCAN_THREADS), s, ev0, ev1, h->M);
       else NSGPU_KLAUNCH(k2_scan<false>, dim3(1), dim3(SCAN_THREADS), s, ev0, ev1, h->M);
       return true;
-    case 4:
+    default:
       if (!(wide && h->M.trace)) return false;
       NSGPU_KLAUNCH(k_tpatch, dim3(64), dim3(256), s, ev0, ev1, h->M);
       return true;
-    default:  // k2_sdef(n) after k2_rank(n + 1): window n was staged by k2_pa(n + 1) (folded: k2_rank's blocks 1 .. NSDEF)
-      if (!df || h->M.sdef_fold) return false;
-      NSGPU_KLAUNCH(k2_sdef, dim3(NSDEF), dim3(SCAN_THREADS), s, ev0, ev1, h->M);
-      return true;
   }
 }
-// Diagnostic mode (eager launches with NSGPU_P2P_DEBUG=1): after every kernel the stream is drained (a
-// fault is reported with the kernel and window that raised it) and k_dbg checks the engine's invariants
-// (pool, free stack, fresh buffer, window records, children), so that a broken state is reported by the
-// kernel that made it instead of faulting a later one.
+#ifdef NSGPU_PHASE_PROF
+// The invariant checker (diagnostic build only).  Eager launches with NSGPU_P2P_DEBUG=1: after every kernel
+// the stream is drained (a fault is reported with the kernel and window that raised it) and k_dbg checks the
+// engine's invariants (pool, free stack, fresh buffer, window records, children), so that a broken state is
+// reported by the kernel that made it instead of faulting a later one.
 // In graph mode (NSGPU_P2P_DEBUG=2) k_dbg runs after every kernel of the replay (`at`: window << 8 | kernel)
 // and a broken invariant also ends the run (done = 2, error 1024) so that the next kernels do nothing.
 __global__ __launch_bounds__(256) void k_dbg(const P2PDev M, unsigned long long *out, unsigned long long at = 0) {
@@ -3026,23 +2995,22 @@ int launch_windows_dbg(nsgpu_p2p *h, hipStream_t s, bool df) {
   }
   return NSGPU_OK;
 }
+#endif
 int launch_windows(nsgpu_p2p *h, hipStream_t s, bool df, int nwin = NWIN) {
+#ifdef NSGPU_PHASE_PROF
   static const int dbg = [] {
     const char *e = getenv("NSGPU_P2P_DEBUG");
     return e ? atoi(e) : 0;
   }();
   if ((dbg == 1 && h->eager) || (dbg == 2 && !h->eager)) return launch_windows_dbg(h, s, df);
+#endif
   for (int w = 0; w < nwin; w++)
     for (int k = 0; k < NKERN; k++) launch_kernel(h, k, s, df);
   return NSGPU_OK;
 }
-// The deferred pipeline is used for untraced single wide engines (NSGPU_P2P_NODEFER=1: never).
+// The deferred pipeline is used for untraced single wide engines.
 bool df_usable(const nsgpu_p2p *h) {
-  static const bool off = [] {
-    const char *e = getenv("NSGPU_P2P_NODEFER");
-    return e && e[0] == '1';
-  }();
-  return h->M.wide && !h->M.dist && !h->M.trace && h->M.maxc <= PROV_MAXC && h->M.n_nodes < (1u << 24) && !off;
+  return h->M.wide && !h->M.dist && !h->M.trace && h->M.maxc <= PROV_MAXC && h->M.n_nodes < (1u << 24);
 }
 // When the deferred pipeline paused itself (a sorted run, a compaction, a host closure) after window n's
 // bookkeeping: window n's dispatch accounting from its records (k2_scan<true, true>: sinfo for the next
@@ -3250,7 +3218,9 @@ static int build_graph(nsgpu_p2p *h, bool df = false, bool tail = false) {
   // device (Ctl), so one instantiated graph serves every run of this engine
   hipGraphExec_t &gx = tail ? h->gtail[df ? 1 : 0] : df ? h->gexec_df : h->gexec;
   hipGraph_t g = nullptr;
-  if (const int rd = dbg_alloc()) return rd;
+#ifdef NSGPU_PHASE_PROF
+  if (const int rd = dbg_alloc()) return rd;  // (the invariant checker's buffer: allocated before any capture)
+#endif
   NSGPU_HIP(hipStreamBeginCapture(h->s, h->M.dist ? hipStreamCaptureModeRelaxed : hipStreamCaptureModeThreadLocal));
   int rc = NSGPU_OK;
   if (h->M.dist) rc = launch_windows_dist(h, h->s);
@@ -3279,18 +3249,6 @@ static int engine_error(uint32_t err) {
                                  "beyond the deferred pipeline's range (internal), 2048 = the uid counter would pass "
                                  "0xfffffffe: DefaultSimulatorImpl's uint32 m_uid wraps there, which the engine does "
                                  "not replicate)", err);
-}
-
-// The run control into a pinned snapshot after a replay: a copy-engine transfer (hipMemcpyAsync), or with
-// NSGPU_P2P_SNAPK=1 one wave of k_snap on the same queue (no hand-over to the copy engine between replays).
-static hipError_t snapshot(const Ctl *c, Ctl *out, hipStream_t s) {
-  static const bool kern = [] {
-    const char *e = getenv("NSGPU_P2P_SNAPK");
-    return e && e[0] == '1';
-  }();
-  if (!kern) return hipMemcpyAsync(out, c, sizeof(Ctl), hipMemcpyDeviceToHost, s);
-  hipLaunchKernelGGL(k_snap, dim3(1), dim3(64), 0, s, c, out);
-  return hipGetLastError();
 }
 
 // Replays the single engine's window pipeline until the run is over (done >= 2) or the pipeline paused
@@ -3335,7 +3293,8 @@ static int drive(nsgpu_p2p *h, bool *paused) {
     }
     queued = nw;
     df_of[cur] = df;
-    NSGPU_HIP(snapshot(h->M.C, &h->snap[cur], h->s));
+    // (the run control into a pinned snapshot after the replay: a copy-engine transfer)
+    NSGPU_HIP(hipMemcpyAsync(&h->snap[cur], h->M.C, sizeof(Ctl), hipMemcpyDeviceToHost, h->s));
     NSGPU_HIP(hipEventRecord(h->ev[cur], h->s));
     if (have_prev) {
       NSGPU_HIP(hipEventSynchronize(h->ev[cur ^ 1]));
@@ -3565,6 +3524,7 @@ extern "C" int nsgpu_p2p_run(nsgpu_p2p *h, void *stream) {
   NSGPU_HIP(hipEventSynchronize(h->t1));
   NSGPU_HIP(hipStreamSynchronize(h->s));
   NSGPU_HIP(hipEventElapsedTime(&h->last_ms, h->t0, h->t1));
+#ifdef NSGPU_PHASE_PROF
   if (err & 1024u) {  // (debug mode 2: a graph-resident check stopped the run)
     unsigned long long o[4] = {};
     NSGPU_HIP(hipMemcpy(o, g_dbg_out, sizeof(o), hipMemcpyDeviceToHost));
@@ -3572,6 +3532,7 @@ extern "C" int nsgpu_p2p_run(nsgpu_p2p *h, void *stream) {
                      "C.windows %llu): %llu %llu", o[0], KERNEL_NAMES[o[3] & 0xff], (o[3] >> 8) & 0xff, o[3] >> 32, o[1],
                      o[2]);
   }
+#endif
   if (err) return engine_error(err);
   NSGPU_HIP(hipEventRecord(h->ev[0], h->s));
   NSGPU_HIP(hipStreamWaitEvent(cs, h->ev[0], 0));
@@ -3938,8 +3899,7 @@ static int group_host_step(nsgpu_p2p_group *g, const Ctl &c0) {
 // Runs every partition to the end of the simulation (blocking), like nsgpu_p2p_run.
 extern "C" int nsgpu_p2p_group_run(nsgpu_p2p_group *g, void *stream) {
   if (!g) return set_error(NSGPU_EINVAL, "nsgpu_p2p_group_run: null");
-  // NSGPU_P2P_EAGER: the replays' kernels launched one by one (rocprofv3's kernel tracer does not follow graphs)
-  static const bool eager = getenv("NSGPU_P2P_EAGER") != nullptr;
+  static const bool eager = env_eager();
   if (!eager && !g->gexec) {
     hipGraph_t gr = nullptr;
     NSGPU_HIP(hipStreamBeginCapture(g->s, hipStreamCaptureModeThreadLocal));

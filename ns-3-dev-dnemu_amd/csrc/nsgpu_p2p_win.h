@@ -28,10 +28,7 @@ enum : uint32_t { MODE_NORMAL = 0, MODE_RUN = 1, MODE_SORT = 2, MODE_COMPACT = 3
 constexpr uint64_t TOMB = ~0ull;        // ev_ts of a free pool slot
 constexpr uint32_t NOSRC = 0xffffffffu;
 constexpr int NHUB = 32;                // hub blocks of k2_handle
-#ifndef NMB_N
-#define NMB_N 128
-#endif
-constexpr int NMB = NMB_N;              // maintenance blocks of k2_handle
+constexpr int NMB = 128;                // maintenance blocks of k2_handle
 constexpr int MAXHUB = WCAP / (CH + 1) + 1;
 constexpr int K2_GRID_W = NHB + NHUB + NMB;  // holders, hub blocks, pool maintenance
 constexpr int K2_GRID = K2_GRID_W + NRB;       // + rank tiles (single engine; partitioned: k_gtile ranks)
@@ -55,9 +52,9 @@ __device__ __forceinline__ Ctl *vec_ctl(Ctl *p) {
   asm volatile("" : "+v"(g));
   return (Ctl *)g;  // (a global pointer: global, not flat, loads)
 }
-// a staged rank's position in the stage arrays and cpt (k2_sdef's thread r / 8 loads it as its (r % 8)-th)
+// a staged rank's position in the stage arrays and cpt (df_sdef's thread r / 8 loads it as its (r % 8)-th)
 __device__ __forceinline__ uint32_t stg_pos(uint32_t r) { return (r & 7u) * STG_NT + (r >> 3); }
-// a rank's word in k2_sdef's per-rank LDS arrays: one pad word per 64, so a wave's 8-strided accesses
+// a rank's word in df_sdef's per-rank LDS arrays: one pad word per 64, so a wave's 8-strided accesses
 // (lane l, rank 8l + q) fall in 64 different banks
 __device__ __forceinline__ uint32_t lds_pad(uint32_t r) { return r + (r >> 6); }
 constexpr int NMAX_PAD = NMAX + NMAX / 64;
@@ -459,7 +456,7 @@ inline int pa_grid_rt(const P2PDev &M) {
   return pa_grid<WIDE>() + (M.pool_cap > (1ull << 20) ? GRID_POOL_BIG - GRID_POOL : 0);
 }
 // DF: the deferred pipeline's variant (single wide engine): when the last window is staged (C.pdf) its records
-// are written in rank order to the stage for k2_sdef and its children get provisional uids (no dispatch log
+// are written in rank order to the stage for df_sdef and its children get provisional uids (no dispatch log
 // here); the pool's provisional uids of the window before it are resolved as the pool is read.
 template <bool DIST, bool WIDE, bool DF = false>
 __global__ __launch_bounds__(TB) void k2_pa(const P2PDev M) {
@@ -533,7 +530,7 @@ __global__ __launch_bounds__(TB) void k2_pa(const P2PDev M) {
   uint32_t rk2[2] = {0, 0}, ninl0 = 0, lpd = 0;
   if (DF && WIDE && g >= (uint64_t)WCAP && slot_role) {
     ldd = M.ldat[g - WCAP];
-    lpd = M.ldpd[g - WCAP];  // (its parent as a dense index: k2_sdef finds the parent's rank in LDS)
+    lpd = M.ldpd[g - WCAP];  // (its parent as a dense index: df_sdef finds the parent's rank in LDS)
   }
   // (a speculative entry past the last window's records is followed too: clamped into the record space)
   const uint32_t rec =
@@ -565,7 +562,7 @@ __global__ __launch_bounds__(TB) void k2_pa(const P2PDev M) {
     if (blockIdx.x == 0 && threadIdx.x < M.nranks) x2hdr(M, M.x2_send, threadIdx.x)->n = 0;  // (X2 has sent them)
     if (c_prep) return;
   }
-  // k2_sdef's flag, every window (its blocks only read it: a block may start after another finished)
+  // df_sdef's flag, every window (its blocks only read it: a block may start after another finished)
   if (DF && g == 0)
     C.sflag = (c_done < 2 && c_mode < MODE_SORT && c_mode != MODE_RUN && c_pdf && c_pvalid)
                   ? 1u | (uint32_t)(((c_wn - 1) & 3) << 1) : 0u;
@@ -615,10 +612,9 @@ __global__ __launch_bounds__(TB) void k2_pa(const P2PDev M) {
     C.hcap = hcap;
   }
   const uint32_t pW = c_pvalid ? c_pW : 0;
-#ifndef PA_PPT
-#define PA_PPT 2  // (4: config 4 149.5 M ev/s, 2: 153 M — twice the pool blocks, each half the claims and writes)
-#endif
-  constexpr int PPT = PA_PPT;  // (pool entries a thread reads a chunk)
+  // (pool entries a thread reads a chunk; 4: config 4 149.5 M ev/s, 2: 153 M — twice the pool blocks, each half the
+  // claims and writes)
+  constexpr int PPT = 2;
   {  // a pool block past the pool's end (most of them: the pool holds a few thousand entries) has nothing to do
     const uint64_t pb = blockIdx.x - (uint64_t)(NSGB + rrb);
     if (!slot_block && !remote_role && partition && !run && !drun && !(DIST && dtrim && pb < (uint64_t)(WCAP / TB)) &&
@@ -644,16 +640,16 @@ __global__ __launch_bounds__(TB) void k2_pa(const P2PDev M) {
     const bool vs = slot_role && (g < (uint64_t)WCAP ? g < pW : (c_pvalid && g - WCAP < c_plt));
     const uint32_t s = rec;
     const bool loc = WIDE && g >= (uint64_t)WCAP;
-    const bool stg = DF && c_pdf;  // the last window is staged for k2_sdef (deferred dispatch accounting)
+    const bool stg = DF && c_pdf;  // the last window is staged for df_sdef (deferred dispatch accounting)
     const uint64_t rel = (stg && loc) ? (uint64_t)ldd.z : spk >> 32;
     const uint64_t t = c_ptmin + rel;
     const uint32_t pn = (uint32_t)((c_wn - 1) & 1);  // (DF: the last window's parity)
     const uint32_t srank = pn ? rk2[1] : rk2[0];
     BLK_MARK(34, c_win);  // bound, publish_bound
     if (stg && vs && srank >= (uint32_t)NMAX) atomicOr(M.error, 256u);
-    const bool sw = stg && vs && srank < (uint32_t)NMAX;  // the record is staged at its rank (k2_sdef logs it)
+    const bool sw = stg && vs && srank < (uint32_t)NMAX;  // the record is staged at its rank (df_sdef logs it)
     if (sw) {
-      // a provisional uid (a child of the window before) resolves now: k2_sdef ran for that window.  The
+      // a provisional uid (a child of the window before) resolves now: df_sdef ran for that window.  The
       // prefix's load is issued here and the stage is written after the children, so its trip overlaps theirs
       uint32_t ku = (uint32_t)spk;
       if (!loc && (ku & PROV)) {
@@ -702,7 +698,7 @@ __global__ __launch_bounds__(TB) void k2_pa(const P2PDev M) {
           e.uid = stg ? prov_uid(c_wn - 1, srank, j) : uid0 + si.z + j;
           if ((e.kind & 0xffu) == K_FWD_UP) {  // leaf: dispatched inside its window (or never), not queued
             if (stg) {
-              if (rel < ilim && srank < (uint32_t)NMAX) {  // (k2_sdef logs it after its group)
+              if (rel < ilim && srank < (uint32_t)NMAX) {  // (df_sdef logs it after its group)
                 if (ii) M.sleaf[(uint64_t)srank * M.maxc + ii] = make_uint2(e.ctx, j);
                 else st_pending.par = e.ctx | (j << 24);  // (a gen-0 record's: local records have no leaves)
                 ii++;
@@ -818,7 +814,7 @@ __global__ __launch_bounds__(TB) void k2_pa(const P2PDev M) {
         nts[q] = TOMB;
         if (i < P) nts[q] = M.ev_ts[0][i], nuid[q] = M.ev_uid[0][i], nkind[q] = M.ev_kind[0][i];
       }
-      if (DF) {  // children the window before the last one parked: their uids resolve now (k2_sdef ran for it)
+      if (DF) {  // children the window before the last one parked: their uids resolve now (df_sdef ran for it)
 #pragma unroll
         for (int q = 0; q < PPT; q++) {
           const uint64_t i = c0 + (uint64_t)q * TB + threadIdx.x;
@@ -2419,20 +2415,14 @@ __device__ void df_book(const P2PDev &M, Ctl &C, bool ranked, uint32_t W, uint32
 // DF: the deferred pipeline's variant: it reads k2_handle's snapshot (rk_*), always runs for a formed window,
 // copies the window's keys / contexts for the next k2_pa (pwkey / pwctx: k2_scan's job in the other
 // pipeline), and its block 0 does the window's bookkeeping (df_book); the dispatch accounting (log, digest,
-// uid resolution) is deferred to k2_sdef once the next k2_pa has staged the records in rank order.
+// uid resolution) is deferred to df_sdef once the next k2_pa has staged the records in rank order.
 template <int NT>
 __device__ void df_sdef(const P2PDev &M, Ctl &C, uint32_t b, uint32_t nsb);
 constexpr int RKT_DF = 1024;              // the deferred pipeline's k2_rank blocks: SUBS tiles at once
-#ifndef NSDEF_N
-#define NSDEF_N 4
-#endif
-#ifndef RK_GRID_DF_N
-#define RK_GRID_DF_N 256
-#endif
-constexpr int NSDEF = NSDEF_N;            // blocks of the deferred accounting (df_sdef: each scans the whole
+constexpr int NSDEF = 4;                  // blocks of the deferred accounting (df_sdef: each scans the whole
                                           // window, then resolves / logs / digests a quarter of its records)
 static_assert(NSDEF == 1 || NSDEF == 2 || NSDEF == 4 || NSDEF == 8, "a thread's NMAX / NT records split evenly");
-constexpr int RK_GRID_DF = RK_GRID_DF_N;    // one 1024-thread block per CU (~150 KB of LDS each): bookkeeping, accounting, tiles
+constexpr int RK_GRID_DF = 256;           // one 1024-thread block per CU (~150 KB of LDS each): bookkeeping, accounting, tiles
 template <bool DF>
 __global__ __launch_bounds__(DF ? RKT_DF : RKT) void k2_rank(const P2PDev M) {
   constexpr int NT = DF ? RKT_DF : RKT, SUBS = NT / RKT;
@@ -2446,7 +2436,7 @@ __global__ __launch_bounds__(DF ? RKT_DF : RKT) void k2_rank(const P2PDev M) {
   // ranking
   if constexpr (DF) {
     if (blockIdx.x >= 1 && blockIdx.x <= (uint32_t)NSDEF) {
-      if (M.sdef_fold) df_sdef<NT>(M, C, blockIdx.x - 1, NSDEF);
+      df_sdef<NT>(M, C, blockIdx.x - 1, NSDEF);
       BLK_REC(2, c_win);  // (diagnostic build: k2_scan's per-block slot, unused by the deferred pipeline)
       return;
     }
@@ -2626,7 +2616,7 @@ __global__ __launch_bounds__(DF ? RKT_DF : RKT) void k2_rank(const P2PDev M) {
 
 // The deferred pipeline's window bookkeeping (k2_rank<true>'s block 0; NT threads): k2_scan's run
 // bookkeeping without its scan — the child totals come from k2_handle (acc_tc / acc_tinl), the dispatch
-// bases of the window go to winfo for k2_sdef, and the next k2_pa stages the window (pdf = 1).  The
+// bases of the window go to winfo for df_sdef, and the next k2_pa stages the window (pdf = 1).  The
 // free-stack move and the hub resets are the block's; the rest is thread 0's.
 template <int NT>
 __device__ void df_book(const P2PDev &M, Ctl &C, bool ranked, uint32_t W, uint32_t Lt, uint64_t wn) {
@@ -2729,14 +2719,14 @@ __device__ void df_book(const P2PDev &M, Ctl &C, bool ranked, uint32_t W, uint32
   }
 }
 
-// ---- k2_sdef: a deferred window's dispatch accounting (DF pipeline; one block) ----
+// ---- df_sdef: a deferred window's dispatch accounting (DF pipeline; k2_rank<true>'s accounting blocks) ----
 // Window n's records, staged in rank order by the next k2_pa: exclusive scans of (children, inline children,
 // same-ts group heads) give each record its dispatch rank (K0 + rank + the inline leaves of earlier ts groups)
 // and child prefix; a local record's uid resolves through its parent's rank and this window's prefixes (k2_pa
 // resolved the provisional ones at staging); the log and digest get every record and leaf; the child prefixes
 // are kept (cpt) for the provisional uids of window n's children.  Afterwards the window's rank accumulators
 // are cleared (their parity is window n + 2's).
-// NSDEF blocks of NT threads (k2_rank<true>'s blocks 1 .. NSDEF, or the k2_sdef kernel): each scans the whole
+// NSDEF blocks of NT threads (k2_rank<true>'s blocks 1 .. NSDEF): each scans the whole
 // window and resolves / logs / digests its share (every NSDEF-th record of a thread).  Every record is loaded once, into
 // registers (RPT consecutive ranks a thread), in the same memory trip as the run control; the scan's per-rank
 // results go to LDS (child / inline prefixes, the group of each rank, group starts, and the rank of each dense
@@ -2748,7 +2738,7 @@ __device__ void df_sdef(const P2PDev &M, Ctl &C, uint32_t b, uint32_t nsb) {
 #ifdef NSGPU_PHASE_PROF
   const uint64_t c_win = C.rk_win - 1;  // (diagnostic build: marks 22..30 in the sampled window)
 #endif
-  static_assert(NT == (int)STG_NT, "k2_sdef's rank slices are the stage layout's");
+  static_assert(NT == (int)STG_NT, "df_sdef's rank slices are the stage layout's");
   constexpr int RPT = NMAX / NT;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   WInfo wa[4];  // (all four: loaded with the flag, picked by it)
@@ -2894,9 +2884,6 @@ __device__ void df_sdef(const P2PDev &M, Ctl &C, uint32_t b, uint32_t nsb) {
   for (uint32_t i = b * NT + tid; i < w.Lt; i += nsb * NT) M.lrank[(uint64_t)pn * LMAX + i] = 0;
 
   BLK_MARK(30, c_win);  // clears
-}
-__global__ __launch_bounds__(SCAN_THREADS) void k2_sdef(const P2PDev M) {
-  df_sdef<SCAN_THREADS>(M, *M.C, blockIdx.x, gridDim.x);
 }
 
 // ---- k2_scan: rank order; child / inline prefixes, same-ts groups, run bookkeeping ----
@@ -3594,14 +3581,6 @@ __global__ void k_host_resume(const P2PDev M, uint64_t hts, uint32_t huid, uint3
 }
 
 __global__ void k_set_uid(const P2PDev M, uint32_t uid) { M.C->uid = uid; }
-// The run control copied into a pinned host snapshot by one wave on the engine's stream (drive's per-replay
-// check without a copy-engine transfer between two graph replays; the event after it publishes the stores)
-static_assert(sizeof(Ctl) % 4 == 0, "Ctl in words");
-__global__ __launch_bounds__(64) void k_snap(const Ctl *__restrict__ c, Ctl *__restrict__ out) {
-  const uint32_t *s = reinterpret_cast<const uint32_t *>(c);
-  uint32_t *d = reinterpret_cast<uint32_t *>(out);
-  for (uint32_t i = threadIdx.x; i < (uint32_t)(sizeof(Ctl) / 4); i += 64) d[i] = s[i];
-}
 
 // A host application's UdpSocket::Send of one datagram of application `a`'s flow, made by the host
 // closure running now (uid `cur`): the same steps as OnOffApplication::SendPacket's send

@@ -1251,7 +1251,6 @@ static int wifi_create(const nsgpu_wifi_scenario *sc, int rx_log, int64_t j0, in
       int ncu = 0;
       if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu < 1) ncu = 256;
       size_t P = (size_t)((std::max<int64_t>(NO, 1) + 4 * (int64_t)ncu - 1) / (4 * (int64_t)ncu));
-      if (const char *e = getenv("NSGPU_WIFI_PHYS_PER_BLOCK")) P = (size_t)atoi(e);  // (diagnostic sweeps)
       P = std::max<size_t>(1, std::min(P, pmax));
       if (pmax >= 1) {
         h->lds_ok = true;

@@ -11,7 +11,7 @@
 // draw (:783) is the host's: each EndReceive's (snr, per) goes back to it (nsgpu_wifil_read_ends).
 //
 // Epochs.  The host runtime (nsgpu_sim) owns the uid counter and the dispatch order; before it runs a host
-// closure with key (T, u) it advances the device to that key (nsgpu_wifil_advance): every phy's lane runs
+// closure with key (T, u) it advances the device to that key (nsgpu_wifil_advance): every phy's wave runs
 // its pending Receive / EndReceive events with keys below (T, u), in (ts, uid) order, then the epoch's
 // syncs get their EndReceive uids.  A host closure's SendPacket (nsgpu_wifil_send) applies the sender's
 // state switch at once and queues one Receive per receiver, with the uids the runtime hands out.
@@ -25,7 +25,6 @@
 // Receive queue (sorted by (arrival, uid)) and up to LPE_CAP pending EndReceive records.
 #include <algorithm>
 #include <atomic>
-#include <chrono>
 #include <cstdio>
 #include <cstring>
 #include <vector>
@@ -41,7 +40,6 @@ constexpr uint32_t END_STAGE = 128;  // EndReceive records an epoch returns with
 constexpr size_t STAT_HDR = 32;      // the status block: counters (5 x u32), the epoch flag (word 6), then the ends
 static_assert(sizeof(nsgpu_wifil_end) % 8 == 0 && STAT_HDR % 8 == 0, "status block alignment");
 constexpr uint32_t WE_TX_IN_TX = 1, WE_NICAP = 2, WE_RQCAP = 4, WE_PECAP = 8, WE_CAP = 16, WE_CKCAP = 32;
-constexpr int NB = 8;  // ring entries loaded per batch
 
 struct LNi {  // InterferenceHelper::NiChange (interference-helper.cc:91-110)
   int64_t t;
@@ -358,18 +356,6 @@ __device__ __forceinline__ uint32_t wave_incscan32(uint32_t v) {
   return v;
 }
 
-// One index of counter *ctr per calling lane: the wave's active lanes share one atomic (every phy's lane
-// appending to the same epoch lists one atomic each serialized on the counter's line: ~11 ns apiece).
-__device__ __forceinline__ uint32_t wave_alloc(uint32_t *ctr) {
-  const uint64_t m = __ballot(1);
-  const int lane = threadIdx.x & 63;
-  const int first = __ffsll((unsigned long long)m) - 1;
-  uint32_t base = 0;
-  if (lane == first) base = atomicAdd(ctr, (uint32_t)__popcll(m));
-  base = (uint32_t)__builtin_amdgcn_readlane((int)base, first);  // (first is uniform)
-  return base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-}
-
 // YansWifiChannel::Send's delivery of transmission t (index k, from the closure's uid base) to phy j (not the
 // sender): its Receive — ConstantSpeed delay, the loss chain + RxGain, DbmToW, the receiver loop's uid.
 __device__ __forceinline__ bool reception(const WDev &D, int64_t j, const LTx &t, uint32_t k, double dbm, uint32_t base,
@@ -393,46 +379,6 @@ struct SendBatch {
   uint32_t base[NSEND];
 };
 
-// ---- the NiChanges ring of one phy (RingNi of nsgpu_wifi.hip: time-sorted, eager prefix cursor) ----
-__device__ __forceinline__ void ni_insert(LNi *ring, uint32_t head, uint32_t &len, uint32_t m, int64_t t, double d) {
-  // AddNiChangeEvent (interference-helper.cc:378-383): at upper_bound (time).  The entries after it (a
-  // start while receiving passes every pending end: ~100 of them) move up one place, read NB at a time
-  // from the tail (one memory trip per NB, not per entry)
-  uint32_t q = len;
-  while (q > 0) {
-    const uint32_t nb = q < (uint32_t)NB ? q : (uint32_t)NB;
-    LNi e[NB];
-#pragma unroll
-    for (int u = 0; u < NB; u++) e[u] = ring[(head + q - 1 - u) & m];  // (past the head: masked, unused)
-    uint32_t k = 0;  // the batch's entries after t: a run from the tail
-#pragma unroll
-    for (int u = 0; u < NB; u++)
-      if ((uint32_t)u < nb && k == (uint32_t)u && e[u].t > t) k++;
-#pragma unroll
-    for (int u = 0; u < NB; u++)
-      if ((uint32_t)u < k) ring[(head + q - u) & m] = e[u];
-    q -= k;
-    if (k < nb) break;
-  }
-  ring[(head + q) & m] = LNi{t, d};
-  len++;
-}
-template <bool LE>
-__device__ __forceinline__ void cursor_advance(const LNi *ring, uint32_t head, uint32_t len, uint32_t m, int64_t lim,
-                                               uint32_t &cur_n, double &cur_s) {
-  while (cur_n < len) {
-    LNi e[NB];
-#pragma unroll
-    for (int u = 0; u < NB; u++) e[u] = ring[(head + cur_n + u) & m];
-#pragma unroll
-    for (int u = 0; u < NB; u++) {
-      if (cur_n >= len || (LE ? e[u].t > lim : e[u].t >= lim)) return;
-      cur_s += e[u].d;
-      cur_n++;
-    }
-  }
-}
-
 // EndReceive's order key against another pending EndReceive of the same phy (ts, then uid; a uid of the
 // running epoch is above every known one, and those order by their syncing Receives' keys).
 __device__ __forceinline__ bool pe_before(const LPe &a, const LPe &b) {
@@ -448,268 +394,26 @@ __device__ __forceinline__ void mir_put(const WDev &D, int64_t j, const WMir &m0
   if (P.endTx != m0.endTx || P.endRx != m0.endRx || P.endCca != m0.endCca || P.rxing != m0.rxing) D.mir[j] = mir_of(P);
 }
 
-// One phy's events of the epoch: every pending Receive / EndReceive with a key below (bts, buid).
 #ifdef NSGPU_PHASE_PROF
-// diagnostic build: [0] sum over epochs of the slowest lane's time, [1] sum of lane times, [2] lanes, [3] events,
-// [4] sum over epochs of the most events one lane ran, [5] epochs, [6] max lane time, [7] its events
-__device__ unsigned long long g_wl_ph[8];
-__device__ unsigned long long g_wl_ep[2];  // the current epoch's slowest lane time / most events (reset by host)
-// k_wl_stepw's waves, recorded without atomics for WREC_E epochs from epoch g_wtarget on (the epoch counter
-// g_wepoch counts k_wl_prof_epoch launches): per wave (start, loads done, loop done, end) s_memtime stamps and
-// its events
+// diagnostic build: k_wl_stepw's waves, recorded without atomics for WREC_E epochs from epoch g_wtarget on (the
+// epoch counter g_wepoch counts k_wl_prof_epoch launches): per wave (start, loads done, loop done, end)
+// s_memtime stamps and its events
 constexpr uint32_t WREC_E = 8, WREC_P = 16384;
 __device__ unsigned long long g_wrec[WREC_E][WREC_P][5];
 __device__ uint32_t g_wepoch, g_wtarget;
 #endif
-__global__ __launch_bounds__(64) void k_wl_step(const WDev D, uint64_t bts, uint32_t buid) {
-  const int64_t j = D.j0 + (int64_t)blockIdx.x * 64 + threadIdx.x;
-  if (j >= D.j0 + D.nown) return;
-#ifdef NSGPU_PHASE_PROF
-  const uint64_t pt0 = __builtin_amdgcn_s_memrealtime();
-  uint32_t pev = 0;
-#endif
-  LPhy P = D.ps[j];
-  const WMir m0 = mir_of(P);
-  LNi *ring = D.ni + (uint64_t)j * (D.ni_mask + 1);
-  LRx *rq = D.rq + (uint64_t)j * (D.rq_mask + 1);
-  LPe *pe = D.pe + (uint64_t)j * LPE_CAP;
-  const uint32_t m = D.ni_mask, ctx = D.node[j];
-  uint32_t err = 0;
-  for (;;) {
-    // the next pending EndReceive and the next Receive
-    int e = -1;
-    LPe eb{};
-    for (int q = 0; q < LPE_CAP; q++) {
-      const LPe c = pe[q];
-      if (c.used && (e < 0 || pe_before(c, eb))) e = q, eb = c;
-    }
-    const bool hr = P.rq_len > 0;
-    LRx r{};
-    if (hr) r = rq[P.rq_head & D.rq_mask];
-    bool take_r;
-    if (hr && e >= 0) take_r = r.at < eb.ts || (r.at == eb.ts && (eb.euid == NONE || r.uid < eb.euid));
-    else if (hr) take_r = true;
-    else if (e >= 0) take_r = false;
-    else break;
-    if (take_r) {
-      if (!(r.at < bts || (r.at == bts && r.uid < buid))) break;
-    } else {
-      if (!(eb.ts < bts || (eb.ts == bts && eb.euid != NONE && eb.euid < buid))) break;
-    }
-    if (!take_r) {  // ---- YansWifiPhy::EndReceive (yans-wifi-phy.cc:770-799)
-      const int64_t nw = (int64_t)eb.ts;
-      nsgpu_wifil_end rec{eb.ts, eb.euid, (uint32_t)j, 0.0, 0.0, eb.tx, eb.can ? (uint32_t)NSGPU_WIFI_END_CANCELLED : 0u,
-                          eb.can ? 0.0 : eb.w};
-      LEck eck{0, NONE, 0.0};
-      P.c.end++;
-      if (eb.can) {  // EventImpl::Invoke skips a cancelled event (event-impl.cc:40-46); still dispatched
-        P.c.end_cancelled++;
-      } else {
-        // InterferenceHelper::CalculateSnrPer (interference-helper.cc:336-353): ni = (start, m_firstPower), the
-        // list after the event's own start entry (the ring's head: no fold while receiving) up to its end
-        // entry, (end, 0) — CalculateNoiseInterferenceW (:229-243) — then CalculatePer's walk (:257-334)
-        const LTx t = D.tx[eb.tx];
-        const Mode pm = make_mode(t.mc, t.rate, t.bw), hm = header_mode(pm, t.preamble);
-        const double noise0 = P.firstPower;
-        rec.snr = snr_of(D, eb.w, noise0, pm);
-        const int64_t t0 = (int64_t)eb.sts;
-        const int64_t hdrStart = t0 + (int64_t)preamble_us(t.mc, pm.bw, t.preamble) * 1000;
-        const int64_t payStart = hdrStart + (int64_t)header_us(t.mc, pm.bw, t.preamble) * 1000;
-        // The walk's sequential part (the noise sums, the chunk bounds) runs here; the chunks' error-rate
-        // models (~10 pow / erfc calls each, ~100-200 chunks an EndReceive) run lane-parallel in k_wl_mid,
-        // which multiplies them in this order.  A zero-length chunk is 1.0 (CalculateChunkSuccessRate) and
-        // is not recorded.  Without room in the chunk pool the product is formed here.
-        const uint32_t need = 2 * P.len + 2;
-        const uint32_t cs = atomicAdd(&D.cnt[4], need);
-        const bool defer = (uint64_t)cs + need <= D.ck_cap;
-        uint32_t cn = 0;
-        double psr = 1.0, noiseW = noise0;
-        auto ck = [&](int64_t dur, bool hdr) {
-          if (defer) {
-            if (dur != 0) D.ck[cs + cn++] = LCk{noiseW, (int64_t)((uint64_t)dur << 1) | (hdr ? 1 : 0)};
-          } else {
-            psr *= hdr ? chunk(D, snr_of(D, eb.w, noiseW, hm), dur, hm) : chunk(D, snr_of(D, eb.w, noiseW, pm), dur, pm);
-          }
-        };
-        int64_t previous = t0;
-        uint32_t q = 1;
-        LNi nb[NB];  // the ring read NB entries a trip (the walk itself stays one entry at a time)
-        uint32_t nbq = q - (uint32_t)NB;  // (q - nbq >= NB: the first entry loads a batch)
-        for (bool last = false; !last;) {
-          int64_t current;
-          double delta;
-          if (q < P.len) {
-            if (q - nbq >= (uint32_t)NB) {
-              nbq = q;
-#pragma unroll
-              for (int u = 0; u < NB; u++) nb[u] = ring[(P.head + q + u) & m];
-            }
-            const LNi en = nb[q - nbq];
-            if (en.t == nw && eb.w == -en.d) {
-              current = nw, delta = 0.0, last = true;  // (the event's end entry: the closing (end, 0))
-            } else {
-              current = en.t, delta = en.d;
-            }
-            q++;
-          } else {
-            current = nw, delta = 0.0, last = true;
-          }
-          if (previous >= payStart) {
-            ck(current - previous, false);
-          } else if (previous >= hdrStart) {
-            if (current >= payStart) {
-              ck(payStart - previous, true);
-              ck(current - payStart, false);
-            } else {
-              ck(current - previous, true);
-            }
-          } else {
-            if (current >= payStart) {
-              ck(payStart - hdrStart, true);
-              ck(current - payStart, false);
-            } else if (current >= hdrStart) {
-              ck(current - hdrStart, true);
-            }
-          }
-          noiseW += delta;
-          previous = current;
-        }
-        eck = LEck{cs, defer ? cn : NONE, eb.w};
-        rec.per = 1 - psr;  // (deferred: k_wl_mid overwrites it)
-        P.rxing = 0;  // NotifyRxEnd (); SwitchFromRxEndOk / Error -> DoSwitchFromRx (wifi-phy-state-helper.cc:391-402)
-      }
-      const uint32_t sl = eb.euid == NONE ? eb.sslot : NONE;
-      const uint32_t ei = wave_alloc(&D.cnt[2]);
-      if (ei < D.end_cap) {
-        D.ends[ei] = rec;
-        D.end_sslot[ei] = sl;
-        D.eck[ei] = eck;
-      } else {
-        err |= WE_CAP;
-      }
-      const uint32_t vi = wave_alloc(D.evc + (blockIdx.x % EV_STRIPES) * EV_STRIDE);
-      if (vi < D.ev_scap) D.ev[(blockIdx.x % EV_STRIPES) * D.ev_scap + vi] = LEv{eb.ts, eb.euid, ctx, sl, 0};
-      else err |= WE_CAP;
-      pe[e].used = 0;
-      if (P.live == (uint32_t)e) P.live = NONE;
-#ifdef NSGPU_PHASE_PROF
-      pev++;
-#endif
-      continue;
-    }
-    // ---- YansWifiChannel::Receive -> YansWifiPhy::StartReceivePacket (yans-wifi-phy.cc:399-496)
-    P.rq_head++;
-    P.rq_len--;
-    const int64_t nw = (int64_t)r.at;
-    const int64_t endNew = nw + D.tx[r.tx].dur;
-    if (P.len + 2 > m + 1) {
-      err |= WE_NICAP;
-      break;
-    }
-    // InterferenceHelper::AppendEvent (interference-helper.cc:192-212)
-    if (!P.rxing) {  // fold the entries up to upper_bound (now) into m_firstPower; the new entry first
-      cursor_advance<true>(ring, P.head, P.len, m, nw, P.cur_n, P.cur_s);
-      P.head = (P.head + P.cur_n) & m;
-      P.len -= P.cur_n;
-      P.cur_n = 0;
-      P.head = (P.head - 1) & m;
-      ring[P.head] = LNi{nw, r.w};
-      P.len++;
-      P.firstPower = P.cur_s;
-    } else {
-      ni_insert(ring, P.head, P.len, m, nw, r.w);
-    }
-    ni_insert(ring, P.head, P.len, m, endNew, -r.w);
-    P.ni_max = P.len > P.ni_max ? P.len : P.ni_max;
-    const int st = P.endTx > nw ? 2 : P.rxing ? 1 : P.endCca > nw ? 3 : 0;  // GetState (:159-183)
-    bool maybe = false;
-    P.c.rx++;
-    if (st == 1 || st == 2) {  // drop; noise after the current Rx / Tx (:431-457)
-      if (st == 1) P.c.drop_rx++;
-      else P.c.drop_tx++;
-      int64_t until = (st == 1 ? P.endRx : P.endTx) - nw;  // GetDelayUntilIdle (:122-151)
-      until = until > 0 ? until : 0;
-      maybe = endNew > nw + until;
-    } else if (r.w > D.edW) {  // sync (:461-472): SwitchToRx, NotifyRxStart, Schedule (rxDuration, EndReceive)
-      int q = -1;
-      for (int k = 0; k < LPE_CAP; k++)
-        if (!pe[k].used) {
-          q = k;
-          break;
-        }
-      const uint32_t sl = wave_alloc(&D.cnt[1]);
-      if (q < 0 || sl >= D.sync_cap) {
-        err |= q < 0 ? WE_PECAP : WE_CAP;
-        break;
-      }
-      D.sync[sl] = LSync{r.at, r.uid, NONE, (uint32_t)(j * LPE_CAP + q), 0};
-      pe[q] = LPe{(uint64_t)endNew, r.at, r.uid, NONE, r.tx, 0, sl, 1, r.w};
-      P.live = (uint32_t)q;
-      P.rxing = 1;
-      P.endRx = endNew;
-      P.c.sync++;
-    } else {
-      P.c.drop_ed++;
-      maybe = true;
-    }
-    if (maybe) {  // maybeCcaBusy (:485-495): GetEnergyDuration (interference-helper.cc:171-190)
-      cursor_advance<false>(ring, P.head, P.len, m, nw, P.cur_n, P.cur_s);
-      double noise = P.cur_s;
-      int64_t end = nw;
-      for (uint32_t q0 = P.cur_n; q0 < P.len; q0 += NB) {  // (NB entries a trip; the sums one at a time)
-        LNi en[NB];
-#pragma unroll
-        for (int u = 0; u < NB; u++) en[u] = ring[(P.head + q0 + u) & m];
-        bool stop = false;
-#pragma unroll
-        for (int u = 0; u < NB; u++) {
-          if (stop || q0 + u >= P.len) {
-            stop = true;
-            continue;
-          }
-          noise += en[u].d;
-          end = en[u].t;
-          if (noise < D.ccaW) stop = true;
-        }
-        if (stop) break;
-      }
-      const int64_t cca = end > nw ? end - nw : 0;
-      if (cca != 0) {  // SwitchMaybeToCcaBusy (wifi-phy-state-helper.cc:404-423)
-        P.endCca = P.endCca > nw + cca ? P.endCca : nw + cca;
-        P.c.cca_switches++;
-      }
-    }
-    const uint32_t vi = wave_alloc(D.evc + (blockIdx.x % EV_STRIPES) * EV_STRIDE);
-    if (vi < D.ev_scap) D.ev[(blockIdx.x % EV_STRIPES) * D.ev_scap + vi] = LEv{r.at, r.uid, ctx, NONE, 0};
-    else err |= WE_CAP;
-#ifdef NSGPU_PHASE_PROF
-    pev++;
-#endif
-  }
-  D.ps[j] = P;
-  mir_put(D, j, m0, P);
-  if (err) atomicOr(&D.cnt[3], err);
-#ifdef NSGPU_PHASE_PROF
-  const uint64_t dt = __builtin_amdgcn_s_memrealtime() - pt0;
-  atomicAdd(&g_wl_ph[1], (unsigned long long)dt);
-  atomicAdd(&g_wl_ph[2], 1ull);
-  atomicAdd(&g_wl_ph[3], (unsigned long long)pev);
-  atomicMax(&g_wl_ep[0], (unsigned long long)dt);
-  atomicMax(&g_wl_ep[1], (unsigned long long)pev);
-  if (dt > g_wl_ph[6]) {
-    g_wl_ph[6] = dt;
-    g_wl_ph[7] = pev;
-  }
-#endif
-}
-// ---- the epoch with one wave per phy (the default; NSGPU_WIFIL_LANE=1: the lane-per-phy k_wl_step above) ----
-// k_wl_step's lanes spend their time in the NiChanges ring: a start inserted while receiving shifts every
-// pending end (100-300 entries at 10^4 phys), and the cursor and the CCA energy walk read the ring entry by
-// entry, 8 a memory trip.  Here the 64 lanes of a wave serve ONE phy: the ring is read 64 entries a trip, an
-// insertion shifts 64 entries a trip, and the sums whose order matters (the cursor's prefix, the energy
-// walk, CalculatePer's walk) run over the loaded entries lane by lane with readlane — no memory trip.  The
-// same operations in the same order as k_wl_step (bit-exact).  Every decision is wave-uniform; lane 0
-// makes the stores of uniform values.
+// ---- the epoch with one wave per phy ----
+// One phy's events of the epoch: every pending Receive / EndReceive with a key below (bts, buid), each the
+// reference's own code path — YansWifiPhy::EndReceive (yans-wifi-phy.cc:770-799) with
+// InterferenceHelper::CalculateSnrPer (interference-helper.cc:336-353), and YansWifiChannel::Receive ->
+// YansWifiPhy::StartReceivePacket (yans-wifi-phy.cc:399-496) with InterferenceHelper::AppendEvent
+// (interference-helper.cc:192-212) and GetEnergyDuration (:171-190).  A phy's time goes into its NiChanges
+// ring: a start inserted while receiving shifts every pending end (100-300 entries at 10^4 phys), and the
+// cursor and the CCA energy walk read the ring entry by entry.  So the 64 lanes of a wave serve ONE phy: the
+// ring is read 64 entries a trip, an insertion shifts 64 entries a trip, and the sums whose order matters
+// (the cursor's prefix, the energy walk, CalculatePer's walk) run over the loaded entries lane by lane with
+// readlane — no memory trip, and the reference's order of additions (bit-exact).  Every decision is
+// wave-uniform; lane 0 makes the stores of uniform values.
 __device__ __forceinline__ uint32_t lead_run(uint64_t bm) { return ~bm ? (uint32_t)__builtin_ctzll(~bm) : 64u; }
 __device__ __forceinline__ int64_t rl_i64(int64_t v, int u) {
   const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, u);
@@ -1020,8 +724,13 @@ __global__ __launch_bounds__(64) void k_wl_stepw(const WDev D, uint64_t bts, uin
       if (eb.can) {  // EventImpl::Invoke skips a cancelled event (event-impl.cc:40-46); still dispatched
         P.c.end_cancelled++;
       } else {
-        // InterferenceHelper::CalculateSnrPer (interference-helper.cc:336-353), as k_wl_step: the walk's
-        // sequential part here (64 ring entries a trip, then lane by lane), the chunks' models in k_wl_mid
+        // InterferenceHelper::CalculateSnrPer (interference-helper.cc:336-353): ni = (start, m_firstPower), the
+        // list after the event's own start entry (the ring's head: no fold while receiving) up to its end
+        // entry, (end, 0) — CalculateNoiseInterferenceW (:229-243) — then CalculatePer's walk (:257-334).  The
+        // walk's sequential part (the noise sums, the chunk bounds) runs here, 64 ring entries a trip, then
+        // lane by lane; the chunks' error-rate models (~10 pow / erfc calls each, ~100-200 chunks an
+        // EndReceive) run lane-parallel in k_wl_mid, which multiplies them in this order.  A zero-length
+        // chunk is 1.0 (CalculateChunkSuccessRate) and is not recorded.
         const LTx t = D.tx[eb.tx];
         const Mode pm = make_mode(t.mc, t.rate, t.bw);
         const double noise0 = P.firstPower;
@@ -1229,13 +938,7 @@ __global__ __launch_bounds__(64) void k_wl_stepw(const WDev D, uint64_t bts, uin
 }
 
 #ifdef NSGPU_PHASE_PROF
-__global__ void k_wl_prof_epoch() {  // (one thread: fold the epoch's maxima, reset them)
-  g_wl_ph[0] += g_wl_ep[0];
-  g_wl_ph[4] += g_wl_ep[1];
-  g_wl_ph[5] += 1;
-  g_wl_ep[0] = g_wl_ep[1] = 0;
-  g_wepoch++;
-}
+__global__ void k_wl_prof_epoch() { g_wepoch++; }  // (one thread: the wave records' epoch counter)
 #endif
 
 // CalculatePer's chunk product for the epoch's deferred EndReceives (interference-helper.cc:257-334): one
@@ -1545,8 +1248,8 @@ __global__ __launch_bounds__(TS_T) void k_wl_rank(const WDev D, uint64_t K0, int
   if (tid < (uint32_t)EV_STRIPES) D.evc[tid * EV_STRIDE] = 0, D.evt[tid * EV_STRIDE] = 0;
 }
 
-// (diagnostic, NSGPU_WIFIL_NOORDER=1) what k_wl_rank's last block zeroes, without the order; and (partitions,
-// whose epochs are ordered over every partition's gathered events) the partition's own lists once gathered
+// What k_wl_rank's last block zeroes, without the order: a partition's own lists once gathered (partitions'
+// epochs are ordered over every partition's gathered events)
 __global__ void k_wl_zero(const WDev D) {
   const uint32_t tid = threadIdx.x;
   if (tid < 3 || tid == 4) D.cnt[tid] = 0;
@@ -1726,11 +1429,6 @@ struct nsgpu_wifil {
   unsigned long long *h_digtot = nullptr, *d_digtot = nullptr;  // (mapped) the ordered epochs' digest sum
   uint64_t dig_added = 0;                // the part of it already added to a caller's digest
   uint32_t seq = 0;                      // epochs launched (the close's flag)
-  // host-side timing (NSGPU_WIFIL_HOSTPROF=1, printed at destroy): launches, the wait, the rest of an advance,
-  // and the time between advances (the host closure and the runtime), in ns summed over epochs
-  bool hprof = false;
-  uint64_t hp_n = 0, hp_launch = 0, hp_wait = 0, hp_post = 0, hp_out = 0;
-  std::chrono::steady_clock::time_point hp_last{};
   nsgpu_wifil_end *h_ends = nullptr;
   WMir *h_mir = nullptr;                 // mapped host memory: every phy's state fields (D.mir; GetState)
   std::vector<uint32_t> erank;
@@ -1799,10 +1497,6 @@ extern "C" int nsgpu_wifil_destroy(nsgpu_wifil *h) {
     nsgpu_wifil_destroy(m);
   }
   h->mem.clear();
-  if (h->hprof && h->hp_n)
-    fprintf(stderr, "nsgpu_wifil host: %llu epochs, per epoch (us): launches %.2f, wait %.2f, rest of advance %.2f, "
-            "between advances %.2f\n", (unsigned long long)h->hp_n, h->hp_launch / 1e3 / h->hp_n, h->hp_wait / 1e3 / h->hp_n,
-            h->hp_post / 1e3 / h->hp_n, h->hp_out / 1e3 / (h->hp_n > 1 ? h->hp_n - 1 : 1));
   for (hipStream_t q : {h->s, h->s2})
     if (q) {
       (void)hipStreamSynchronize(q);
@@ -1856,10 +1550,6 @@ static int wl_create(const nsgpu_wifil_config *c, int64_t j0, int64_t nown, int6
       c->loss.n > NSGPU_MAX_LOSS_CHAIN || c->error_model > NSGPU_WIFIL_YANS)
     return set_error(NSGPU_EINVAL, "nsgpu_wifil_create: ni_cap / rxq_cap must be powers of two >= 2, tx_cap in (0, 2^32)");
   nsgpu_wifil *h = new nsgpu_wifil();
-  {
-    const char *e = getenv("NSGPU_WIFIL_HOSTPROF");
-    h->hprof = e && e[0] == '1';
-  }
   const int64_t N = c->n_phy;
   WDev &D = h->D;
   D.nphy = N;
@@ -2095,9 +1785,6 @@ extern "C" int nsgpu_wifil_advance(nsgpu_wifil *h, uint64_t bound_ts, uint32_t b
                                    uint32_t *log_ctx, uint64_t log_cap) {
   if (!h || !uid || !dispatched || !digest) return set_error(NSGPU_EINVAL, "nsgpu_wifil_advance: null");
   if (!h->mem.empty()) return wlg_advance(h, bound_ts, bound_uid, uid, dispatched, digest, log_ts, log_uid, log_ctx, log_cap);
-  using clk = std::chrono::steady_clock;
-  const clk::time_point hp0 = h->hprof ? clk::now() : clk::time_point{};
-  if (h->hprof && h->hp_n) h->hp_out += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(hp0 - h->hp_last).count();
   const WDev D = h->D;  // (this epoch's parity: its status block, lists, syncs; zeroed by the order two epochs back)
   const uint32_t b = h->par;
   if (h->ord_pending[b]) {  // (that order is their last reader; it has had a whole epoch: usually done, then the
@@ -2107,18 +1794,8 @@ extern "C" int nsgpu_wifil_advance(nsgpu_wifil *h, uint64_t bound_ts, uint32_t b
     h->ord_pending[b] = false;
   }
   // epoch: the phys' waves, then the tail (PER products + sync ranks + the close), then the order behind it
-  static const bool lane_step = [] {  // (NSGPU_WIFIL_LANE=1: the lane-per-phy step kernel)
-    const char *e = getenv("NSGPU_WIFIL_LANE");
-    return e && e[0] == '1';
-  }();
-  if (lane_step) {
-    int rcf = wl_flush_sends(h);
-    if (rcf) return rcf;
-    hipLaunchKernelGGL(k_wl_step, dim3(wl_grid(D.nown, 64)), dim3(64), 0, h->s, D, bound_ts, bound_uid);
-  } else {
-    hipLaunchKernelGGL(k_wl_stepw, dim3(wl_grid(D.nown, 1)), dim3(64), 0, h->s, D, bound_ts, bound_uid, h->sb);
-    h->sb.n = 0;
-  }
+  hipLaunchKernelGGL(k_wl_stepw, dim3(wl_grid(D.nown, 1)), dim3(64), 0, h->s, D, bound_ts, bound_uid, h->sb);
+  h->sb.n = 0;
 #ifdef NSGPU_PHASE_PROF
   hipLaunchKernelGGL(k_wl_prof_epoch, dim3(1), dim3(1), 0, h->s);
 #endif
@@ -2126,16 +1803,7 @@ extern "C" int nsgpu_wifil_advance(nsgpu_wifil *h, uint64_t bound_ts, uint32_t b
   hipLaunchKernelGGL(k_wl_mid, dim3(MID_PER + MID_RANK), dim3(256), 0, h->s, D, *uid, h->d_stat, seq);
   NSGPU_HIP(hipGetLastError());
   const bool logging = log_ts && log_uid && log_ctx && *dispatched < log_cap;
-  static const bool no_order = [] {  // (diagnostic: NSGPU_WIFIL_NOORDER=1 skips the order — digest and log wrong)
-    const char *e = getenv("NSGPU_WIFIL_NOORDER");
-    return e && e[0] == '1';
-  }();
-  if (no_order) {  // (the counters the order would zero for the epoch two on)
-    hipLaunchKernelGGL(k_wl_zero, dim3(1), dim3(64), 0, h->s, D);
-  } else if (int rco = wl_launch_order(h, D, b, *dispatched, logging ? 1 : 0)) {
-    return rco;
-  }
-  const clk::time_point hp1 = h->hprof ? clk::now() : clk::time_point{};
+  if (int rco = wl_launch_order(h, D, b, *dispatched, logging ? 1 : 0)) return rco;
   {  // the epoch's flag in the mapped status block (a spin: a stream synchronize's wake-up took microseconds);
      // the stream is queried now and then, so a failed kernel (no flag) ends the wait with its error
     volatile uint32_t *flag = reinterpret_cast<volatile uint32_t *>(h->h_stat) + 6;
@@ -2149,13 +1817,13 @@ extern "C" int nsgpu_wifil_advance(nsgpu_wifil *h, uint64_t bound_ts, uint32_t b
     }
     std::atomic_thread_fence(std::memory_order_acquire);
   }
-  const clk::time_point hp2 = h->hprof ? clk::now() : clk::time_point{};
   wl_use_stat(h, b ^ 1);  // (the next epoch's block; SendPackets until then report their errors there)
   int rc = wl_check(h, "nsgpu_wifil_advance");
   if (rc) return rc;
   const uint32_t nev = h->h_cnt[0], nsync = h->h_cnt[1], nend = h->h_cnt[2];
-  // (r05z4n: a diagnostic build that skipped the order also skipped its zeroing of the epoch counters, so nev
-  // grew epoch by epoch past the dense array — a count beyond it is an engine fault, reported as one)
+  // (the order zeroes the epoch counters for the epoch two on; were that zeroing ever missed, nev would grow
+  // epoch by epoch past the dense array, as in fault r05z4n — a count beyond it is an engine fault, reported
+  // as one)
   if ((uint64_t)nev > (uint64_t)D.nphy * EVB + D.ev_cap || nend > D.end_cap || nsync > D.sync_cap)
     return set_error(NSGPU_ESTATE, "nsgpu_wifil_advance: epoch counts beyond the engine's arrays (events %u, syncs "
                                    "%u, ends %u): the epoch counters were not reset", nev, nsync, nend);
@@ -2204,17 +1872,6 @@ extern "C" int nsgpu_wifil_advance(nsgpu_wifil *h, uint64_t bound_ts, uint32_t b
   const uint64_t tot = *h->h_digtot;  // (the ordered epochs' terms so far: one aligned 8-byte store's value)
   *digest += tot - h->dig_added;
   h->dig_added = tot;
-  if (h->hprof) {
-    const clk::time_point hp3 = clk::now();
-    const auto ns = [](clk::time_point a, clk::time_point b) {
-      return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(b - a).count();
-    };
-    h->hp_launch += ns(hp0, hp1);
-    h->hp_wait += ns(hp1, hp2);
-    h->hp_post += ns(hp2, hp3);
-    h->hp_n++;
-    h->hp_last = hp3;
-  }
   if (nend > END_STAGE) NSGPU_HIP(hipStreamSynchronize(h->s));
   std::sort(h->ends_epoch.begin(), h->ends_epoch.end(),
             [](const nsgpu_wifil_end &a, const nsgpu_wifil_end &b) { return a.ts != b.ts ? a.ts < b.ts : a.uid < b.uid; });
@@ -2792,14 +2449,6 @@ extern "C" int nsgpu_wifil_create_dist(const nsgpu_wifil_config *c, int64_t phy_
 }
 
 #ifdef NSGPU_PHASE_PROF
-// (diagnostic build only) the k_wl_step counters above, reset after the read
-extern "C" int nsgpu_wifil_prof_read(unsigned long long *out) {
-  NSGPU_HIP(hipDeviceSynchronize());
-  NSGPU_HIP(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_wl_ph), sizeof(unsigned long long) * 8));
-  unsigned long long z[8] = {};
-  NSGPU_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_wl_ph), z, sizeof(z)));
-  return NSGPU_OK;
-}
 // (diagnostic build only) k_wl_stepw's wave records: arm for WREC_E epochs from `target` on (out null), or read
 // them (out: WREC_E x WREC_P x 5 words)
 extern "C" int nsgpu_wifil_prof_waves(uint32_t target, unsigned long long *out) {
