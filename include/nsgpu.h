@@ -234,6 +234,17 @@ int nsgpu_wifil_listen(nsgpu_wifil *h, uint32_t phy, int on);
 int nsgpu_wifil_send_plan(const nsgpu_wifil_config *cfg, uint32_t sender, uint32_t uid_base, uint32_t *rx_phy,
                           uint32_t *rx_uid, uint32_t *rx_ctx, uint64_t cap, uint64_t *n);
 int nsgpu_wifil_next_end(nsgpu_wifil *h, nsgpu_wifil_next *out);
+/* RxStart / CCA-busy notifications: from the next advance on, every StartReceivePacket (yans-wifi-phy.cc:399-496)
+ * of a phy with on = 1 leaves one nsgpu_wifil_note — the branch it took at :417-495 (sync :461-472, drop while RX
+ * :431-443 / TX :444-457, drop below the ED threshold :475-483), GetState's value at :417, SwitchToRx's rxDuration
+ * (:468) and, where maybeCcaBusy (:485-495) was reached, GetEnergyDuration's non-zero result (:491-494).  No phy
+ * notifies by default; the epoch kernel then runs as without this interface.  phy >= n_phy: NSGPU_EINVAL; a
+ * partitioned handle (create_dist / create_group): NSGPU_ESTATE (notifications are single-engine for now).
+ * nsgpu_wifil_read_notes has nsgpu_wifil_read_ends' contract: the notes of the epochs advanced so far and not yet
+ * read, in (ts, uid) order (cap 0: the count only, kept).  More notes in one epoch than the engine's array holds
+ * fail that advance with NSGPU_ENOMEM; none is dropped silently. */
+int nsgpu_wifil_notify(nsgpu_wifil *h, uint32_t phy, int on);
+int nsgpu_wifil_read_notes(nsgpu_wifil *h, nsgpu_wifil_note *out, uint64_t cap, uint64_t *n);  /* since last read */
 /* Partitioned closed-loop PHY (YansWifiChannel::Send, yans-wifi-channel.cc:77-115, fans a SendPacket out to
  * every receiver; the receivers are split over GPUs).  Every rank runs the same host program (MAC closures, uids,
  * GetState) over the returned handle, which takes every nsgpu_wifil_* call above; the device work of phys
@@ -391,6 +402,17 @@ int nsgpu_sim_wifi_set_position(nsgpu_sim *s, uint32_t phy, double x, double y, 
 typedef void (*nsgpu_wifi_end_fn)(void *user, const nsgpu_wifil_end *end);
 int nsgpu_sim_wifi_set_end_handler(nsgpu_sim *s, nsgpu_wifi_end_fn fn, void *user);
 int nsgpu_sim_wifi_listen(nsgpu_sim *s, uint32_t phy, int on);
+/* RxStart / CCA-busy notifications (nsgpu_wifil_notify): after every epoch of the PHY — the partial and hand-back
+ * epochs too — the runtime calls fn (user, &note) for each of the epoch's notes in (ts, uid) order, with Now (),
+ * the current uid and the context set to the Receive event's (its ts, its uid, the receiver's node), before the
+ * epoch's EndReceive hand-back call and before the host event that bounded the epoch is returned.  DcfManager's
+ * Notify*Now (dcf-manager.cc:591-641) and WifiPhyStateHelper's switches schedule nothing, so running them there
+ * is exact.  A handler must not schedule and must not send: a uid counter that moved across a call makes this and
+ * every later Run fail with NSGPU_ESTATE.  Delivered notes are consumed; with no handler they stay readable through
+ * nsgpu_wifil_read_notes. */
+typedef void (*nsgpu_wifi_note_fn)(void *user, const nsgpu_wifil_note *note);
+int nsgpu_sim_wifi_set_note_handler(nsgpu_sim *s, nsgpu_wifi_note_fn fn, void *user);
+int nsgpu_sim_wifi_notify(nsgpu_sim *s, uint32_t phy, int on);
 
 /* ---------------- GPU-resident point-to-point subset (configs 2, 4) ----------------
  * Replaces, for a topology of PointToPointNetDevices, the handler chain

@@ -395,6 +395,20 @@ typedef struct nsgpu_wifil_phy_state {
   int64_t delay_until_idle;  /* GetDelayUntilIdle (:122-151) */
 } nsgpu_wifil_phy_state;
 
+/* One StartReceivePacket of a notifying phy (nsgpu_wifil_notify): which branch of yans-wifi-phy.cc:417-495 it
+ * took, with the arguments of the state helper's switches — what DcfManager::NotifyRxStartNow /
+ * NotifyMaybeCcaBusyStartNow (dcf-manager.cc:591-641) and the State / RxOk traces are fed from. */
+enum { NSGPU_WIFIL_NOTE_SYNC = 0, NSGPU_WIFIL_NOTE_DROP_RX = 1, NSGPU_WIFIL_NOTE_DROP_TX = 2, NSGPU_WIFIL_NOTE_DROP_ED = 3 };
+typedef struct nsgpu_wifil_note {
+  uint64_t ts;            /* StartReceivePacket's Now () */
+  uint32_t uid, phy;      /* the Receive event's uid; the receiver */
+  uint32_t tx, kind;      /* transmission index (SendPacket calls in order); NSGPU_WIFIL_NOTE_* */
+  uint32_t state, pad_;   /* nsgpu_wifil_state GetState () returned at :417, before any switch */
+  int64_t rx_duration;    /* ns (the argument of SwitchToRx / NotifyRxStart on a sync) */
+  int64_t cca_duration;   /* GetEnergyDuration's result when maybeCcaBusy was reached and it is non-zero
+                             (the argument of SwitchMaybeToCcaBusy), else 0 */
+} nsgpu_wifil_note;
+
 #ifdef __cplusplus
 }
 #endif

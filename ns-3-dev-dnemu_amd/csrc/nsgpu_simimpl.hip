@@ -55,6 +55,10 @@ struct nsgpu_sim {
   void *wifi_end_user = nullptr;
   uint64_t wifi_listen_n = 0;                // phys listened to
   std::vector<uint8_t> lis_on;
+  nsgpu_wifi_note_fn wifi_note_fn = nullptr;  // RxStart / CCA-busy notifications (nsgpu_sim_wifi_set_note_handler)
+  void *wifi_note_user = nullptr;
+  std::vector<nsgpu_wifil_note> wifi_notes;   // the epoch's, while they are delivered
+  bool note_scheduled = false;  // a note handler scheduled or sent (sticky: uids were handed out at the wrong place)
   bool uid_spent = false;  // a Schedule call hit the uid limit (a closure's call fails; the run then fails too)
   uint32_t cur_uid = 0;
   uint64_t cur_ts = 0;
@@ -361,9 +365,12 @@ int nsgpu_sim_remove_key(nsgpu_sim *s, uint64_t ts, uint32_t uid, uint32_t ctx, 
 // The next window (see the file header).  *n = 0: nothing is left to dispatch (the queue is empty and
 // the attached engine, if any, has run out), or a Stop was dispatched.  `force`: pop even after a Stop
 // (RunOneEvent).
+static int deliver_notes(nsgpu_sim *s);
 static int pop_window(nsgpu_sim *s, nsgpu_event *out, uint32_t cap, uint32_t *n, bool force) {
   *n = 0;
   if (s->uid_spent) return nsgpu::uid_range_error("nsgpu_sim: Run after a Schedule call failed at the uid limit");
+  if (s->note_scheduled)
+    return set_error(NSGPU_ESTATE, "nsgpu_sim: Run after a Wi-Fi note handler scheduled or sent");
   s->win.clear();
   s->win_next = 0;
   if (!s->win_removed.empty()) s->win_removed.clear();
@@ -413,6 +420,7 @@ static int pop_window(nsgpu_sim *s, nsgpu_event *out, uint32_t cap, uint32_t *n,
                                s->log_ctx, s->log_cap);
       if (rc == NSGPU_ERANGE) s->uid_spent = true;  // (sticky: the epoch's EndReceives would take wrapped uids)
       if (rc) return rc;
+      if ((rc = deliver_notes(s))) return rc;  // (before the epoch's hand-back call and the host event that bounded it)
       if (handback) {
         nsgpu_wifil_end end;
         if (!nsgpu::wifil_epoch_end(s->wifi, nx.uid, &end))
@@ -480,6 +488,33 @@ static int pop_window(nsgpu_sim *s, nsgpu_event *out, uint32_t cap, uint32_t *n,
     s->win.push_back(f);
   }
   *n = k;
+  return NSGPU_OK;
+}
+
+// The last epoch's notes to the note handler, in (ts, uid) order, each with Now / uid / context of its Receive
+// event (what the EndReceive hand-back does for its event).  Without a handler they stay with the PHY.
+static int deliver_notes(nsgpu_sim *s) {
+  if (!s->wifi_note_fn) return NSGPU_OK;
+  uint64_t n = 0;
+  int rc = nsgpu_wifil_read_notes(s->wifi, nullptr, 0, &n);
+  if (rc || n == 0) return rc;
+  s->wifi_notes.resize(n);
+  if ((rc = nsgpu_wifil_read_notes(s->wifi, s->wifi_notes.data(), n, &n))) return rc;
+  for (uint64_t i = 0; i < n; i++) {
+    const nsgpu_wifil_note &t = s->wifi_notes[i];
+    s->cur_ts = t.ts;
+    s->cur_uid = t.uid;
+    s->cur_ctx = nsgpu::wifil_node(s->wifi, t.phy);
+    const uint32_t u0 = s->uid;
+    s->wifi_note_fn(s->wifi_note_user, &t);
+    if (s->uid != u0 || s->uid_spent) {
+      s->note_scheduled = true;
+      break;
+    }
+  }
+  if (s->note_scheduled)
+    return set_error(NSGPU_ESTATE, "nsgpu_sim: a Wi-Fi note handler scheduled or sent (the uid counter moved across "
+                                   "its call); a handler must do neither");
   return NSGPU_OK;
 }
 
@@ -704,6 +739,18 @@ int nsgpu_sim_wifi_set_end_handler(nsgpu_sim *s, nsgpu_wifi_end_fn fn, void *use
   s->wifi_end_fn = fn;
   s->wifi_end_user = user;
   return NSGPU_OK;
+}
+
+int nsgpu_sim_wifi_set_note_handler(nsgpu_sim *s, nsgpu_wifi_note_fn fn, void *user) {
+  if (!s) return set_error(NSGPU_EINVAL, "nsgpu_sim_wifi_set_note_handler: null");
+  s->wifi_note_fn = fn;
+  s->wifi_note_user = user;
+  return NSGPU_OK;
+}
+
+int nsgpu_sim_wifi_notify(nsgpu_sim *s, uint32_t phy, int on) {
+  if (!s || !s->wifi) return set_error(NSGPU_ESTATE, "nsgpu_sim_wifi_notify: no Wi-Fi PHY attached");
+  return nsgpu_wifil_notify(s->wifi, phy, on);
 }
 
 int nsgpu_sim_wifi_listen(nsgpu_sim *s, uint32_t phy, int on) {

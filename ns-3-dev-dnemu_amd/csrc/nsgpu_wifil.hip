@@ -37,9 +37,9 @@ namespace {
 constexpr uint32_t NONE = 0xffffffffu;
 constexpr int LPE_CAP = 8;  // pending EndReceive records of one phy (the live one + cancelled ones)
 constexpr uint32_t END_STAGE = 128;  // EndReceive records an epoch returns with its counters (more: a second copy)
-constexpr size_t STAT_HDR = 32;      // the status block: counters (5 x u32), the epoch flag (word 6), then the ends
+constexpr size_t STAT_HDR = 32;      // the status block: counters (6 x u32), the epoch flag (word 6), then the ends
 static_assert(sizeof(nsgpu_wifil_end) % 8 == 0 && STAT_HDR % 8 == 0, "status block alignment");
-constexpr uint32_t WE_TX_IN_TX = 1, WE_NICAP = 2, WE_RQCAP = 4, WE_PECAP = 8, WE_CAP = 16, WE_CKCAP = 32;
+constexpr uint32_t WE_TX_IN_TX = 1, WE_NICAP = 2, WE_RQCAP = 4, WE_PECAP = 8, WE_CAP = 16, WE_CKCAP = 32, WE_NOTECAP = 64;
 
 struct LNi {  // InterferenceHelper::NiChange (interference-helper.cc:91-110)
   int64_t t;
@@ -110,7 +110,7 @@ struct WDev {
   nsgpu_wifil_end *ends;
   uint32_t *end_sslot;
   uint32_t *cnt;  // [0] events, [1] syncs, [2] ends, [3] error bits (sticky: a SendPacket's are seen at the
-                  // next advance), [4] chunk slots claimed ([0..2], [4] zeroed by the order's
+                  // next advance), [4] chunk slots claimed, [5] notes ([0..2], [4], [5] zeroed by the order's
                   // k_wl_rank, for the epoch two on)
   LCk *ck;        // the epoch's deferred chunks (ck_cap; a walk that finds no room computes its PER inline)
   LEck *eck;      // per end record
@@ -139,6 +139,11 @@ struct WDev {
   int64_t j0, nown;
   const LSync *xsync;
   uint32_t xn, pad_x;
+  // RxStart / CCA-busy notifications (nsgpu_wifil_notify): a flag per phy, and the epoch's notes (k_wl_stepw<true>,
+  // launched only while some phy notifies; the host reads them before the next epoch: one array, no parity)
+  const uint32_t *note_on;
+  nsgpu_wifil_note *notes;
+  uint64_t note_cap;
 };
 // The epoch's dispatched events are appended to EV_STRIPES lists (phy j's to stripe j % EV_STRIPES): one
 // counter a phy's event would serialize ~10^4 atomics an epoch on one line.
@@ -484,6 +489,7 @@ __device__ __forceinline__ void w_ni_insert(LNi *ring, uint32_t head, uint32_t &
 constexpr uint32_t RL = 256;
 constexpr uint32_t RSPEC = 32, QSPEC = 4;  // ring / queue entries loaded with the state (speculatively)
 constexpr uint32_t EVB = 64, ENB = 8, SYB = 8;
+constexpr uint32_t NTB = 32;  // staged notes (k_wl_stepw<true>; a phy's notes leave the wave in its own order)
 constexpr uint32_t LOCAL = 0x80000000u;
 struct LEnd {  // a staged end record
   nsgpu_wifil_end rec;
@@ -506,9 +512,10 @@ __device__ __forceinline__ LRx shfl_up_rx(const LRx &a) {
 // One epoch of every phy, a wave each: first the SendPackets the last host closure made (nsgpu_wifil_send
 // batches up to NSEND of them into this launch: the sender's switch and this phy's Receive of each, what
 // k_wl_send does — they precede every event of the epoch), then every pending Receive / EndReceive with a
-// key below (bts, buid), in (ts, uid) order.
-__global__ __launch_bounds__(64) void k_wl_stepw(const WDev D, uint64_t bts, uint32_t buid,
-                                                                                   const SendBatch sb) {
+// key below (bts, buid), in (ts, uid) order.  NOTE: the instantiation launched while some phy notifies
+// (nsgpu_wifil_notify) — a notifying phy's wave stages one nsgpu_wifil_note per Receive; <false> holds none of it.
+template <bool NOTE>
+__global__ __launch_bounds__(64) void k_wl_stepw(const WDev D, uint64_t bts, uint32_t buid, const SendBatch sb) {
   const int64_t j = D.j0 + blockIdx.x;
   const uint32_t lane = threadIdx.x;
   if (j >= D.j0 + D.nown) return;
@@ -521,6 +528,9 @@ __global__ __launch_bounds__(64) void k_wl_stepw(const WDev D, uint64_t bts, uin
   __shared__ LEv s_ev[EVB];
   __shared__ LEnd s_end[ENB];
   __shared__ LSync s_sy[SYB];
+  __shared__ nsgpu_wifil_note s_nt[NOTE ? NTB : 1];  // (<false> never names it: no LDS there)
+  bool noting = false;
+  if constexpr (NOTE) noting = D.note_on[j] != 0;
   LPhy P = D.ps[j];
   // (issued with the state: the ring's first RSPEC entries and the queue's first QSPEC at their compact places
   // — a fast epoch leaves them there, head 0 — used when the state says they are the ones; the first trip moves
@@ -628,7 +638,7 @@ __global__ __launch_bounds__(64) void k_wl_stepw(const WDev D, uint64_t bts, uin
   pt1 = __builtin_amdgcn_s_memtime();
 #endif
   // ---- staged appends
-  uint32_t ns = 0, ne = 0, nv = 0;
+  uint32_t ns = 0, ne = 0, nv = 0, nn = 0;
   bool slotted = false;  // (the phy's own event slots are written: further events go to the stripes)
   auto flush = [&]() {  // claim the staged syncs, end records and events (one atomic each), patch, store
     __syncthreads();
@@ -675,6 +685,16 @@ __global__ __launch_bounds__(64) void k_wl_stepw(const WDev D, uint64_t bts, uin
         LEv v = s_ev[lane];
         v.sslot = fix(v.sslot);
         evs[bv + lane] = v;
+      }
+    }
+    if constexpr (NOTE) {
+      if (nn) {  // (wave-uniform) the staged notes' places: one atomic, then a lane a note
+        uint32_t bn = 0;
+        if (lane == 0) bn = atomicAdd(&D.cnt[5], nn);
+        bn = rl_u32(bn, 0);
+        if ((uint64_t)bn + nn > D.note_cap) err |= WE_NOTECAP;
+        else if (lane < nn) D.notes[bn + lane] = s_nt[lane];
+        nn = 0;
       }
     }
     ns = ne = nv = 0;
@@ -845,11 +865,15 @@ __global__ __launch_bounds__(64) void k_wl_stepw(const WDev D, uint64_t bts, uin
     w_ni_insert(ring, P.head, P.len, m, endNew, -r.w);
     P.ni_max = P.len > P.ni_max ? P.len : P.ni_max;
     const int st = P.endTx > nw ? 2 : P.rxing ? 1 : P.endCca > nw ? 3 : 0;  // GetState (:159-183)
+    static_assert(NSGPU_WIFIL_IDLE == 0 && NSGPU_WIFIL_RX == 1 && NSGPU_WIFIL_TX == 2 && NSGPU_WIFIL_CCA_BUSY == 3, "st");
+    uint32_t nkind = NSGPU_WIFIL_NOTE_DROP_ED;  // (NOTE) the branch taken, and SwitchMaybeToCcaBusy's argument
+    int64_t ncca = 0;
     bool maybe = false;
     P.c.rx++;
     if (st == 1 || st == 2) {  // drop; noise after the current Rx / Tx (:431-457)
       if (st == 1) P.c.drop_rx++;
       else P.c.drop_tx++;
+      nkind = st == 1 ? NSGPU_WIFIL_NOTE_DROP_RX : NSGPU_WIFIL_NOTE_DROP_TX;
       int64_t until = (st == 1 ? P.endRx : P.endTx) - nw;  // GetDelayUntilIdle (:122-151)
       until = until > 0 ? until : 0;
       maybe = endNew > nw + until;
@@ -870,6 +894,7 @@ __global__ __launch_bounds__(64) void k_wl_stepw(const WDev D, uint64_t bts, uin
       P.rxing = 1;
       P.endRx = endNew;
       P.c.sync++;
+      nkind = NSGPU_WIFIL_NOTE_SYNC;
     } else {
       P.c.drop_ed++;
       maybe = true;
@@ -895,6 +920,16 @@ __global__ __launch_bounds__(64) void k_wl_stepw(const WDev D, uint64_t bts, uin
       if (cca != 0) {  // SwitchMaybeToCcaBusy (wifi-phy-state-helper.cc:404-423)
         P.endCca = P.endCca > nw + cca ? P.endCca : nw + cca;
         P.c.cca_switches++;
+        ncca = cca;
+      }
+    }
+    if constexpr (NOTE) {
+      if (noting) {
+        if (nn == NTB) flush();
+        if (lane == 0)
+          s_nt[nn] = nsgpu_wifil_note{r.at, r.uid, (uint32_t)j, r.tx, nkind, (uint32_t)st, 0,
+                                      nkind == NSGPU_WIFIL_NOTE_SYNC ? r.dur : 0, ncca};
+        nn++;
       }
     }
     if (nv == EVB) flush();
@@ -904,7 +939,7 @@ __global__ __launch_bounds__(64) void k_wl_stepw(const WDev D, uint64_t bts, uin
 #ifdef NSGPU_PHASE_PROF
   pt2 = __builtin_amdgcn_s_memtime();
 #endif
-  if (ns | ne | nv) flush();
+  if (ns | ne | nv | nn) flush();
   // ---- write-backs: the pending records, the queue's rest (fast, after insertions), the ring (fast), the state
   if (pe_dirty && lane < (uint32_t)LPE_CAP) pe[lane] = mine;
   if (fast && (nins || rqn)) {  // (the queue's rest at its compact place: head 0)
@@ -1090,6 +1125,7 @@ __device__ __forceinline__ void wl_fin(const WDev &D, uint8_t *hst, uint32_t seq
     hc[1] = D.cnt[1];
     hc[2] = D.cnt[2];
     hc[3] = D.cnt[3];
+    hc[5] = D.cnt[5];
     D.cnt[0] = nev;
   }
   __threadfence_system();  // (the block's writes to the host's copy land before the epoch's flag)
@@ -1244,7 +1280,7 @@ __global__ __launch_bounds__(TS_T) void k_wl_rank(const WDev D, uint64_t K0, int
     *hdig = atomicAdd(D.edig, 0ull);
     atomicExch(D.ticket, 0u);
   }
-  if (tid < 3 || tid == 4) D.cnt[tid] = 0;  // (events, syncs, ends; the chunk pool)
+  if (tid < 3 || tid == 4 || tid == 5) D.cnt[tid] = 0;  // (events, syncs, ends; the chunk pool; the notes)
   if (tid < (uint32_t)EV_STRIPES) D.evc[tid * EV_STRIDE] = 0, D.evt[tid * EV_STRIDE] = 0;
 }
 
@@ -1252,9 +1288,9 @@ __global__ __launch_bounds__(TS_T) void k_wl_rank(const WDev D, uint64_t K0, int
 // epochs are ordered over every partition's gathered events)
 __global__ void k_wl_zero(const WDev D) {
   const uint32_t tid = threadIdx.x;
-  if (tid < 3 || tid == 4) D.cnt[tid] = 0;
+  if (tid < 3 || tid == 4 || tid == 5) D.cnt[tid] = 0;
   if (tid < (uint32_t)EV_STRIPES) D.evc[tid * EV_STRIDE] = 0, D.evt[tid * EV_STRIDE] = 0;
-  if (tid == 5 && D.gtot) *D.gtot = 0;
+  if (tid == 6 && D.gtot) *D.gtot = 0;
 }
 __global__ void k_wl_set(uint32_t *p, uint32_t v) { *p = v; }
 
@@ -1441,6 +1477,12 @@ struct nsgpu_wifil {
   bool lis_dirty = false;
   uint32_t *d_lis = nullptr;
   unsigned long long *d_next = nullptr, *h_next = nullptr;
+  // RxStart / CCA-busy notifications: the notifying phys (a flag each; their count picks the epoch kernel), the
+  // notes of the epochs advanced and not yet read, and the last epoch's (sorted by (ts, uid))
+  std::vector<uint8_t> note_on;
+  uint64_t n_note_on = 0;
+  uint32_t *d_note_on = nullptr;
+  std::vector<nsgpu_wifil_note> notes, notes_epoch;
   // ---- a partitioned PHY (nsgpu_wifil_create_dist / nsgpu_wifil_create_group): this handle is the host side
   // every rank replicates (the MAC's closures, the uids, GetState, the ends); `mem` are the partitions it runs —
   // one (RCCL: `comm`, the others on other GPUs) or all of them (a loopback group on this device) — each an engine
@@ -1697,7 +1739,7 @@ static int wl_check_bits(uint32_t e, const char *what) {
   if (e & WE_TX_IN_TX)
     return set_error(NSGPU_ESTATE, "%s: SendPacket while transmitting (yans-wifi-phy.cc:508 NS_ASSERT)", what);
   return set_error(NSGPU_ENOMEM, "%s: capacity exceeded (bits %u: 2 NiChanges ring, 4 Receive queue, 8 pending "
-                                 "EndReceive records, 16 epoch lists, 32 CalculatePer chunk pool)", what, e);
+                                 "EndReceive records, 16 epoch lists, 32 CalculatePer chunk pool, 64 epoch notes)", what, e);
 }
 static int wl_check(nsgpu_wifil *h, const char *what) { return wl_check_bits(h->h_cnt[3], what); }
 
@@ -1794,7 +1836,10 @@ extern "C" int nsgpu_wifil_advance(nsgpu_wifil *h, uint64_t bound_ts, uint32_t b
     h->ord_pending[b] = false;
   }
   // epoch: the phys' waves, then the tail (PER products + sync ranks + the close), then the order behind it
-  hipLaunchKernelGGL(k_wl_stepw, dim3(wl_grid(D.nown, 1)), dim3(64), 0, h->s, D, bound_ts, bound_uid, h->sb);
+  // (the notifying instantiation only while some phy notifies: the default path's kernel holds none of it)
+  const bool noting = h->n_note_on != 0;
+  if (noting) hipLaunchKernelGGL(k_wl_stepw<true>, dim3(wl_grid(D.nown, 1)), dim3(64), 0, h->s, D, bound_ts, bound_uid, h->sb);
+  else hipLaunchKernelGGL(k_wl_stepw<false>, dim3(wl_grid(D.nown, 1)), dim3(64), 0, h->s, D, bound_ts, bound_uid, h->sb);
   h->sb.n = 0;
 #ifdef NSGPU_PHASE_PROF
   hipLaunchKernelGGL(k_wl_prof_epoch, dim3(1), dim3(1), 0, h->s);
@@ -1820,16 +1865,18 @@ extern "C" int nsgpu_wifil_advance(nsgpu_wifil *h, uint64_t bound_ts, uint32_t b
   wl_use_stat(h, b ^ 1);  // (the next epoch's block; SendPackets until then report their errors there)
   int rc = wl_check(h, "nsgpu_wifil_advance");
   if (rc) return rc;
-  const uint32_t nev = h->h_cnt[0], nsync = h->h_cnt[1], nend = h->h_cnt[2];
+  const uint32_t nev = h->h_cnt[0], nsync = h->h_cnt[1], nend = h->h_cnt[2], nnote = h->h_cnt[5];
   // (the order zeroes the epoch counters for the epoch two on; were that zeroing ever missed, nev would grow
   // epoch by epoch past the dense array, as in fault r05z4n — a count beyond it is an engine fault, reported
   // as one)
-  if ((uint64_t)nev > (uint64_t)D.nphy * EVB + D.ev_cap || nend > D.end_cap || nsync > D.sync_cap)
+  if ((uint64_t)nev > (uint64_t)D.nphy * EVB + D.ev_cap || nend > D.end_cap || nsync > D.sync_cap || nnote > D.note_cap)
     return set_error(NSGPU_ESTATE, "nsgpu_wifil_advance: epoch counts beyond the engine's arrays (events %u, syncs "
-                                   "%u, ends %u): the epoch counters were not reset", nev, nsync, nend);
+                                   "%u, ends %u, notes %u): the epoch counters were not reset", nev, nsync, nend, nnote);
   //  the uid range before anything of the epoch is published (ends, dispatch count, digest): the
   // epoch's EndReceives are queued, none dispatched; the caller makes the error sticky (nsgpu_sim: uid_spent)
   if ((uint64_t)*uid + nsync > nsgpu::UID_NEXT_MAX) return nsgpu::uid_range_error("nsgpu_wifil_advance");
+  h->notes_epoch.resize(nnote);  // (before the next epoch's kernel reuses the array; waited for below)
+  if (nnote) NSGPU_HIP(hipMemcpyAsync(h->notes_epoch.data(), D.notes, nnote * sizeof(nsgpu_wifil_note), hipMemcpyDeviceToHost, h->s));
   h->ends_epoch.resize(nend);
   if (nend > END_STAGE) {
     NSGPU_HIP(hipMemcpyAsync(h->ends_epoch.data(), D.ends, nend * sizeof(nsgpu_wifil_end), hipMemcpyDeviceToHost, h->s));
@@ -1872,7 +1919,12 @@ extern "C" int nsgpu_wifil_advance(nsgpu_wifil *h, uint64_t bound_ts, uint32_t b
   const uint64_t tot = *h->h_digtot;  // (the ordered epochs' terms so far: one aligned 8-byte store's value)
   *digest += tot - h->dig_added;
   h->dig_added = tot;
-  if (nend > END_STAGE) NSGPU_HIP(hipStreamSynchronize(h->s));
+  if (nend > END_STAGE || nnote) NSGPU_HIP(hipStreamSynchronize(h->s));
+  if (nnote) {  // (the notifying phys' only: a small set)
+    std::sort(h->notes_epoch.begin(), h->notes_epoch.end(),
+              [](const nsgpu_wifil_note &a, const nsgpu_wifil_note &b) { return a.ts != b.ts ? a.ts < b.ts : a.uid < b.uid; });
+    h->notes.insert(h->notes.end(), h->notes_epoch.begin(), h->notes_epoch.end());
+  }
   std::sort(h->ends_epoch.begin(), h->ends_epoch.end(),
             [](const nsgpu_wifil_end &a, const nsgpu_wifil_end &b) { return a.ts != b.ts ? a.ts < b.ts : a.uid < b.uid; });
   h->ends.insert(h->ends.end(), h->ends_epoch.begin(), h->ends_epoch.end());
@@ -1964,6 +2016,44 @@ extern "C" int nsgpu_wifil_read_phys(nsgpu_wifil *h, nsgpu_wifi_phy_counters *ou
   NSGPU_HIP(hipMemcpyAsync(ps.data(), h->D.ps, ps.size() * sizeof(LPhy), hipMemcpyDeviceToHost, h->s));
   NSGPU_HIP(hipStreamSynchronize(h->s));
   for (size_t j = 0; j < ps.size(); j++) out[j] = wl_counters(ps[j]);
+  return NSGPU_OK;
+}
+
+// RxStart / CCA-busy notifications of phy, from the next advance on (in stream order with the epochs).  The flags
+// and the epoch's note array are sized at the first opt-in: a Receive leaves at most one note, so the array holds
+// what the epoch's event lists hold.
+extern "C" int nsgpu_wifil_notify(nsgpu_wifil *h, uint32_t phy, int on) {
+  if (!h || phy >= h->D.nphy) return set_error(NSGPU_EINVAL, "nsgpu_wifil_notify: bad phy");  // (before anything is sized)
+  if (!h->mem.empty())
+    return set_error(NSGPU_ESTATE, "nsgpu_wifil_notify: notifications are single-engine for now (a partitioned handle)");
+  const uint8_t v = on ? 1 : 0;
+  if (h->note_on.empty()) {
+    if (!v) return NSGPU_OK;
+    const uint64_t cap = (uint64_t)h->D.nphy * EVB + h->D.ev_cap;
+    int rc = wl_alloc(h, &h->d_note_on, (size_t)h->D.nphy);
+    if (!rc) rc = wl_alloc(h, &h->D.notes, (size_t)cap);
+    if (rc) return rc;
+    h->D.note_on = h->d_note_on;
+    h->D.note_cap = cap;
+    h->note_on.assign((size_t)h->D.nphy, 0);
+  }
+  if (h->note_on[phy] == v) return NSGPU_OK;
+  hipLaunchKernelGGL(k_wl_set, dim3(1), dim3(1), 0, h->s, h->d_note_on + phy, (uint32_t)v);
+  NSGPU_HIP(hipGetLastError());
+  h->note_on[phy] = v;
+  h->n_note_on += v ? 1 : (uint64_t)-1;
+  return NSGPU_OK;
+}
+
+// The notes of the epochs advanced since the last call, in (ts, uid) order (cap 0: count only, kept).
+extern "C" int nsgpu_wifil_read_notes(nsgpu_wifil *h, nsgpu_wifil_note *out, uint64_t cap, uint64_t *n) {
+  if (!h || !n) return set_error(NSGPU_EINVAL, "nsgpu_wifil_read_notes: null");
+  *n = h->notes.size();
+  if (!out || cap == 0) return NSGPU_OK;
+  const uint64_t k = std::min<uint64_t>(cap, h->notes.size());
+  std::copy(h->notes.begin(), h->notes.begin() + (ptrdiff_t)k, out);
+  h->notes.erase(h->notes.begin(), h->notes.begin() + (ptrdiff_t)k);
+  *n = k;
   return NSGPU_OK;
 }
 
@@ -2126,7 +2216,7 @@ static int wlg_advance(nsgpu_wifil *G, uint64_t bts, uint32_t buid, uint32_t *ui
   const int P = (int)G->plo.size();
   // (1) every partition's epoch: the batched SendPackets, then its phys' events below the bound
   for (nsgpu_wifil *m : G->mem) {
-    if (m->D.nown) hipLaunchKernelGGL(k_wl_stepw, dim3((unsigned)m->D.nown), dim3(64), 0, s, m->D, bts, buid, m->sb);
+    if (m->D.nown) hipLaunchKernelGGL(k_wl_stepw<false>, dim3((unsigned)m->D.nown), dim3(64), 0, s, m->D, bts, buid, m->sb);
     m->sb.n = 0;
   }
   NSGPU_HIP(hipGetLastError());

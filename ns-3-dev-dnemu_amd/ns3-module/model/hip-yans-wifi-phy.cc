@@ -4,7 +4,11 @@
  *  - which phys a SendPacket's YansWifiChannel::Send reaches, with which uids and contexts: nsgpu_sim_wifi_send /
  *    nsgpu_wifil_send_plan (tests/test_wifi_binding_cpu.py against the oracle's channel loop);
  *  - where the EndReceive's host part runs in the order: the runtime's hand-back (nsgpu_sim_wifi_set_end_handler,
- *    tests/test_gpu_wifi_loop.py: a MAC that replies at each EndReceive, full pop log = the oracle's).
+ *    tests/test_gpu_wifi_loop.py: a MAC that replies at each EndReceive, full pop log = the oracle's);
+ *  - what the state helper is fed with: the device's notes, in order, with Now () set
+ *    (nsgpu_sim_wifi_set_note_handler, tests/test_gpu_wifi_notes.py: the notes, the SendPackets and the end records
+ *    drive a restated WifiPhyStateHelper through every switch with no NS_ASSERT violated, and its state equals the
+ *    device's at every MAC attempt).
  * This file only maps ns-3 objects onto those calls.
  */
 #include "hip-yans-wifi-phy.h"
@@ -16,6 +20,7 @@
 #include "ns3/nist-error-rate-model.h"
 #include "ns3/yans-error-rate-model.h"
 #include "ns3/uinteger.h"
+#include "ns3/pointer.h"
 #include <cmath>
 
 NS_LOG_COMPONENT_DEFINE ("HipYansWifiPhy");
@@ -50,6 +55,21 @@ HipYansWifiPhy::HipYansWifiPhy ()
     m_bound (false),
     m_random (0.0, 1.0)
 {
+}
+
+// YansWifiPhy::m_state (created by its constructor, yans-wifi-phy.cc:135) through the public "State" attribute
+// (:108-111); fetched at the first use, once the object's TypeId is set
+Ptr<WifiPhyStateHelper>
+HipYansWifiPhy::Helper (void)
+{
+  if (m_hipState == 0)
+    {
+      PointerValue state;
+      GetAttribute ("State", state);
+      m_hipState = state.Get<WifiPhyStateHelper> ();
+      NS_ASSERT (m_hipState != 0);
+    }
+  return m_hipState;
 }
 
 void
@@ -94,22 +114,20 @@ HipYansWifiPhy::PowerDbm (uint8_t level) const
   return base;
 }
 
-// YansWifiPhy::SendPacket (yans-wifi-phy.cc:499-522): the traces and the listeners' NotifyTxStart here, the state
-// switch (an RX abandoned: m_endRxEvent.Cancel) and YansWifiChannel::Send on the device
+// YansWifiPhy::SendPacket (yans-wifi-phy.cc:499-522): the traces and the state helper's SwitchToTx here (:510-520,
+// in that order), the device's own switch (an RX abandoned: m_endRxEvent.Cancel) and YansWifiChannel::Send on the
+// device
 void
 HipYansWifiPhy::SendPacket (Ptr<const Packet> packet, WifiMode txMode, enum WifiPreamble preamble, uint8_t txPower)
 {
   NS_LOG_FUNCTION (this << packet << txMode << preamble << (uint32_t) txPower);
-  NS_ASSERT (!IsStateTx ());
+  NS_ASSERT (!Helper ()->IsStateTx () && !IsStateTx ());
   const Time txDuration = CalculateTxDuration (packet->GetSize (), txMode, preamble);
   NotifyTxBegin (packet);
   const uint32_t rate500 = txMode.GetDataRate () / 500000;
   const bool shortPreamble = (WIFI_PREAMBLE_SHORT == preamble);
   NotifyMonitorSniffTx (packet, (uint16_t) GetChannelFrequencyMhz (), GetChannelNumber (), rate500, shortPreamble);
-  for (std::vector<WifiPhyListener *>::const_iterator i = m_listeners.begin (); i != m_listeners.end (); ++i)
-    {
-      (*i)->NotifyTxStart (txDuration);  // (WifiPhyStateHelper::SwitchToTx, wifi-phy-state-helper.cc:254-290)
-    }
+  Helper ()->SwitchToTx (txDuration, packet, txMode, preamble, txPower);  // (:520: m_txTrace, NotifyTxStart, State)
   uint32_t modclass = NSGPU_WIFI_DSSS;
   switch (txMode.GetModulationClass ())
     {
@@ -124,24 +142,12 @@ HipYansWifiPhy::SendPacket (Ptr<const Packet> packet, WifiMode txMode, enum Wifi
                                  shortPreamble ? NSGPU_WIFI_PREAMBLE_SHORT : NSGPU_WIFI_PREAMBLE_LONG));
 }
 
-void
-HipYansWifiPhy::SetReceiveOkCallback (WifiPhy::RxOkCallback callback)
-{
-  m_rxOk = callback;
-  YansWifiPhy::SetReceiveOkCallback (callback);
-}
-
-void
-HipYansWifiPhy::SetReceiveErrorCallback (WifiPhy::RxErrorCallback callback)
-{
-  m_rxError = callback;
-  YansWifiPhy::SetReceiveErrorCallback (callback);
-}
-
+// (SetReceiveOkCallback / SetReceiveErrorCallback are YansWifiPhy's: they set the state helper's, :388-397, which
+// SwitchFromRxEndOk / Error call)
 void
 HipYansWifiPhy::RegisterListener (WifiPhyListener *listener)
 {
-  m_listeners.push_back (listener);
+  Helper ()->RegisterListener (listener);  // (:665-669)
 }
 
 bool
@@ -196,26 +202,33 @@ HipYansWifiPhy::EndReceiveHandBack (const nsgpu_wifil_end &end, Ptr<const Packet
       const double noiseDbm = 10.0 * std::log10 (end.rx_w / end.snr) - GetRxNoiseFigure () + 30;
       NotifyMonitorSniffRx (packet, (uint16_t) GetChannelFrequencyMhz (), GetChannelNumber (), rate500, shortPreamble,
                             signalDbm, noiseDbm);
-      for (std::vector<WifiPhyListener *>::const_iterator i = m_listeners.begin (); i != m_listeners.end (); ++i)
-        {
-          (*i)->NotifyRxEndOk ();  // (SwitchFromRxEndOk, wifi-phy-state-helper.cc:338-352)
-        }
-      if (!m_rxOk.IsNull ())
-        {
-          m_rxOk (packet, end.snr, mode, preamble);
-        }
+      Helper ()->SwitchFromRxEndOk (packet, end.snr, mode, preamble);  // (:791: RxOk trace, NotifyRxEndOk, the MAC)
     }
   else
     {
       NotifyRxDrop (packet);
-      for (std::vector<WifiPhyListener *>::const_iterator i = m_listeners.begin (); i != m_listeners.end (); ++i)
-        {
-          (*i)->NotifyRxEndError ();  // (SwitchFromRxEndError, :354-368)
-        }
-      if (!m_rxError.IsNull ())
-        {
-          m_rxError (packet, end.snr);
-        }
+      Helper ()->SwitchFromRxEndError (packet, end.snr);  // (:797)
+    }
+}
+
+// YansWifiPhy::StartReceivePacket's host-visible part (:417-495) for one Receive the device ran
+void
+HipYansWifiPhy::OnNote (const nsgpu_wifil_note &note, Ptr<const Packet> sent)
+{
+  NS_ASSERT (Simulator::Now ().GetNanoSeconds () == (int64_t) note.ts);
+  Ptr<Packet> packet = sent->Copy ();  // (YansWifiChannel::Send's copy per receiver, :97)
+  if (note.kind == NSGPU_WIFIL_NOTE_SYNC)
+    {
+      Helper ()->SwitchToRx (NanoSeconds (note.rx_duration));  // (:465)
+      NotifyRxBegin (packet);                                    // (:467)
+    }
+  else
+    {
+      NotifyRxDrop (packet);  // (:440 / :451 / :477)
+    }
+  if (note.cca_duration != 0)
+    {
+      Helper ()->SwitchMaybeToCcaBusy (NanoSeconds (note.cca_duration));  // (:491-495)
     }
 }
 
@@ -298,6 +311,7 @@ HipWifiBinding::DoDispose (void)
   if (m_rt)
     {
       nsgpu_sim_wifi_set_end_handler (m_rt, 0, 0);
+      nsgpu_sim_wifi_set_note_handler (m_rt, 0, 0);
     }
   m_phys.clear ();
   m_tx.clear ();
@@ -348,6 +362,17 @@ HipWifiBinding::EndHandBack (void *user, const nsgpu_wifil_end *end)
     }
   const Tx &t = b->m_tx[end->tx];
   b->m_phys[end->phy]->EndReceiveHandBack (*end, t.packet, t.mode, t.preamble);
+}
+
+void
+HipWifiBinding::NoteHandBack (void *user, const nsgpu_wifil_note *note)
+{
+  HipWifiBinding *b = static_cast<HipWifiBinding *> (user);
+  if (note->phy >= b->m_phys.size () || note->tx >= b->m_tx.size ())
+    {
+      NS_FATAL_ERROR ("HipWifiBinding: a notification of an unknown phy / transmission");
+    }
+  b->m_phys[note->phy]->OnNote (*note, b->m_tx[note->tx].packet);
 }
 
 void
@@ -424,10 +449,12 @@ HipWifiBinding::Attach (Ptr<HipSimulatorImpl> impl, Ptr<YansWifiChannel> channel
   m_rt = impl->GetRuntime ();
   NSGPU_RT (nsgpu_sim_attach_wifi (m_rt, m_engine));
   NSGPU_RT (nsgpu_sim_wifi_set_end_handler (m_rt, &HipWifiBinding::EndHandBack, this));
+  NSGPU_RT (nsgpu_sim_wifi_set_note_handler (m_rt, &HipWifiBinding::NoteHandBack, this));
   for (uint32_t i = 0; i < n; i++)
     {
       m_phys[i]->Bind (this, m_rt, i);
       NSGPU_RT (nsgpu_sim_wifi_listen (m_rt, i, 1));  // (every phy's EndReceive runs its MAC callbacks)
+      NSGPU_RT (nsgpu_sim_wifi_notify (m_rt, i, 1));  // (and its StartReceivePackets drive its state helper)
     }
 }
 

@@ -8,7 +8,11 @@
  *    queries (IsStateIdle / Rx / Tx / CcaBusy, GetDelayUntilIdle: wifi-phy-state-helper.cc:122-183) read the
  *    device's state through nsgpu_sim_wifi_state, and EndReceive (yans-wifi-phy.cc:770-799) comes back to the host
  *    at its place in the event order (nsgpu_sim_wifi_set_end_handler): the m_random draw, the Rx traces and the
- *    MAC's receive callbacks run here, so their Schedule calls take the uids the reference's would.
+ *    MAC's receive callbacks run here, so their Schedule calls take the uids the reference's would.  The phy
+ *    drives ns-3's own WifiPhyStateHelper (the "State" attribute, yans-wifi-phy.cc:108-111): SwitchToTx at
+ *    SendPacket, SwitchFromRxEndOk / Error at the hand-back, and SwitchToRx / SwitchMaybeToCcaBusy from the
+ *    device's notifications (nsgpu_sim_wifi_set_note_handler) — so the registered WifiPhyListeners (DcfManager's)
+ *    and the State / Tx / RxOk / RxError trace sources fire as the reference's do.
  *  - ns3::HipYansWifiPhyHelper : YansWifiPhyHelper — Create () makes HipYansWifiPhy objects (the stock helper's
  *    Create hard-codes ns3::YansWifiPhy, yans-wifi-helper.cc:232-241); everything else (pcap / ascii) is the
  *    stock helper's.
@@ -16,9 +20,10 @@
  *    channel numbers, nodes and PHY attributes into a nsgpu_wifil_config, the engine created and attached to the
  *    HipSimulatorImpl's runtime, every phy bound to its index and handed back.
  *
- * Not delivered (documented in INTEGRATION.md §3.2): WifiPhyListener::NotifyRxStart / NotifyMaybeCcaBusyStart at the
- * device's syncs / CCA switches (NotifyTxStart and NotifyRxEndOk / Error are); a MAC that reads the state when it
- * needs it (GetState / IsStateIdle) is exact.
+ * Notifications: a StartReceivePacket's switches (NotifyRxStart, NotifyMaybeCcaBusyStart,
+ * the PhyRxBegin / PhyRxDrop traces) are delivered after the device epoch that ran it, with Now () set to its time,
+ * before the host event that bounded the epoch; DcfManager's Notify*Now schedule nothing, so that is exact.  A
+ * listener that schedules or sends from such a notification is refused by the runtime (NSGPU_ESTATE).
  */
 #ifndef HIP_YANS_WIFI_PHY_H
 #define HIP_YANS_WIFI_PHY_H
@@ -26,6 +31,7 @@
 #include "ns3/yans-wifi-phy.h"
 #include "ns3/yans-wifi-helper.h"
 #include "ns3/yans-wifi-channel.h"
+#include "ns3/wifi-phy-state-helper.h"
 #include "ns3/random-variable.h"
 #include "ns3/object-factory.h"
 #include "ns3/packet.h"
@@ -48,8 +54,6 @@ public:
   uint32_t GetIndex (void) const;
 
   virtual void SendPacket (Ptr<const Packet> packet, WifiMode mode, enum WifiPreamble preamble, uint8_t txPowerLevel);
-  virtual void SetReceiveOkCallback (WifiPhy::RxOkCallback callback);
-  virtual void SetReceiveErrorCallback (WifiPhy::RxErrorCallback callback);
   virtual void RegisterListener (WifiPhyListener *listener);
   virtual bool IsStateCcaBusy (void);
   virtual bool IsStateIdle (void);
@@ -63,9 +67,13 @@ public:
    * the m_random draw against the device's PER, then the traces and the MAC's callbacks (:783-798) */
   void EndReceiveHandBack (const nsgpu_wifil_end &end, Ptr<const Packet> packet, WifiMode mode,
                            enum WifiPreamble preamble);
+  /* one StartReceivePacket of this phy on the device (yans-wifi-phy.cc:417-495), called by the runtime after the
+   * epoch that ran it (Now () = its time): the state helper's switches and the PhyRxBegin / PhyRxDrop traces */
+  void OnNote (const nsgpu_wifil_note &note, Ptr<const Packet> packet);
 
 private:
   nsgpu_wifil_phy_state State (void) const;
+  Ptr<WifiPhyStateHelper> Helper (void);
   /* YansWifiPhy::GetPowerDbm (:753-768, private there) from the public attributes */
   double PowerDbm (uint8_t level) const;
 
@@ -74,9 +82,7 @@ private:
   uint32_t m_index;
   bool m_bound;
   UniformVariable m_random;  // YansWifiPhy::m_random (:783)
-  WifiPhy::RxOkCallback m_rxOk;
-  WifiPhy::RxErrorCallback m_rxError;
-  std::vector<WifiPhyListener *> m_listeners;
+  Ptr<WifiPhyStateHelper> m_hipState;  // YansWifiPhy::m_state (private there), through the "State" attribute
 };
 
 class HipYansWifiPhyHelper : public YansWifiPhyHelper
@@ -119,6 +125,7 @@ public:
 private:
   virtual void DoDispose (void);
   static void EndHandBack (void *user, const nsgpu_wifil_end *end);
+  static void NoteHandBack (void *user, const nsgpu_wifil_note *note);
 
   struct Tx
   {

@@ -177,6 +177,10 @@ SIGNATURES = {
     "nsgpu_wifil_create_group": (C.c_int, [_vp, _vp, C.c_int, C.POINTER(C.c_void_p)]),
     "nsgpu_sim_wifi_set_end_handler": (C.c_int, [_vp, _vp, _vp]),
     "nsgpu_sim_wifi_listen": (C.c_int, [_vp, _u32, C.c_int]),
+    "nsgpu_wifil_notify": (C.c_int, [_vp, _u32, C.c_int]),
+    "nsgpu_wifil_read_notes": (C.c_int, [_vp, _vp, _u64, _vp]),
+    "nsgpu_sim_wifi_set_note_handler": (C.c_int, [_vp, _vp, _vp]),
+    "nsgpu_sim_wifi_notify": (C.c_int, [_vp, _u32, C.c_int]),
     "nsgpu_p2p_group_create": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_void_p)]),
     "nsgpu_p2p_group_reset": (C.c_int, [_vp, _vp]),
     "nsgpu_p2p_group_run": (C.c_int, [_vp, _vp]),
@@ -525,6 +529,7 @@ class EventId(C.Structure):  # nsgpu_event_id
 
 EVENT_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint64)
 WIFI_END_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p)  # nsgpu_wifi_end_fn (user, const nsgpu_wifil_end *)
+WIFI_NOTE_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p)  # nsgpu_wifi_note_fn (user, const nsgpu_wifil_note *)
 
 
 class Sched:
@@ -778,6 +783,28 @@ class Sim:
     def wifi_listen(self, phy, on=True):
         """The hand-back for `phy`'s EndReceives on (or off)."""
         check(lib().nsgpu_sim_wifi_listen(self.h, phy, 1 if on else 0))
+
+    def wifi_set_note_handler(self, fn):
+        """RxStart / CCA-busy notifications (nsgpu_sim_wifi_set_note_handler): fn(note) — a wifi.WIFIL_NOTE_DTYPE
+        record — runs after each epoch of the PHY for every StartReceivePacket of a notifying phy (wifi_notify), in
+        (ts, uid) order, with now () / current_uid () / context () the Receive event's.  fn must not schedule or
+        send.  fn None: none (the notes stay readable through LoopPhy.read_notes)."""
+        import wifi
+        if fn is None:
+            check(lib().nsgpu_sim_wifi_set_note_handler(self.h, None, None))
+            self._note_cb = None
+            return
+        size = wifi.WIFIL_NOTE_DTYPE.itemsize
+
+        def tramp(user, p):
+            fn(np.frombuffer(C.string_at(p, size), wifi.WIFIL_NOTE_DTYPE)[0])
+
+        self._note_cb = WIFI_NOTE_FN(tramp)
+        check(lib().nsgpu_sim_wifi_set_note_handler(self.h, C.cast(self._note_cb, C.c_void_p), None))
+
+    def wifi_notify(self, phy, on=True):
+        """`phy`'s notifications on (or off), from the next epoch on."""
+        check(lib().nsgpu_sim_wifi_notify(self.h, phy, 1 if on else 0))
 
     def wifi_state(self, phy):
         """WifiPhyStateHelper::GetState of `phy` now: (state, delay until idle ns)."""

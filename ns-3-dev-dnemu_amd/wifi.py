@@ -262,6 +262,9 @@ NIST, YANS = 0, 1  # nsgpu_wifil_error_model
 IDLE, RX, TX, CCA_BUSY = 0, 1, 2, 3  # nsgpu_wifil_state
 WIFIL_END_DTYPE = np.dtype([("ts", "<u8"), ("uid", "<u4"), ("phy", "<u4"), ("snr", "<f8"), ("per", "<f8"),
                             ("tx", "<u4"), ("flags", "<u4"), ("rx_w", "<f8")])
+NOTE_SYNC, NOTE_DROP_RX, NOTE_DROP_TX, NOTE_DROP_ED = 0, 1, 2, 3  # NSGPU_WIFIL_NOTE_*
+WIFIL_NOTE_DTYPE = np.dtype([("ts", "<u8"), ("uid", "<u4"), ("phy", "<u4"), ("tx", "<u4"), ("kind", "<u4"),
+                             ("state", "<u4"), ("pad_", "<u4"), ("rx_duration", "<i8"), ("cca_duration", "<i8")])
 
 
 # ---- sniffer records (YansWifiPhyHelper's pcap / ascii sinks; the codec is in libnsgpu: nsgpu_wifi_*) ----
@@ -424,6 +427,19 @@ class LoopPhy:
         if n.value:
             nsgpu.check(nsgpu.lib().nsgpu_wifil_read_ends(self.h, out.ctypes.data, n.value, C.byref(n)))
         return out
+
+    def notify(self, phy, on=True):
+        """One nsgpu_wifil_note per StartReceivePacket of `phy` from the next advance on (or none: on=False)."""
+        nsgpu.check(nsgpu.lib().nsgpu_wifil_notify(self.h, phy, 1 if on else 0))
+
+    def read_notes(self):
+        """The notes of the epochs advanced since the last call (WIFIL_NOTE_DTYPE, (ts, uid) order)."""
+        n = C.c_uint64()
+        nsgpu.check(nsgpu.lib().nsgpu_wifil_read_notes(self.h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, WIFIL_NOTE_DTYPE)
+        if n.value:
+            nsgpu.check(nsgpu.lib().nsgpu_wifil_read_notes(self.h, out.ctypes.data, n.value, C.byref(n)))
+        return out[:n.value]
 
     def read_phys(self):
         out = np.zeros(self.phys.n_phy, PHY_COUNTERS_DTYPE)
