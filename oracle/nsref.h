@@ -220,6 +220,15 @@ typedef struct nsref_wifil_sends {
 int nsref_wifil_replay(const nsgpu_wifil_config *cfg, const nsref_wifil_sends *sn, uint64_t *log_ts, uint32_t *log_uid,
                        uint32_t *log_ctx, uint64_t log_cap, nsgpu_wifil_end *ends, uint64_t ends_cap, uint64_t *n_ends,
                        nsgpu_wifi_phy_counters *phys, uint64_t out[6], uint64_t *tx_out, uint64_t tx_cap);
+/* The same replay with a mode and a preamble per send (sn's own modclass / rate / bw / preamble are not read). */
+typedef struct nsref_wifil_send_modes {
+  const uint32_t *modclass, *bw, *preamble;
+  const uint64_t *rate;
+} nsref_wifil_send_modes;
+int nsref_wifil_replay_modes(const nsgpu_wifil_config *cfg, const nsref_wifil_sends *sn,
+                             const nsref_wifil_send_modes *modes, uint64_t *log_ts, uint32_t *log_uid, uint32_t *log_ctx,
+                             uint64_t log_cap, nsgpu_wifil_end *ends, uint64_t ends_cap, uint64_t *n_ends,
+                             nsgpu_wifi_phy_counters *phys, uint64_t out[6], uint64_t *tx_out, uint64_t tx_cap);
 /* InterferenceHelper::CalculateChunkSuccessRate's error-rate model call for one chunk (tests). */
 double nsref_wifil_chunk_success(uint32_t model, uint32_t modclass, uint64_t rate, uint32_t bw, double snr, uint32_t nbits);
 

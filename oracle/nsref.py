@@ -539,16 +539,22 @@ class WifilSendsStruct(C.Structure):  # nsref_wifil_sends (nsref.h)
                 ("move_ts", C.c_void_p), ("move_phy", C.c_void_p), ("move_xyz", C.c_void_p)]
 
 
+class WifilSendModesStruct(C.Structure):  # nsref_wifil_send_modes (nsref.h)
+    _fields_ = [("modclass", C.c_void_p), ("bw", C.c_void_p), ("preamble", C.c_void_p), ("rate", C.c_void_p)]
+
+
 def wifil_replay(cfg_struct, ts, phy, size, mode, preamble, dbm, stop_ts, n_phy, end_dtype, phys_dtype, log_cap=1 << 16,
-                 moves=()):
-    """moves: [(ts, phy, (x, y, z))] — MobilityModel::SetPosition host closures scheduled after the sends."""
+                 moves=(), modes=None, preambles=None):
     """A replayed transmission schedule on the closed-loop oracle PHY (nsref_wifil_replay): SendPacket of phy[k]
     (size[k] bytes) at ts[k], host closures scheduled at setup in send order, then Stop (stop_ts).  Returns as
-    wifil_run."""
-    f = lib().nsref_wifil_replay
+    wifil_run.
+    moves: [(ts, phy, (x, y, z))] — MobilityModel::SetPosition host closures scheduled after the sends.
+    modes, preambles: per-send (modclass, rate, bw) tuples and preambles (both or neither; default: mode, preamble
+    for every send) — nsref_wifil_replay_modes."""
+    f = lib().nsref_wifil_replay_modes
     f.restype = C.c_int
-    f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
-                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                  C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
     ts = np.ascontiguousarray(ts, np.uint64)
     phy = np.ascontiguousarray(phy, np.uint32)
     size = np.ascontiguousarray(size, np.uint32)
@@ -557,6 +563,15 @@ def wifil_replay(cfg_struct, ts, phy, size, mode, preamble, dbm, stop_ts, n_phy,
     mxyz = np.array([c for m in moves for c in m[2]] or [0.0], np.float64)
     sn = WifilSendsStruct(len(ts), ts.ctypes.data, phy.ctypes.data, size.ctypes.data, mode[0], mode[2], preamble, 0,
                           mode[1], stop_ts, dbm, len(moves), mts.ctypes.data, mph.ctypes.data, mxyz.ctypes.data)
+    sm = None
+    if modes is not None:
+        if len(modes) != len(ts) or len(preambles) != len(ts):
+            raise ValueError("wifil_replay: one mode and one preamble per send")
+        kmc = np.array([m[0] for m in modes], np.uint32)
+        krate = np.array([m[1] for m in modes], np.uint64)
+        kbw = np.array([m[2] for m in modes], np.uint32)
+        kpre = np.ascontiguousarray(preambles, np.uint32)
+        sm = C.byref(WifilSendModesStruct(kmc.ctypes.data, kbw.ctypes.data, kpre.ctypes.data, krate.ctypes.data))
     lts = np.zeros(log_cap, np.uint64)
     luid = np.zeros(log_cap, np.uint32)
     lctx = np.zeros(log_cap, np.uint32)
@@ -564,9 +579,9 @@ def wifil_replay(cfg_struct, ts, phy, size, mode, preamble, dbm, stop_ts, n_phy,
     out = np.zeros(6, np.uint64)
     n = C.c_uint64()
     txo = np.zeros((len(ts) + 1, 3), np.uint64)
-    args = lambda ends, cap: (C.byref(cfg_struct), C.byref(sn), lts.ctypes.data, luid.ctypes.data, lctx.ctypes.data,
-                              log_cap, ends, cap, C.byref(n), phys.ctypes.data, out.ctypes.data, txo.ctypes.data,
-                              txo.shape[0])
+    args = lambda ends, cap: (C.byref(cfg_struct), C.byref(sn), sm, lts.ctypes.data, luid.ctypes.data,
+                              lctx.ctypes.data, log_cap, ends, cap, C.byref(n), phys.ctypes.data, out.ctypes.data,
+                              txo.ctypes.data, txo.shape[0])
     rc = f(*args(None, 0))
     if rc != 0:
         raise RuntimeError(f"nsref_wifil_replay: {rc}")

@@ -797,9 +797,11 @@ int nsref_wifi_run(const nsgpu_wifi_scenario *sc, nsgpu_wifi_stats *stats, nsgpu
 
 // A replayed transmission schedule: host closures scheduled at setup in send order (Schedule (ts_k, SendPacket
 // of phy_k)), then Simulator::Stop (Time); the same PHY and run loop as nsref_wifil_run.
-int nsref_wifil_replay(const nsgpu_wifil_config *cfg, const nsref_wifil_sends *sn, uint64_t *log_ts, uint32_t *log_uid,
-                       uint32_t *log_ctx, uint64_t log_cap, nsgpu_wifil_end *ends, uint64_t ends_cap, uint64_t *n_ends,
-                       nsgpu_wifi_phy_counters *phys, uint64_t out[6], uint64_t *tx_out, uint64_t tx_cap) {
+// (modes: a mode and a preamble per send, or NULL: sn's for every send.)
+int nsref_wifil_replay_modes(const nsgpu_wifil_config *cfg, const nsref_wifil_sends *sn,
+                             const nsref_wifil_send_modes *modes, uint64_t *log_ts, uint32_t *log_uid, uint32_t *log_ctx,
+                             uint64_t log_cap, nsgpu_wifil_end *ends, uint64_t ends_cap, uint64_t *n_ends,
+                             nsgpu_wifi_phy_counters *phys, uint64_t out[6], uint64_t *tx_out, uint64_t tx_cap) {
   Loop L;
   L.cfg = cfg;
   L.mac = nullptr;
@@ -834,7 +836,9 @@ int nsref_wifil_replay(const nsgpu_wifil_config *cfg, const nsref_wifil_sends *s
     }
     if (e.kind == Loop::STOP) break;
     if (e.kind == Loop::SEND) {
-      const int rc = L.send_packet(sn->phy[e.a], sn->size[e.a], sn->modclass, sn->rate, sn->bw, sn->preamble, sn->dbm);
+      const int rc = L.send_packet(sn->phy[e.a], sn->size[e.a], modes ? modes->modclass[e.a] : sn->modclass,
+                                   modes ? modes->rate[e.a] : sn->rate, modes ? modes->bw[e.a] : sn->bw,
+                                   modes ? modes->preamble[e.a] : sn->preamble, sn->dbm);
       if (rc) return rc;
     } else if (e.kind == Loop::MOVE) {
       const uint32_t j = sn->move_phy[e.a];
@@ -865,6 +869,13 @@ int nsref_wifil_replay(const nsgpu_wifil_config *cfg, const nsref_wifil_sends *s
   if (phys)
     for (int64_t j = 0; j < cfg->n_phy; j++) phys[j] = L.phy[(size_t)j].c;
   return 0;
+}
+
+int nsref_wifil_replay(const nsgpu_wifil_config *cfg, const nsref_wifil_sends *sn, uint64_t *log_ts, uint32_t *log_uid,
+                       uint32_t *log_ctx, uint64_t log_cap, nsgpu_wifil_end *ends, uint64_t ends_cap, uint64_t *n_ends,
+                       nsgpu_wifi_phy_counters *phys, uint64_t out[6], uint64_t *tx_out, uint64_t tx_cap) {
+  return nsref_wifil_replay_modes(cfg, sn, nullptr, log_ts, log_uid, log_ctx, log_cap, ends, ends_cap, n_ends, phys, out,
+                                  tx_out, tx_cap);
 }
 
 double nsref_wifil_chunk_success(uint32_t model, uint32_t modclass, uint64_t rate, uint32_t bw, double snr, uint32_t nbits) {

@@ -1,9 +1,11 @@
 """Closed-loop Wi-Fi (config 3 with the MAC on the host): host closures send only when the
 device reports the phy IDLE, EndReceive's (snr, per) go back to the host for its draw.  GPU = oracle on the
 full (ts, uid, context) pop log, the digest, the per-phy counters and state; SNR / PER within 1e-9
-relative (device libm vs glibc; the state machine does not depend on them).  SNR / PER are parity
-unpinned: the reference holds no CalculateSnrPer fixture (wifi-interference-test-suite.cc only compares
-PERs of its own runs)."""
+relative (device libm vs glibc; the state machine does not depend on them).  The reference holds no
+CalculateSnrPer fixture (wifi-interference-test-suite.cc only compares PERs of its own runs), so no
+reference-held vector pins SNR / PER; what pins them is tests/wifi_per_ref.py, an independent high-precision
+evaluation of the reference's formulas, to which tests/test_gpu_wifi_per.py holds the device (every mode,
+both models, CalculatePer's interval cases) and tests/test_wifi_per_cpu.py the oracle used here."""
 import numpy as np
 import pytest
 

@@ -2,7 +2,10 @@
 (nist-error-rate-model.cc, yans-error-rate-model.cc, dsss-error-rate-model.cc — restated here in Python from
 the same lines), CalculatePer on an isolated reception (interference-helper.cc:257-334: the preamble is not a
 chunk, the header at the header mode, the payload at the payload mode), and the run's invariants.  No
-reference fixture pins SNR / PER (parity unpinned); tests/test_gpu_wifi_loop.py compares the device with this."""
+reference-held vector pins SNR / PER; they are pinned by tests/wifi_per_ref.py, an independent high-precision
+evaluation of the reference's formulas (tests/test_wifi_per_cpu.py holds this oracle to it over every mode, both
+models and CalculatePer's interval cases; the three spot checks below stay as quick known answers).
+tests/test_gpu_wifi_loop.py compares the device with this oracle."""
 import math
 
 import numpy as np
