@@ -214,6 +214,29 @@ int nsgpu_wifil_get_state(nsgpu_wifil *h, uint32_t phy, uint64_t now, nsgpu_wifi
 /* MobilityModel::SetPosition of phy's node (src/mobility/model/mobility-model.cc): the later SendPackets'
  * YansWifiChannel::Send fan-outs (yans-wifi-channel.cc:92-96) read the new position */
 int nsgpu_wifil_set_position(nsgpu_wifil *h, uint32_t phy, double x, double y, double z);
+/* Constant-velocity mobility on the device: ConstantVelocityHelper (constant-velocity-helper.cc) per phy — what
+ * ConstantVelocityMobilityModel, Ns2MobilityHelper's replays and RandomWaypointMobilityModel's legs integrate through.
+ * A phy with a model accumulates m_position += m_velocity * (now - m_lastUpdate).GetSeconds () (Update, :69-84, no
+ * FMA) at the reference's accumulation points: at a SendPacket every other phy of the sender's channel number
+ * updates, and the sender if there is at least one of them (yans-wifi-channel.cc:84-96 through
+ * MobilityModel::GetDistanceFrom, mobility-model.cc:78-84); phys on other channels keep their m_lastUpdate.  A phy
+ * that was never given a model stays a ConstantPositionMobilityModel, and a run with no model launches the kernels
+ * it launched without this interface.  Every call runs in stream order with the sends:
+ *   set_mobility     installs *m (NULL: back to constant position, at the position held then);
+ *   set_velocity     ConstantVelocityMobilityModel::SetVelocity (constant-velocity-mobility-model.cc:43-50): Update,
+ *                    SetVelocity, Unpause;
+ *   pause            Update, then Pause (paused != 0) / Unpause (RandomWaypoint's legs);
+ *   set_position_at  ConstantVelocityHelper::SetPosition (:43-49): position, velocity 0, m_lastUpdate = now (a phy
+ *                    without a model: nsgpu_wifil_set_position, `now` unused);
+ *   get_mobility     GetPosition + GetVelocity at now: performs Update — an accumulation point, as in ns-3.
+ * phy >= n_phy: NSGPU_EINVAL, before anything is touched.  set_velocity / pause / get_mobility on a phy without a
+ * model, and the untimed nsgpu_wifil_set_position on a phy with one (it has no `now`): NSGPU_ESTATE.  A partitioned
+ * handle (create_dist / create_group) refuses set_mobility with NSGPU_EINVAL: mobility is single-engine for now. */
+int nsgpu_wifil_set_mobility(nsgpu_wifil *h, uint32_t phy, const nsgpu_mobility *m);
+int nsgpu_wifil_set_velocity(nsgpu_wifil *h, uint64_t now, uint32_t phy, const double v[3]);
+int nsgpu_wifil_pause(nsgpu_wifil *h, uint64_t now, uint32_t phy, uint32_t paused);
+int nsgpu_wifil_set_position_at(nsgpu_wifil *h, uint64_t now, uint32_t phy, double x, double y, double z);
+int nsgpu_wifil_get_mobility(nsgpu_wifil *h, uint64_t now, uint32_t phy, nsgpu_mobility *out);
 int nsgpu_wifil_read_ends(nsgpu_wifil *h, nsgpu_wifil_end *out, uint64_t cap, uint64_t *n);  /* since last read */
 int nsgpu_wifil_read_phys(nsgpu_wifil *h, nsgpu_wifi_phy_counters *out);                    /* n_phy */
 int nsgpu_wifil_pending(nsgpu_wifil *h, uint64_t *n, uint64_t *next_ts);
@@ -390,6 +413,14 @@ int nsgpu_sim_wifi_send(nsgpu_sim *s, uint32_t phy, uint32_t size, double dbm, u
 int nsgpu_sim_wifi_state(nsgpu_sim *s, uint32_t phy, nsgpu_wifil_phy_state *out);
 /* a host closure's MobilityModel::SetPosition of phy's node (nsgpu_wifil_set_position on the attached PHY) */
 int nsgpu_sim_wifi_set_position(nsgpu_sim *s, uint32_t phy, double x, double y, double z);
+/* constant-velocity mobility of the attached PHY's phys (nsgpu_wifil_set_mobility and its neighbours) from the
+ * running closure: the timed calls take Now ().  nsgpu_sim_wifi_set_position above goes to
+ * nsgpu_wifil_set_position_at when the phy has a model.  nsgpu_sim_wifi_get_mobility is MobilityModel::GetPosition /
+ * GetVelocity: host code that reads a position goes through it, since the read is an accumulation point. */
+int nsgpu_sim_wifi_set_mobility(nsgpu_sim *s, uint32_t phy, const nsgpu_mobility *m);
+int nsgpu_sim_wifi_set_velocity(nsgpu_sim *s, uint32_t phy, const double v[3]);
+int nsgpu_sim_wifi_pause(nsgpu_sim *s, uint32_t phy, uint32_t paused);
+int nsgpu_sim_wifi_get_mobility(nsgpu_sim *s, uint32_t phy, nsgpu_mobility *out);
 /* EndReceive hand-back (YansWifiPhy::EndReceive, yans-wifi-phy.cc:770-799): for every phy marked with
  * nsgpu_sim_wifi_listen, the runtime stops the device AT each of the phy's EndReceives (the event itself runs on
  * the device: CalculateSnrPer, the state switch) and calls fn (user, &end) right there in the (ts, uid) order,

@@ -271,7 +271,8 @@ enum nsgpu_wifi_preamble { NSGPU_WIFI_PREAMBLE_LONG = 0, NSGPU_WIFI_PREAMBLE_SHO
 
 typedef struct nsgpu_wifi_scenario {
   int64_t n_phy;                /* YansWifiChannel::m_phyList, in Add order */
-  const double *x, *y, *z;      /* ConstantPositionMobilityModel positions */
+  const double *x, *y, *z;      /* ConstantPositionMobilityModel positions (the open-loop engine mirrors no other
+                                 * model: its reception table assumes fixed distances) */
   const uint32_t *channel;      /* GetChannelNumber () */
   const uint32_t *node;         /* context of the Receive events (0xffffffff: no NetDevice) */
   nsgpu_loss_chain loss;
@@ -357,7 +358,8 @@ NSGPU_HD static inline uint64_t nsgpu_wifi_term(uint64_t kind, uint64_t ts, uint
 /* ---- closed-loop Wi-Fi PHY (nsgpu_wifil_*, attached to nsgpu_sim: SendPacket from host closures) ---- */
 typedef struct nsgpu_wifil_config {
   int64_t n_phy;                /* YansWifiChannel::m_phyList, in Add order */
-  const double *x, *y, *z;      /* ConstantPositionMobilityModel positions */
+  const double *x, *y, *z;      /* positions at setup: every phy starts as a ConstantPositionMobilityModel; a
+                                 * constant-velocity model is installed per phy afterwards (nsgpu_wifil_set_mobility) */
   const uint32_t *channel;      /* GetChannelNumber () */
   const uint32_t *node;         /* context of the Receive / EndReceive events */
   nsgpu_loss_chain loss;
@@ -408,6 +410,16 @@ typedef struct nsgpu_wifil_note {
   int64_t cca_duration;   /* GetEnergyDuration's result when maybeCcaBusy was reached and it is non-zero
                              (the argument of SwitchMaybeToCcaBusy), else 0 */
 } nsgpu_wifil_note;
+
+/* ConstantVelocityHelper of one phy's node (constant-velocity-helper.h; nsgpu_wifil_set_mobility /
+ * nsgpu_wifil_get_mobility): what ConstantVelocityMobilityModel, Ns2MobilityHelper's replays and
+ * RandomWaypointMobilityModel's legs integrate through.  The device restates ConstantVelocityHelper::Update
+ * (constant-velocity-helper.cc:69-84) at every accumulation point, in the reference's order of operations. */
+typedef struct nsgpu_mobility {
+  double pos[3], vel[3];   /* m_position, m_velocity (get: GetVelocity — zero while paused) */
+  int64_t last_update;     /* m_lastUpdate, ns */
+  uint32_t paused, pad_;   /* m_paused (a fresh ConstantVelocityMobilityModel is paused) */
+} nsgpu_mobility;
 
 #ifdef __cplusplus
 }

@@ -769,7 +769,27 @@ int nsgpu_sim_wifi_listen(nsgpu_sim *s, uint32_t phy, int on) {
 // MobilityModel::SetPosition of `phy`'s node from the running closure: the later SendPackets' fan-outs see it.
 int nsgpu_sim_wifi_set_position(nsgpu_sim *s, uint32_t phy, double x, double y, double z) {
   if (!s || !s->wifi) return set_error(NSGPU_ESTATE, "nsgpu_sim_wifi_set_position: no Wi-Fi PHY attached");
-  return nsgpu_wifil_set_position(s->wifi, phy, x, y, z);
+  // (a phy with a constant-velocity model: ConstantVelocityHelper::SetPosition at Now; one without: the untimed call)
+  return nsgpu_wifil_set_position_at(s->wifi, s->cur_ts, phy, x, y, z);
+}
+
+// Constant-velocity mobility of the attached PHY's phys from the running closure (the timed calls at Now).
+int nsgpu_sim_wifi_set_mobility(nsgpu_sim *s, uint32_t phy, const nsgpu_mobility *m) {
+  if (!s || !s->wifi) return set_error(NSGPU_ESTATE, "nsgpu_sim_wifi_set_mobility: no Wi-Fi PHY attached");
+  return nsgpu_wifil_set_mobility(s->wifi, phy, m);
+}
+int nsgpu_sim_wifi_set_velocity(nsgpu_sim *s, uint32_t phy, const double v[3]) {
+  if (!s || !s->wifi) return set_error(NSGPU_ESTATE, "nsgpu_sim_wifi_set_velocity: no Wi-Fi PHY attached");
+  return nsgpu_wifil_set_velocity(s->wifi, s->cur_ts, phy, v);
+}
+int nsgpu_sim_wifi_pause(nsgpu_sim *s, uint32_t phy, uint32_t paused) {
+  if (!s || !s->wifi) return set_error(NSGPU_ESTATE, "nsgpu_sim_wifi_pause: no Wi-Fi PHY attached");
+  return nsgpu_wifil_pause(s->wifi, s->cur_ts, phy, paused);
+}
+// MobilityModel::GetPosition / GetVelocity of `phy`'s node at Now: an accumulation point, as in ns-3.
+int nsgpu_sim_wifi_get_mobility(nsgpu_sim *s, uint32_t phy, nsgpu_mobility *out) {
+  if (!s || !s->wifi) return set_error(NSGPU_ESTATE, "nsgpu_sim_wifi_get_mobility: no Wi-Fi PHY attached");
+  return nsgpu_wifil_get_mobility(s->wifi, s->cur_ts, phy, out);
 }
 
 // WifiPhyStateHelper::GetState of `phy` at Now (the device has run every event before the running closure).

@@ -83,6 +83,12 @@ struct LSync {  // one sync of the epoch (its EndReceive's uid comes from the sy
   uint32_t suid, euid;
   uint32_t loc, pad;  // its pending EndReceive record: pe[loc]
 };
+struct WMob {  // a phy's ConstantVelocityHelper (constant-velocity-helper.h) next to its position D.x / y / z
+  double vx, vy, vz;     // m_velocity
+  int64_t last;          // m_lastUpdate, ns
+  uint32_t flags, pad;   // MOB_ON: a model is installed (clear: a constant-position phy); MOB_PAUSED: m_paused
+};
+constexpr uint32_t MOB_ON = 1, MOB_PAUSED = 2;
 struct LCk {  // one chunk of an EndReceive's CalculatePer walk, evaluated by k_wl_mid: the noise before it,
   double noise;  // and (duration << 1) | (1: the PLCP header mode)
   int64_t dm;
@@ -144,6 +150,9 @@ struct WDev {
   const uint32_t *note_on;
   nsgpu_wifil_note *notes;
   uint64_t note_cap;
+  // constant-velocity mobility (nsgpu_wifil_set_mobility): a record per phy, sized at the first install (null
+  // until then); k_wl_move, launched ahead of a send's k_wl_rx only while some phy has a model, updates x / y / z
+  WMob *mob;
 };
 // The epoch's dispatched events are appended to EV_STRIPES lists (phy j's to stripe j % EV_STRIPES): one
 // counter a phy's event would serialize ~10^4 atomics an epoch on one line.
@@ -325,6 +334,21 @@ __device__ __forceinline__ double get_seconds(const WDev &D, int64_t ts) {
   double v = (double)hi;
   v += flo;
   return neg ? -v : v;
+}
+// ConstantVelocityHelper::Update (constant-velocity-helper.cc:69-84) of phy j at `now`, restated literally: the
+// products and sums round one by one (the library is built -ffp-contract=off: no FMA), so the doubles depend on
+// the accumulation points exactly as the reference's do.  A phy without a model is untouched.
+__device__ __forceinline__ void mob_update(const WDev &D, int64_t j, int64_t now) {
+  WMob &m = D.mob[j];
+  if (!(m.flags & MOB_ON)) return;
+  const int64_t delta = now - m.last;  // Time deltaTime = now - m_lastUpdate
+  m.last = now;
+  if (m.flags & MOB_PAUSED) return;
+  const double deltaS = get_seconds(D, delta);
+  double *const x = const_cast<double *>(D.x), *const y = const_cast<double *>(D.y), *const z = const_cast<double *>(D.z);
+  x[j] += m.vx * deltaS;
+  y[j] += m.vy * deltaS;
+  z[j] += m.vz * deltaS;
 }
 // InterferenceHelper::CalculateChunkSuccessRate — interference-helper.cc:244-255
 __device__ double chunk(const WDev &D, double snir, int64_t duration, const Mode &m) {
@@ -1349,6 +1373,58 @@ __global__ __launch_bounds__(256) void k_wl_rx(const WDev D, LRx *row, LTx t, ui
   row[j] = e;
 }
 
+// The position reads of one SendPacket of phy s at `now` (YansWifiChannel::Send, yans-wifi-channel.cc:84-96: per
+// receiver GetDelay / CalcRxPower -> MobilityModel::GetDistanceFrom, mobility-model.cc:78-84, reads the receiver's
+// position and the sender's): every phy of the sender's channel number other than the sender updates, and the
+// sender when there is at least one of them (upd_sender; its later updates of the same send have a zero delta);
+// phys on other channels keep their m_lastUpdate.  One lane per phy, launched ahead of the send's k_wl_rx — whose
+// every lane reads the sender's position, so the update is not made in place there — and only while some phy has
+// a model: a run without one launches k_wl_rx alone, as before.
+__global__ __launch_bounds__(256) void k_wl_move(const WDev D, uint32_t s, int64_t now, uint32_t upd_sender) {
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (j >= D.nphy) return;
+  if (j == (int64_t)s ? !upd_sender : D.chan[j] != D.chan[s]) return;
+  mob_update(D, j, now);
+}
+// A host call on one phy's model, in stream order with the sends (one thread, as k_wl_set):
+// install / remove (nsgpu_wifil_set_mobility), ConstantVelocityMobilityModel::SetVelocity
+// (constant-velocity-mobility-model.cc:43-50), Update + Pause / Unpause, ConstantVelocityHelper::SetPosition
+// (constant-velocity-helper.cc:43-49), and GetPosition + GetVelocity (:51-60, DoGetPosition's Update first).
+enum MobOp : uint32_t { MOB_INSTALL, MOB_REMOVE, MOB_SET_VELOCITY, MOB_PAUSE, MOB_SET_POSITION, MOB_GET };
+__global__ void k_wl_mob(const WDev D, uint32_t op, uint32_t j, int64_t now, nsgpu_mobility a, nsgpu_mobility *out) {
+  WMob &m = D.mob[j];
+  double *const x = const_cast<double *>(D.x), *const y = const_cast<double *>(D.y), *const z = const_cast<double *>(D.z);
+  switch (op) {
+    case MOB_INSTALL:
+      x[j] = a.pos[0], y[j] = a.pos[1], z[j] = a.pos[2];
+      m = WMob{a.vel[0], a.vel[1], a.vel[2], a.last_update, MOB_ON | (a.paused ? MOB_PAUSED : 0u), 0};
+      break;
+    case MOB_REMOVE:
+      m = WMob{};
+      break;
+    case MOB_SET_VELOCITY:  // m_helper.Update (); m_helper.SetVelocity (speed); m_helper.Unpause ()
+      mob_update(D, j, now);
+      m.vx = a.vel[0], m.vy = a.vel[1], m.vz = a.vel[2];
+      m.last = now;
+      m.flags &= ~MOB_PAUSED;
+      break;
+    case MOB_PAUSE:
+      mob_update(D, j, now);
+      m.flags = a.paused ? m.flags | MOB_PAUSED : m.flags & ~MOB_PAUSED;
+      break;
+    case MOB_SET_POSITION:  // m_position = position; m_velocity = Vector (0, 0, 0); m_lastUpdate = Now ()
+      x[j] = a.pos[0], y[j] = a.pos[1], z[j] = a.pos[2];
+      m.vx = m.vy = m.vz = 0.0;
+      m.last = now;
+      break;
+    default: {  // MOB_GET
+      mob_update(D, j, now);
+      const bool p = (m.flags & MOB_PAUSED) != 0;
+      *out = nsgpu_mobility{{x[j], y[j], z[j]}, {p ? 0.0 : m.vx, p ? 0.0 : m.vy, p ? 0.0 : m.vz}, m.last, p ? 1u : 0u, 0};
+    }
+  }
+}
+
 // Pending device events and the smallest ts among them (Next / IsFinished).
 __global__ __launch_bounds__(256) void k_wl_pending(const WDev D, unsigned long long *out) {
   const int64_t j = D.j0 + (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -1483,6 +1559,11 @@ struct nsgpu_wifil {
   uint64_t n_note_on = 0;
   uint32_t *d_note_on = nullptr;
   std::vector<nsgpu_wifil_note> notes, notes_epoch;
+  // constant-velocity mobility: the phys with a model (a flag each; their count decides whether a send launches
+  // k_wl_move), and the device word nsgpu_wifil_get_mobility reads back
+  std::vector<uint8_t> mob_on;
+  uint64_t n_mob = 0;
+  nsgpu_mobility *d_mobout = nullptr;
   // ---- a partitioned PHY (nsgpu_wifil_create_dist / nsgpu_wifil_create_group): this handle is the host side
   // every rank replicates (the MAC's closures, the uids, GetState, the ends); `mem` are the partitions it runs —
   // one (RCCL: `comm`, the others on other GPUs) or all of them (a loopback group on this device) — each an engine
@@ -1787,6 +1868,15 @@ static int wl_queue_send(nsgpu_wifil *h, const LTx &t, double dbm, uint32_t uid_
     int rcf = wl_flush_sends(h);
     if (rcf) return rcf;
   }
+  if (h->n_mob) {
+    // Mobility and the batch: a flushed send's receptions are re-derived by k_wl_send from the positions held at
+    // the flush, so the batch is flushed before anything that can change a position — this send's updates here,
+    // and every nsgpu_wifil_set_mobility / _set_velocity / _pause / _set_position_at / _get_mobility (as
+    // nsgpu_wifil_set_position always did).  Each send is then applied from the positions of its own send.
+    if (int rcf = wl_flush_sends(h)) return rcf;
+    hipLaunchKernelGGL(k_wl_move, dim3(wl_grid(h->D.nphy, 256)), dim3(256), 0, h->s, h->D, t.phy, (int64_t)t.ts,
+                       h->recv[t.phy] ? 1u : 0u);
+  }
   const uint32_t k = (uint32_t)h->n_tx++;
   if (h->sb.n == 0) h->sb.k0 = k;
   hipLaunchKernelGGL(k_wl_rx, dim3(wl_grid(h->D.nown, 256)), dim3(256), 0, h->s, h->D,
@@ -1943,12 +2033,17 @@ extern "C" int nsgpu_wifil_flush(nsgpu_wifil *h, uint64_t *digest) {
   return NSGPU_OK;
 }
 
+static bool wl_mobile(const nsgpu_wifil *h, uint32_t phy) { return phy < h->mob_on.size() && h->mob_on[phy]; }
+
 // MobilityModel::SetPosition of `phy`'s node (mobility-model.cc SetPosition -> DoSetPosition; e.g. a host closure
 // at run time): YansWifiChannel::Send reads the positions at each send (yans-wifi-channel.cc:92-96), so the
 // later sends' fan-outs see it; receptions already scheduled keep their delay and power.  In stream order with
 // the sends.
 extern "C" int nsgpu_wifil_set_position(nsgpu_wifil *h, uint32_t phy, double x, double y, double z) {
   if (!h || phy >= h->D.nphy) return set_error(NSGPU_EINVAL, "nsgpu_wifil_set_position: bad phy");
+  if (wl_mobile(h, phy))
+    return set_error(NSGPU_ESTATE, "nsgpu_wifil_set_position: phy %u has a constant-velocity model, whose SetPosition "
+                                   "sets m_lastUpdate: use nsgpu_wifil_set_position_at", phy);
   if (!h->mem.empty()) {  // (every partition holds every position)
     for (nsgpu_wifil *m : h->mem)
       if (int rcm = nsgpu_wifil_set_position(m, phy, x, y, z)) return rcm;
@@ -1960,6 +2055,70 @@ extern "C" int nsgpu_wifil_set_position(nsgpu_wifil *h, uint32_t phy, double x, 
   for (int c = 0; c < 3; c++)
     NSGPU_HIP(hipMemcpyAsync(dst[c] + phy, &v[c], sizeof(double), hipMemcpyHostToDevice, h->s));
   NSGPU_HIP(hipStreamSynchronize(h->s));  // (v is on this stack)
+  return NSGPU_OK;
+}
+
+// One k_wl_mob call on phy's model (the batch first: see wl_queue_send).
+static int wl_mob_op(nsgpu_wifil *h, uint32_t op, uint32_t phy, uint64_t now, const nsgpu_mobility &a) {
+  if (int rcf = wl_flush_sends(h)) return rcf;
+  hipLaunchKernelGGL(k_wl_mob, dim3(1), dim3(1), 0, h->s, h->D, op, phy, (int64_t)now, a, h->d_mobout);
+  NSGPU_HIP(hipGetLastError());
+  return NSGPU_OK;
+}
+
+// Installs ConstantVelocityHelper state on `phy` (m == NULL: removes it; the phy stays where it is, a constant
+// position again).  The records are sized at the first install, as nsgpu_wifil_notify sizes its flags.
+extern "C" int nsgpu_wifil_set_mobility(nsgpu_wifil *h, uint32_t phy, const nsgpu_mobility *m) {
+  if (!h || phy >= h->D.nphy) return set_error(NSGPU_EINVAL, "nsgpu_wifil_set_mobility: bad phy");  // (before anything is sized)
+  if (!h->mem.empty())
+    return set_error(NSGPU_EINVAL, "nsgpu_wifil_set_mobility: mobility is single-engine for now (a partitioned handle)");
+  if (h->mob_on.empty()) {
+    if (!m) return NSGPU_OK;
+    int rc = wl_alloc(h, &h->D.mob, (size_t)h->D.nphy);
+    if (!rc) rc = wl_alloc(h, &h->d_mobout, 1);
+    if (rc) return rc;
+    h->mob_on.assign((size_t)h->D.nphy, 0);
+  }
+  const uint8_t v = m ? 1 : 0;
+  if (!v && !h->mob_on[phy]) return NSGPU_OK;
+  if (int rc = wl_mob_op(h, v ? MOB_INSTALL : MOB_REMOVE, phy, 0, m ? *m : nsgpu_mobility{})) return rc;
+  if (h->mob_on[phy] != v) {
+    h->mob_on[phy] = v;
+    h->n_mob += v ? 1 : (uint64_t)-1;
+  }
+  return NSGPU_OK;
+}
+
+extern "C" int nsgpu_wifil_set_velocity(nsgpu_wifil *h, uint64_t now, uint32_t phy, const double v[3]) {
+  if (!h || !v || phy >= h->D.nphy) return set_error(NSGPU_EINVAL, "nsgpu_wifil_set_velocity: bad phy");
+  if (!wl_mobile(h, phy)) return set_error(NSGPU_ESTATE, "nsgpu_wifil_set_velocity: phy %u has no mobility model", phy);
+  nsgpu_mobility a{};
+  a.vel[0] = v[0], a.vel[1] = v[1], a.vel[2] = v[2];
+  return wl_mob_op(h, MOB_SET_VELOCITY, phy, now, a);
+}
+
+extern "C" int nsgpu_wifil_pause(nsgpu_wifil *h, uint64_t now, uint32_t phy, uint32_t paused) {
+  if (!h || phy >= h->D.nphy) return set_error(NSGPU_EINVAL, "nsgpu_wifil_pause: bad phy");
+  if (!wl_mobile(h, phy)) return set_error(NSGPU_ESTATE, "nsgpu_wifil_pause: phy %u has no mobility model", phy);
+  nsgpu_mobility a{};
+  a.paused = paused;
+  return wl_mob_op(h, MOB_PAUSE, phy, now, a);
+}
+
+extern "C" int nsgpu_wifil_set_position_at(nsgpu_wifil *h, uint64_t now, uint32_t phy, double x, double y, double z) {
+  if (!h || phy >= h->D.nphy) return set_error(NSGPU_EINVAL, "nsgpu_wifil_set_position_at: bad phy");
+  if (!wl_mobile(h, phy)) return nsgpu_wifil_set_position(h, phy, x, y, z);  // (ConstantPositionMobilityModel: no time)
+  nsgpu_mobility a{};
+  a.pos[0] = x, a.pos[1] = y, a.pos[2] = z;
+  return wl_mob_op(h, MOB_SET_POSITION, phy, now, a);
+}
+
+extern "C" int nsgpu_wifil_get_mobility(nsgpu_wifil *h, uint64_t now, uint32_t phy, nsgpu_mobility *out) {
+  if (!h || !out || phy >= h->D.nphy) return set_error(NSGPU_EINVAL, "nsgpu_wifil_get_mobility: bad phy");
+  if (!wl_mobile(h, phy)) return set_error(NSGPU_ESTATE, "nsgpu_wifil_get_mobility: phy %u has no mobility model", phy);
+  if (int rc = wl_mob_op(h, MOB_GET, phy, now, nsgpu_mobility{})) return rc;
+  NSGPU_HIP(hipMemcpyAsync(out, h->d_mobout, sizeof(nsgpu_mobility), hipMemcpyDeviceToHost, h->s));
+  NSGPU_HIP(hipStreamSynchronize(h->s));
   return NSGPU_OK;
 }
 

@@ -15,6 +15,8 @@
 #include "ns3/log.h"
 #include "ns3/simulator.h"
 #include "ns3/mobility-model.h"
+#include "ns3/constant-position-mobility-model.h"
+#include "ns3/constant-velocity-mobility-model.h"
 #include "ns3/wifi-net-device.h"
 #include "ns3/node.h"
 #include "ns3/nist-error-rate-model.h"
@@ -22,6 +24,7 @@
 #include "ns3/uinteger.h"
 #include "ns3/pointer.h"
 #include <cmath>
+#include <sstream>
 
 NS_LOG_COMPONENT_DEFINE ("HipYansWifiPhy");
 
@@ -375,6 +378,31 @@ HipWifiBinding::NoteHandBack (void *user, const nsgpu_wifil_note *note)
   b->m_phys[note->phy]->OnNote (*note, b->m_tx[note->tx].packet);
 }
 
+// ConstantVelocityMobilityModel's CourseChange (SetVelocity and SetPosition both fire it, mobility-model.cc:100-104)
+// of phy `context`: a non-zero velocity can only come from SetVelocity (SetPosition zeroes it,
+// constant-velocity-helper.cc:43-49) and is forwarded at Now (); a zero velocity is forwarded as SetPosition of the
+// host object's position (the trace does not tell SetVelocity (0) from SetPosition: a stop takes the host's
+// integration).
+void
+HipWifiBinding::CourseChange (std::string context, Ptr<const MobilityModel> mobility)
+{
+  std::istringstream is (context);
+  uint32_t index = 0;
+  is >> index;
+  NS_ASSERT (index < m_phys.size ());
+  const Vector v = mobility->GetVelocity ();
+  if (v.x != 0.0 || v.y != 0.0 || v.z != 0.0)
+    {
+      const double vel[3] = { v.x, v.y, v.z };
+      NSGPU_RT (nsgpu_sim_wifi_set_velocity (m_rt, index, vel));
+    }
+  else
+    {
+      const Vector p = mobility->GetPosition ();
+      NSGPU_RT (nsgpu_sim_wifi_set_position (m_rt, index, p.x, p.y, p.z));  // (a phy with a model: set_position_at)
+    }
+}
+
 void
 HipWifiBinding::Attach (Ptr<HipSimulatorImpl> impl, Ptr<YansWifiChannel> channel, const nsgpu_loss_chain &loss,
                         double speed, uint64_t txCap)
@@ -383,6 +411,7 @@ HipWifiBinding::Attach (Ptr<HipSimulatorImpl> impl, Ptr<YansWifiChannel> channel
   const uint32_t n = channel->GetNDevices ();
   std::vector<double> x (n), y (n), z (n);
   std::vector<uint32_t> chan (n), node (n);
+  std::vector<Ptr<MobilityModel> > moving (n);  // (the phys whose node aggregates a ConstantVelocityMobilityModel)
   Ptr<HipYansWifiPhy> first;
   for (uint32_t i = 0; i < n; i++)  // (YansWifiChannel::m_phyList order = GetDevice (i)'s)
     {
@@ -393,6 +422,15 @@ HipWifiBinding::Attach (Ptr<HipSimulatorImpl> impl, Ptr<YansWifiChannel> channel
           NS_FATAL_ERROR ("HipWifiBinding: phy " << i << " of the channel is not a HipYansWifiPhy (HipYansWifiPhyHelper)");
         }
       Ptr<MobilityModel> mob = phy->GetMobility ()->GetObject<MobilityModel> ();
+      if (DynamicCast<ConstantVelocityMobilityModel> (mob) != 0)
+        {
+          moving[i] = mob;
+        }
+      else if (DynamicCast<ConstantPositionMobilityModel> (mob) == 0)
+        {
+          NS_FATAL_ERROR ("HipWifiBinding: phy " << i << "'s mobility model " << mob->GetInstanceTypeId ()
+                          << " is not on the device (ConstantPosition and ConstantVelocity are)");
+        }
       const Vector p = mob->GetPosition ();
       x[i] = p.x;
       y[i] = p.y;
@@ -455,6 +493,22 @@ HipWifiBinding::Attach (Ptr<HipSimulatorImpl> impl, Ptr<YansWifiChannel> channel
       m_phys[i]->Bind (this, m_rt, i);
       NSGPU_RT (nsgpu_sim_wifi_listen (m_rt, i, 1));  // (every phy's EndReceive runs its MAC callbacks)
       NSGPU_RT (nsgpu_sim_wifi_notify (m_rt, i, 1));  // (and its StartReceivePackets drive its state helper)
+      if (moving[i] != 0)
+        {
+          // the helper's state as the model shows it: GetPosition above was an Update at Now (), GetVelocity is
+          // zero while paused — a paused model and a zero velocity integrate alike
+          const Vector v = moving[i]->GetVelocity ();
+          nsgpu_mobility m;
+          m.pos[0] = x[i], m.pos[1] = y[i], m.pos[2] = z[i];
+          m.vel[0] = v.x, m.vel[1] = v.y, m.vel[2] = v.z;
+          m.last_update = Simulator::Now ().GetNanoSeconds ();
+          m.paused = 0;
+          m.pad_ = 0;
+          NSGPU_RT (nsgpu_sim_wifi_set_mobility (m_rt, i, &m));
+          std::ostringstream os;
+          os << i;
+          moving[i]->TraceConnect ("CourseChange", os.str (), MakeCallback (&HipWifiBinding::CourseChange, this));
+        }
     }
 }
 

@@ -35,8 +35,10 @@
 #include "ns3/random-variable.h"
 #include "ns3/object-factory.h"
 #include "ns3/packet.h"
+#include "ns3/mobility-model.h"
 #include "hip-simulator-impl.h"
 #include "nsgpu.h"
+#include <string>
 #include <vector>
 
 namespace ns3 {
@@ -112,7 +114,9 @@ public:
   ~HipWifiBinding ();
 
   /* After the topology is built, before Run: the channel's phys (every one a HipYansWifiPhy) on the device,
-   * attached to impl's runtime.  YansWifiChannel keeps its loss / delay models private: the chain and the
+   * attached to impl's runtime.  A phy whose node aggregates a ConstantVelocityMobilityModel gets a device copy of
+   * it (nsgpu_sim_wifi_set_mobility) kept current through its CourseChange trace; a model other than
+   * ConstantPosition / ConstantVelocity is an NS_FATAL_ERROR.  YansWifiChannel keeps its loss / delay models private: the chain and the
    * ConstantSpeed speed are passed (DefaultLoss () is YansWifiChannelHelper::Default's, yans-wifi-helper.cc:134-140). */
   void Attach (Ptr<HipSimulatorImpl> impl, Ptr<YansWifiChannel> channel, const nsgpu_loss_chain &loss,
                double speed = 299792458.0, uint64_t txCap = 1u << 20);
@@ -126,6 +130,8 @@ private:
   virtual void DoDispose (void);
   static void EndHandBack (void *user, const nsgpu_wifil_end *end);
   static void NoteHandBack (void *user, const nsgpu_wifil_note *note);
+  /* a ConstantVelocityMobilityModel's course change (SetVelocity / SetPosition), forwarded to the device copy */
+  void CourseChange (std::string context, Ptr<const MobilityModel> mobility);
 
   struct Tx
   {

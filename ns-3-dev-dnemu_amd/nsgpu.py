@@ -181,6 +181,15 @@ SIGNATURES = {
     "nsgpu_wifil_read_notes": (C.c_int, [_vp, _vp, _u64, _vp]),
     "nsgpu_sim_wifi_set_note_handler": (C.c_int, [_vp, _vp, _vp]),
     "nsgpu_sim_wifi_notify": (C.c_int, [_vp, _u32, C.c_int]),
+    "nsgpu_wifil_set_mobility": (C.c_int, [_vp, _u32, _vp]),
+    "nsgpu_wifil_set_velocity": (C.c_int, [_vp, _u64, _u32, _vp]),
+    "nsgpu_wifil_pause": (C.c_int, [_vp, _u64, _u32, _u32]),
+    "nsgpu_wifil_set_position_at": (C.c_int, [_vp, _u64, _u32, _d, _d, _d]),
+    "nsgpu_wifil_get_mobility": (C.c_int, [_vp, _u64, _u32, _vp]),
+    "nsgpu_sim_wifi_set_mobility": (C.c_int, [_vp, _u32, _vp]),
+    "nsgpu_sim_wifi_set_velocity": (C.c_int, [_vp, _u32, _vp]),
+    "nsgpu_sim_wifi_pause": (C.c_int, [_vp, _u32, _u32]),
+    "nsgpu_sim_wifi_get_mobility": (C.c_int, [_vp, _u32, _vp]),
     "nsgpu_p2p_group_create": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_void_p)]),
     "nsgpu_p2p_group_reset": (C.c_int, [_vp, _vp]),
     "nsgpu_p2p_group_run": (C.c_int, [_vp, _vp]),
@@ -758,6 +767,23 @@ class Sim:
     def wifi_set_position(self, phy, x, y, z):
         """MobilityModel::SetPosition of `phy`'s node from the running closure."""
         check(lib().nsgpu_sim_wifi_set_position(self.h, phy, x, y, z))
+
+    def wifi_set_velocity(self, phy, vel):
+        """ConstantVelocityMobilityModel::SetVelocity of `phy`'s node now (Update, SetVelocity, Unpause); the phy
+        has a model (wifi.LoopPhy.set_mobility)."""
+        check(lib().nsgpu_sim_wifi_set_velocity(self.h, phy, (C.c_double * 3)(*vel)))
+
+    def wifi_pause(self, phy, paused=True):
+        """ConstantVelocityHelper::Update, then Pause (or Unpause) of `phy`'s model now."""
+        check(lib().nsgpu_sim_wifi_pause(self.h, phy, 1 if paused else 0))
+
+    def wifi_get_mobility(self, phy):
+        """MobilityModel::GetPosition / GetVelocity of `phy`'s node now — an accumulation point of its model, as in
+        ns-3: (position, velocity, paused), Python floats."""
+        import wifi
+        m = wifi.Mobility()
+        check(lib().nsgpu_sim_wifi_get_mobility(self.h, phy, C.byref(m)))
+        return tuple(m.pos), tuple(m.vel), bool(m.paused)
 
     def wifi_send(self, phy, size, dbm, mode, preamble):
         """YansWifiPhy::SendPacket of `phy` now (mode = (modclass, rate, bandwidth))."""

@@ -346,6 +346,11 @@ class WifilPhyState(C.Structure):
                 ("end_cca_busy", C.c_int64), ("delay_until_idle", C.c_int64)]
 
 
+class Mobility(C.Structure):  # nsgpu_mobility (include/nsgpu_types.h)
+    _fields_ = [("pos", C.c_double * 3), ("vel", C.c_double * 3), ("last_update", C.c_int64),
+                ("paused", C.c_uint32), ("pad_", C.c_uint32)]
+
+
 class LoopPhys:
     """The phys of a closed-loop run (nsgpu_wifil_config): positions, channels, nodes and the PHY /
     channel attributes (defaults as Scenario above; RxNoiseFigure 7 dB, NistErrorRateModel as
@@ -431,6 +436,21 @@ class LoopPhy:
     def notify(self, phy, on=True):
         """One nsgpu_wifil_note per StartReceivePacket of `phy` from the next advance on (or none: on=False)."""
         nsgpu.check(nsgpu.lib().nsgpu_wifil_notify(self.h, phy, 1 if on else 0))
+
+    def set_mobility(self, phy, pos, vel, paused=False, last_update=0):
+        """A constant-velocity model on `phy` (nsgpu_wifil_set_mobility: ConstantVelocityHelper's position, velocity,
+        m_paused and m_lastUpdate in ns); pos None: back to a constant position."""
+        if pos is None:
+            nsgpu.check(nsgpu.lib().nsgpu_wifil_set_mobility(self.h, phy, None))
+            return
+        m = Mobility((C.c_double * 3)(*pos), (C.c_double * 3)(*vel), int(last_update), 1 if paused else 0, 0)
+        nsgpu.check(nsgpu.lib().nsgpu_wifil_set_mobility(self.h, phy, C.byref(m)))
+
+    def get_mobility(self, now, phy):
+        """nsgpu_wifil_get_mobility at `now` ns (an accumulation point): (position, velocity, paused)."""
+        m = Mobility()
+        nsgpu.check(nsgpu.lib().nsgpu_wifil_get_mobility(self.h, int(now), phy, C.byref(m)))
+        return tuple(m.pos), tuple(m.vel), bool(m.paused)
 
     def read_notes(self):
         """The notes of the epochs advanced since the last call (WIFIL_NOTE_DTYPE, (ts, uid) order)."""
