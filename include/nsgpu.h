@@ -237,6 +237,38 @@ int nsgpu_wifil_set_velocity(nsgpu_wifil *h, uint64_t now, uint32_t phy, const d
 int nsgpu_wifil_pause(nsgpu_wifil *h, uint64_t now, uint32_t phy, uint32_t paused);
 int nsgpu_wifil_set_position_at(nsgpu_wifil *h, uint64_t now, uint32_t phy, double x, double y, double z);
 int nsgpu_wifil_get_mobility(nsgpu_wifil *h, uint64_t now, uint32_t phy, nsgpu_mobility *out);
+/* Channel switching on the device: YansWifiPhy::SetChannelNumber (nch) of phy from the host closure running at `now`
+ * (yans-wifi-phy.cc:327-374), in stream order with the sends and after every earlier send of the closure.
+ * switch_delay_ns is the ChannelSwitchDelay attribute (an argument: nsgpu_wifil_config is the oracle's too).  The
+ * outcome follows from the phy's state at `now` (out->prev_state):
+ *   now == 0         NSGPU_WIFIL_SWITCH_INIT: "this is initialization" (:330-336) — the channel number alone;
+ *   TX               NSGPU_WIFIL_SWITCH_POSTPONED: nothing changes; ns-3 schedules the retry (:349-352), an event with a
+ *                    uid, so the caller (nsgpu.Sim, the ns-3 binding: the owners of closures and of the uid counter)
+ *                    schedules it after out->retry_delay = m_endTx - now;
+ *   RX               the pending EndReceive is cancelled (:343-347; it is still dispatched, as after a SendPacket
+ *                    while RX), then the switch;
+ *   CCA_BUSY, IDLE   NSGPU_WIFIL_SWITCH_DONE, the switch: WifiPhyStateHelper::SwitchToChannelSwitching
+ *                    (wifi-phy-state-helper.cc:323-365: m_rxing = false and m_endRx = now from RX, m_endCcaBusy trimmed
+ *                    to now, m_endSwitching = now + delay), InterferenceHelper::EraseEvents (interference-helper.cc:
+ *                    368-374), m_channelNumber = nch.
+ * Until m_endSwitching GetState is NSGPU_WIFIL_SWITCHING (after TX and RX, before CCA_BUSY; nsgpu_wifil_get_state
+ * reports it with delay_until_idle = m_endSwitching - now).  A Receive dispatched then still enters the interference
+ * list, is dropped (nsgpu_wifil_channel.drop_switching; note kind NSGPU_WIFIL_NOTE_DROP_SWITCHING with state
+ * NSGPU_WIFIL_SWITCHING) and raises m_endCcaBusy when it outlasts the switch (:419-436).  A SendPacket then is ns-3's
+ * NS_ASSERT (:508): a sticky error, the next advance fails with NSGPU_ESTATE.  The channel test is YansWifiChannel::
+ * Send's (yans-wifi-channel.cc:84-113), made at send time: Receives already scheduled for a phy that switches away are
+ * still delivered to it, frames it sent before switching still arrive on its old channel, and from the switch on the
+ * receiver loops of the old and the new channel — the order that gives each Receive its uid — have lost / gained the
+ * phy (nsgpu_wifil_receivers follows).  nsgpu_wifil_send_plan stays a function of the config it is given: after a
+ * switch the caller passes the current channel numbers.  A run that never calls this launches the kernels it
+ * launched without it.
+ * phy >= n_phy or a negative delay: NSGPU_EINVAL; a call while the phy is SWITCHING (ns-3: NS_ASSERT, :338) or on a
+ * partitioned handle (create_dist / create_group: channel switching is single-engine for now): NSGPU_ESTATE — all
+ * before anything is touched.  nsgpu_wifil_get_channel: the phy's channel number, m_startSwitching / m_endSwitching
+ * and switching counters (one device trip). */
+int nsgpu_wifil_set_channel(nsgpu_wifil *h, uint64_t now, uint32_t phy, uint32_t nch, int64_t switch_delay_ns,
+                            nsgpu_wifil_switch *out);
+int nsgpu_wifil_get_channel(nsgpu_wifil *h, uint32_t phy, nsgpu_wifil_channel *out);
 int nsgpu_wifil_read_ends(nsgpu_wifil *h, nsgpu_wifil_end *out, uint64_t cap, uint64_t *n);  /* since last read */
 int nsgpu_wifil_read_phys(nsgpu_wifil *h, nsgpu_wifi_phy_counters *out);                    /* n_phy */
 int nsgpu_wifil_pending(nsgpu_wifil *h, uint64_t *n, uint64_t *next_ts);
@@ -253,7 +285,8 @@ typedef struct nsgpu_wifil_next {
 int nsgpu_wifil_listen(nsgpu_wifil *h, uint32_t phy, int on);
 /* YansWifiChannel::Send's ScheduleWithContext calls for one SendPacket of `sender` (yans-wifi-channel.cc:77-115),
  * host only: the receivers (every other phy on the sender's channel number, in m_phyList order), their Receive uids
- * (uid_base + place) and contexts (their device's node); *n = the count (entries past cap are not written). */
+ * (uid_base + place) and contexts (their device's node); *n = the count (entries past cap are not written).  A pure
+ * function of the config it is given: after a nsgpu_wifil_set_channel the caller passes the current channel numbers. */
 int nsgpu_wifil_send_plan(const nsgpu_wifil_config *cfg, uint32_t sender, uint32_t uid_base, uint32_t *rx_phy,
                           uint32_t *rx_uid, uint32_t *rx_ctx, uint64_t cap, uint64_t *n);
 int nsgpu_wifil_next_end(nsgpu_wifil *h, nsgpu_wifil_next *out);
@@ -421,6 +454,12 @@ int nsgpu_sim_wifi_set_mobility(nsgpu_sim *s, uint32_t phy, const nsgpu_mobility
 int nsgpu_sim_wifi_set_velocity(nsgpu_sim *s, uint32_t phy, const double v[3]);
 int nsgpu_sim_wifi_pause(nsgpu_sim *s, uint32_t phy, uint32_t paused);
 int nsgpu_sim_wifi_get_mobility(nsgpu_sim *s, uint32_t phy, nsgpu_mobility *out);
+/* YansWifiPhy::SetChannelNumber of the attached PHY's phy from the running closure (nsgpu_wifil_set_channel at
+ * Now ()).  NSGPU_WIFIL_SWITCH_POSTPONED: the caller schedules its retry closure after out->retry_delay, as ns-3's
+ * Simulator::Schedule (GetDelayUntilIdle (), &SetChannelNumber, this, nch) — the closure and its uid are the
+ * caller's (nsgpu.Sim.wifi_set_channel does).  nsgpu_sim_wifi_get_channel: nsgpu_wifil_get_channel. */
+int nsgpu_sim_wifi_set_channel(nsgpu_sim *s, uint32_t phy, uint32_t nch, int64_t switch_delay_ns, nsgpu_wifil_switch *out);
+int nsgpu_sim_wifi_get_channel(nsgpu_sim *s, uint32_t phy, nsgpu_wifil_channel *out);
 /* EndReceive hand-back (YansWifiPhy::EndReceive, yans-wifi-phy.cc:770-799): for every phy marked with
  * nsgpu_sim_wifi_listen, the runtime stops the device AT each of the phy's EndReceives (the event itself runs on
  * the device: CalculateSnrPer, the state switch) and calls fn (user, &end) right there in the (ts, uid) order,

@@ -263,7 +263,8 @@ NSGPU_HD static inline uint64_t nsgpu_dispatch_digest_term(uint64_t rank, uint64
  * and SendPacket's (:499-522).  The scenario is a PHY harness in the style of wifi-test.cc:181-260:
  * every transmission is a SendPacket call scheduled before Run (its uid is a setup uid), so the
  * transmission schedule is an input; the MAC, its DCF and EndReceive's m_random draw stay on the host
- * (SURVEY H13).  Channel switching is not modelled (no SWITCHING state). */
+ * (SURVEY H13).  Channel switching — open-loop engine (nsgpu_wifi_*, this fixed schedule): no SWITCHING state;
+ * closed-loop engine (nsgpu_wifil_*): nsgpu_wifil_set_channel. */
 enum nsgpu_wifi_modclass { NSGPU_WIFI_DSSS = 0, NSGPU_WIFI_OFDM = 1, NSGPU_WIFI_ERP_OFDM = 2 };
 enum nsgpu_wifi_store { NSGPU_WIFI_STORE_AUTO = 0, NSGPU_WIFI_STORE_LDS = 1, NSGPU_WIFI_STORE_HBM = 2,
                         NSGPU_WIFI_STORE_MASK = 3, NSGPU_WIFI_INLINE_RX = 4, NSGPU_WIFI_UNSORTED_RX = 8 };
@@ -389,18 +390,34 @@ typedef struct nsgpu_wifil_end {
 } nsgpu_wifil_end;
 
 /* WifiPhyStateHelper of one phy at Now (wifi-phy-state-helper.cc:159-183). */
-enum nsgpu_wifil_state { NSGPU_WIFIL_IDLE = 0, NSGPU_WIFIL_RX = 1, NSGPU_WIFIL_TX = 2, NSGPU_WIFIL_CCA_BUSY = 3 };
+enum nsgpu_wifil_state { NSGPU_WIFIL_IDLE = 0, NSGPU_WIFIL_RX = 1, NSGPU_WIFIL_TX = 2, NSGPU_WIFIL_CCA_BUSY = 3,
+                         NSGPU_WIFIL_SWITCHING = 4 };  /* (after nsgpu_wifil_set_channel, until m_endSwitching) */
 typedef struct nsgpu_wifil_phy_state {
   uint32_t state;  /* nsgpu_wifil_state */
   uint32_t rxing;
   int64_t end_tx, end_rx, end_cca_busy;
-  int64_t delay_until_idle;  /* GetDelayUntilIdle (:122-151) */
+  int64_t delay_until_idle;  /* GetDelayUntilIdle (:122-151); SWITCHING: m_endSwitching - now */
 } nsgpu_wifil_phy_state;
+
+/* YansWifiPhy::SetChannelNumber from a host closure (nsgpu_wifil_set_channel; yans-wifi-phy.cc:327-374). */
+enum { NSGPU_WIFIL_SWITCH_DONE = 0,        /* the phy switched: SWITCHING until now + ChannelSwitchDelay */
+       NSGPU_WIFIL_SWITCH_INIT = 1,        /* Now == 0: the channel number alone, no state change (:330-336) */
+       NSGPU_WIFIL_SWITCH_POSTPONED = 2 }; /* the phy transmits: nothing changed; retry after retry_delay (:349-352) */
+typedef struct nsgpu_wifil_switch {
+  uint32_t outcome, prev_state;  /* NSGPU_WIFIL_SWITCH_*; nsgpu_wifil_state GetState () returned at :339 */
+  int64_t retry_delay;           /* POSTPONED: GetDelayUntilIdle () = m_endTx - now, else 0 */
+} nsgpu_wifil_switch;
+typedef struct nsgpu_wifil_channel {
+  uint32_t channel, pad_;                   /* GetChannelNumber () */
+  int64_t start_switching, end_switching;   /* WifiPhyStateHelper m_startSwitching / m_endSwitching (0: never switched) */
+  uint64_t switches, drop_switching;        /* switches made; frames dropped while SWITCHING (:419-436) */
+} nsgpu_wifil_channel;
 
 /* One StartReceivePacket of a notifying phy (nsgpu_wifil_notify): which branch of yans-wifi-phy.cc:417-495 it
  * took, with the arguments of the state helper's switches — what DcfManager::NotifyRxStartNow /
  * NotifyMaybeCcaBusyStartNow (dcf-manager.cc:591-641) and the State / RxOk traces are fed from. */
-enum { NSGPU_WIFIL_NOTE_SYNC = 0, NSGPU_WIFIL_NOTE_DROP_RX = 1, NSGPU_WIFIL_NOTE_DROP_TX = 2, NSGPU_WIFIL_NOTE_DROP_ED = 3 };
+enum { NSGPU_WIFIL_NOTE_SYNC = 0, NSGPU_WIFIL_NOTE_DROP_RX = 1, NSGPU_WIFIL_NOTE_DROP_TX = 2, NSGPU_WIFIL_NOTE_DROP_ED = 3,
+       NSGPU_WIFIL_NOTE_DROP_SWITCHING = 4 };  /* dropped while switching channels (:419-436), state = SWITCHING */
 typedef struct nsgpu_wifil_note {
   uint64_t ts;            /* StartReceivePacket's Now () */
   uint32_t uid, phy;      /* the Receive event's uid; the receiver */

@@ -792,6 +792,17 @@ int nsgpu_sim_wifi_get_mobility(nsgpu_sim *s, uint32_t phy, nsgpu_mobility *out)
   return nsgpu_wifil_get_mobility(s->wifi, s->cur_ts, phy, out);
 }
 
+// YansWifiPhy::SetChannelNumber of `phy` from the running closure (at Now).  A postponed switch (the phy
+// transmits) is reported with its delay: the retry is a closure of the caller's, scheduled by the caller.
+int nsgpu_sim_wifi_set_channel(nsgpu_sim *s, uint32_t phy, uint32_t nch, int64_t switch_delay_ns, nsgpu_wifil_switch *out) {
+  if (!s || !s->wifi) return set_error(NSGPU_ESTATE, "nsgpu_sim_wifi_set_channel: no Wi-Fi PHY attached");
+  return nsgpu_wifil_set_channel(s->wifi, s->cur_ts, phy, nch, switch_delay_ns, out);
+}
+int nsgpu_sim_wifi_get_channel(nsgpu_sim *s, uint32_t phy, nsgpu_wifil_channel *out) {
+  if (!s || !s->wifi) return set_error(NSGPU_ESTATE, "nsgpu_sim_wifi_get_channel: no Wi-Fi PHY attached");
+  return nsgpu_wifil_get_channel(s->wifi, phy, out);
+}
+
 // WifiPhyStateHelper::GetState of `phy` at Now (the device has run every event before the running closure).
 int nsgpu_sim_wifi_state(nsgpu_sim *s, uint32_t phy, nsgpu_wifil_phy_state *out) {
   if (!s || !s->wifi) return set_error(NSGPU_ESTATE, "nsgpu_sim_wifi_state: no Wi-Fi PHY attached");

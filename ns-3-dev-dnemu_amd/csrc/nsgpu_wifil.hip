@@ -25,6 +25,7 @@
 // Receive queue (sorted by (arrival, uid)) and up to LPE_CAP pending EndReceive records.
 #include <algorithm>
 #include <atomic>
+#include <cstddef>
 #include <cstdio>
 #include <cstring>
 #include <vector>
@@ -40,6 +41,7 @@ constexpr uint32_t END_STAGE = 128;  // EndReceive records an epoch returns with
 constexpr size_t STAT_HDR = 32;      // the status block: counters (6 x u32), the epoch flag (word 6), then the ends
 static_assert(sizeof(nsgpu_wifil_end) % 8 == 0 && STAT_HDR % 8 == 0, "status block alignment");
 constexpr uint32_t WE_TX_IN_TX = 1, WE_NICAP = 2, WE_RQCAP = 4, WE_PECAP = 8, WE_CAP = 16, WE_CKCAP = 32, WE_NOTECAP = 64;
+constexpr uint32_t WE_TX_IN_SWITCHING = 128;
 
 struct LNi {  // InterferenceHelper::NiChange (interference-helper.cc:91-110)
   int64_t t;
@@ -69,11 +71,20 @@ struct LPhy {  // a phy's state between epochs
   uint32_t rxing, head, len, cur_n;
   uint32_t rq_head, rq_len, live, ni_max;
   nsgpu_wifi_phy_counters c;
+  // channel switching (nsgpu_wifil_set_channel): WifiPhyStateHelper m_endSwitching / m_startSwitching, the
+  // switches made and the frames dropped while switching (outside c: the oracle shares that struct).  Only
+  // k_wl_switch writes endSw / startSw / switches; an epoch kernel that is not the SW instantiation neither
+  // reads nor stores this tail (LPHY_HEAD)
+  int64_t endSw, startSw;
+  uint32_t switches, drop_switching;
 };
+constexpr size_t LPHY_HEAD = offsetof(LPhy, endSw);
 struct WMir {  // a phy's state helper fields in pinned host memory: GetState reads them with no device trip
   int64_t endTx, endRx, endCca;
   uint32_t rxing, pad;
+  int64_t endSw;  // (written by k_wl_switch and the host's copy of it alone: the epoch kernels store WMIR_HEAD bytes)
 };
+constexpr size_t WMIR_HEAD = offsetof(WMir, endSw);
 struct LEv {  // one dispatched device event of the epoch
   uint64_t ts;
   uint32_t uid, ctx, sslot, pad;
@@ -145,7 +156,7 @@ struct WDev {
   int64_t j0, nown;
   const LSync *xsync;
   uint32_t xn, pad_x;
-  // RxStart / CCA-busy notifications (nsgpu_wifil_notify): a flag per phy, and the epoch's notes (k_wl_stepw<true>,
+  // RxStart / CCA-busy notifications (nsgpu_wifil_notify): a flag per phy, and the epoch's notes (k_wl_stepw<true, *>,
   // launched only while some phy notifies; the host reads them before the next epoch: one array, no parity)
   const uint32_t *note_on;
   nsgpu_wifil_note *notes;
@@ -418,9 +429,12 @@ __device__ __forceinline__ bool pe_before(const LPe &a, const LPe &b) {
   return a.sts != b.sts ? a.sts < b.sts : a.suid < b.suid;
 }
 
-__device__ __forceinline__ WMir mir_of(const LPhy &P) { return WMir{P.endTx, P.endRx, P.endCca, P.rxing, 0}; }
+__device__ __forceinline__ WMir mir_of(const LPhy &P) { return WMir{P.endTx, P.endRx, P.endCca, P.rxing, 0, P.endSw}; }
 __device__ __forceinline__ void mir_put(const WDev &D, int64_t j, const WMir &m0, const LPhy &P) {
-  if (P.endTx != m0.endTx || P.endRx != m0.endRx || P.endCca != m0.endCca || P.rxing != m0.rxing) D.mir[j] = mir_of(P);
+  if (P.endTx != m0.endTx || P.endRx != m0.endRx || P.endCca != m0.endCca || P.rxing != m0.rxing) {
+    const WMir m{P.endTx, P.endRx, P.endCca, P.rxing, 0, 0};
+    __builtin_memcpy(&D.mir[j], &m, WMIR_HEAD);  // (an epoch never changes endSw)
+  }
 }
 
 #ifdef NSGPU_PHASE_PROF
@@ -513,7 +527,7 @@ __device__ __forceinline__ void w_ni_insert(LNi *ring, uint32_t head, uint32_t &
 constexpr uint32_t RL = 256;
 constexpr uint32_t RSPEC = 32, QSPEC = 4;  // ring / queue entries loaded with the state (speculatively)
 constexpr uint32_t EVB = 64, ENB = 8, SYB = 8;
-constexpr uint32_t NTB = 32;  // staged notes (k_wl_stepw<true>; a phy's notes leave the wave in its own order)
+constexpr uint32_t NTB = 32;  // staged notes (k_wl_stepw<true, *>; a phy's notes leave the wave in its own order)
 constexpr uint32_t LOCAL = 0x80000000u;
 struct LEnd {  // a staged end record
   nsgpu_wifil_end rec;
@@ -538,7 +552,10 @@ __device__ __forceinline__ LRx shfl_up_rx(const LRx &a) {
 // k_wl_send does — they precede every event of the epoch), then every pending Receive / EndReceive with a
 // key below (bts, buid), in (ts, uid) order.  NOTE: the instantiation launched while some phy notifies
 // (nsgpu_wifil_notify) — a notifying phy's wave stages one nsgpu_wifil_note per Receive; <false> holds none of it.
-template <bool NOTE>
+// SW: the instantiation launched once some phy has switched channels (nsgpu_wifil_set_channel) — GetState's
+// SWITCHING rank, StartReceivePacket's SWITCHING branch (yans-wifi-phy.cc:419-436) and SendPacket's
+// !IsStateSwitching () (:508); <*, false> holds none of it and leaves the state's switching tail alone.
+template <bool NOTE, bool SW>
 __global__ __launch_bounds__(64) void k_wl_stepw(const WDev D, uint64_t bts, uint32_t buid, const SendBatch sb) {
   const int64_t j = D.j0 + blockIdx.x;
   const uint32_t lane = threadIdx.x;
@@ -555,7 +572,9 @@ __global__ __launch_bounds__(64) void k_wl_stepw(const WDev D, uint64_t bts, uin
   __shared__ nsgpu_wifil_note s_nt[NOTE ? NTB : 1];  // (<false> never names it: no LDS there)
   bool noting = false;
   if constexpr (NOTE) noting = D.note_on[j] != 0;
-  LPhy P = D.ps[j];
+  LPhy P;
+  if constexpr (SW) P = D.ps[j];
+  else __builtin_memcpy(&P, &D.ps[j], LPHY_HEAD), P.endSw = P.startSw = 0, P.switches = P.drop_switching = 0;
   // (issued with the state: the ring's first RSPEC entries and the queue's first QSPEC at their compact places
   // — a fast epoch leaves them there, head 0 — used when the state says they are the ones; the first trip moves
   // ~1 KB a wave, 10^4 waves at once)
@@ -591,6 +610,10 @@ __global__ __launch_bounds__(64) void k_wl_stepw(const WDev D, uint64_t bts, uin
     changed = true;
     if (P.endTx > (int64_t)t.ts) {  // NS_ASSERT (!IsStateTx ()); SwitchToTx from TX: NS_FATAL_ERROR (:285-287)
       err |= WE_TX_IN_TX;
+      continue;
+    }
+    if (SW && P.endSw > (int64_t)t.ts) {  // NS_ASSERT (... && !m_state->IsStateSwitching ()) (:508)
+      err |= WE_TX_IN_SWITCHING;
       continue;
     }
     if (P.rxing) {  // m_endRxEvent.Cancel (); NotifyRxEnd (); SwitchToTx's RX case (:263-268)
@@ -888,13 +911,19 @@ __global__ __launch_bounds__(64) void k_wl_stepw(const WDev D, uint64_t bts, uin
     }
     w_ni_insert(ring, P.head, P.len, m, endNew, -r.w);
     P.ni_max = P.len > P.ni_max ? P.len : P.ni_max;
-    const int st = P.endTx > nw ? 2 : P.rxing ? 1 : P.endCca > nw ? 3 : 0;  // GetState (:159-183)
+    // GetState (wifi-phy-state-helper.cc:159-183): TX, RX, SWITCHING, CCA_BUSY, IDLE
+    const int st = P.endTx > nw ? 2 : P.rxing ? 1 : SW && P.endSw > nw ? 4 : P.endCca > nw ? 3 : 0;
     static_assert(NSGPU_WIFIL_IDLE == 0 && NSGPU_WIFIL_RX == 1 && NSGPU_WIFIL_TX == 2 && NSGPU_WIFIL_CCA_BUSY == 3, "st");
+    static_assert(NSGPU_WIFIL_SWITCHING == 4 && NSGPU_WIFIL_NOTE_DROP_SWITCHING == 4, "st");
     uint32_t nkind = NSGPU_WIFIL_NOTE_DROP_ED;  // (NOTE) the branch taken, and SwitchMaybeToCcaBusy's argument
     int64_t ncca = 0;
     bool maybe = false;
     P.c.rx++;
-    if (st == 1 || st == 2) {  // drop; noise after the current Rx / Tx (:431-457)
+    if (SW && st == 4) {  // drop (:419-436); noise after the switch when it outlasts m_endSwitching
+      P.drop_switching++;
+      nkind = NSGPU_WIFIL_NOTE_DROP_SWITCHING;
+      maybe = endNew > nw + (P.endSw - nw);  // GetDelayUntilIdle: m_endSwitching - now (> 0 here)
+    } else if (st == 1 || st == 2) {  // drop; noise after the current Rx / Tx (:431-457)
       if (st == 1) P.c.drop_rx++;
       else P.c.drop_tx++;
       nkind = st == 1 ? NSGPU_WIFIL_NOTE_DROP_RX : NSGPU_WIFIL_NOTE_DROP_TX;
@@ -979,7 +1008,10 @@ __global__ __launch_bounds__(64) void k_wl_stepw(const WDev D, uint64_t bts, uin
     P.head = 0;
   }
   if (lane == 0) {
-    if (changed) D.ps[j] = P;
+    if (changed) {
+      if constexpr (SW) D.ps[j] = P;
+      else __builtin_memcpy(&D.ps[j], &P, LPHY_HEAD);
+    }
     mir_put(D, j, m0, P);
     if (err) atomicOr(&D.cnt[3], err);
   }
@@ -1330,6 +1362,10 @@ __global__ __launch_bounds__(256) void k_wl_send(const WDev D, uint32_t k, LTx t
       atomicOr(&D.cnt[3], WE_TX_IN_TX);
       return;
     }
+    if (P.endSw > (int64_t)t.ts) {  // NS_ASSERT (... && !m_state->IsStateSwitching ()) (:508)
+      atomicOr(&D.cnt[3], WE_TX_IN_SWITCHING);
+      return;
+    }
     if (P.rxing) {  // m_endRxEvent.Cancel (); NotifyRxEnd (); SwitchToTx's RX case (:263-268)
       D.pe[(uint64_t)j * LPE_CAP + P.live].can = 1;
       P.live = NONE;
@@ -1422,6 +1458,56 @@ __global__ void k_wl_mob(const WDev D, uint32_t op, uint32_t j, int64_t now, nsg
       const bool p = (m.flags & MOB_PAUSED) != 0;
       *out = nsgpu_mobility{{x[j], y[j], z[j]}, {p ? 0.0 : m.vx, p ? 0.0 : m.vy, p ? 0.0 : m.vz}, m.last, p ? 1u : 0u, 0};
     }
+  }
+}
+
+// YansWifiPhy::SetChannelNumber (nch) of phy j (yans-wifi-phy.cc:327-374), in two launches in stream order with the
+// sends (the host has flushed the batch: every earlier send keeps the receivers of its own Now).
+//
+// k_wl_rechan repairs the receiver loop's order (YansWifiChannel::Send, yans-wifi-channel.cc:84-113: m_phyList order
+// among the phys of one channel number) in place, one lane per phy: the phys after j on `old` lose one place, the
+// phys after j on `nch` gain one, and j's new place is the number of `nch` phys before it — counted a wave at a
+// time (ballot + popcount, one atomic per wave that holds any) into *nbefore, which k_wl_switch reads and clears.
+// D.chan[j] still holds `old` here; no lane reads it for j.
+__global__ __launch_bounds__(256) void k_wl_rechan(const WDev D, uint32_t j, uint32_t old, uint32_t nch, uint32_t *nbefore) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const bool in = i < D.nphy && i != (int64_t)j;
+  const uint32_t c = in ? D.chan[i] : 0u;
+  const uint64_t bm = __ballot(in && i < (int64_t)j && c == nch);
+  if ((threadIdx.x & 63) == 0 && bm) atomicAdd(nbefore, (uint32_t)__popcll(bm));
+  if (!in || i < (int64_t)j) return;
+  uint32_t *const rank = const_cast<uint32_t *>(D.chan_rank);
+  if (c == old) rank[i] -= 1;       // (old != nch: the host launches this kernel only then)
+  else if (c == nch) rank[i] += 1;
+}
+// k_wl_switch (one thread, as k_wl_mob): the switch itself when `sw` (Now != 0) — m_endRxEvent.Cancel () in RX
+// (:343-347: the pending EndReceive stays queued, marked cancelled, as SendPacket-while-RX leaves it),
+// WifiPhyStateHelper::SwitchToChannelSwitching (wifi-phy-state-helper.cc:323-365: m_rxing = false, m_endRx = now from
+// RX; m_endCcaBusy trimmed to now; m_startSwitching, m_endSwitching), InterferenceHelper::EraseEvents
+// (interference-helper.cc:368-374: the ring emptied, m_firstPower = 0, m_rxing = false) — then m_channelNumber =
+// nch and, when the number changed (`moved`), j's place on it.  Now == 0 (:330-336) is the assignment alone.
+__global__ void k_wl_switch(const WDev D, uint32_t j, int64_t now, int64_t delay, uint32_t nch, uint32_t sw, uint32_t moved,
+                            uint32_t *nbefore) {
+  if (sw) {
+    LPhy &P = D.ps[j];
+    if (P.rxing) {
+      D.pe[(uint64_t)j * LPE_CAP + P.live].can = 1;
+      P.live = NONE;
+      P.rxing = 0;
+      P.endRx = now;
+    }
+    if (now < P.endCca) P.endCca = now;
+    P.startSw = now;
+    P.endSw = now + delay;
+    P.len = P.cur_n = 0;
+    P.cur_s = P.firstPower = 0.0;
+    P.switches++;
+    D.mir[j] = mir_of(P);  // (the host applied the same switch to its copy)
+  }
+  const_cast<uint32_t *>(D.chan)[j] = nch;
+  if (moved) {
+    const_cast<uint32_t *>(D.chan_rank)[j] = *nbefore;
+    *nbefore = 0;
   }
 }
 
@@ -1564,6 +1650,12 @@ struct nsgpu_wifil {
   std::vector<uint8_t> mob_on;
   uint64_t n_mob = 0;
   nsgpu_mobility *d_mobout = nullptr;
+  // channel switching (nsgpu_wifil_set_channel): every phy's current channel number (the receiver counts in `recv`
+  // follow it), the switches made (non-zero: the epochs launch the SW instantiation) and k_wl_rechan's count word
+  // (allocated at the first call)
+  std::vector<uint32_t> chan_h;
+  uint64_t n_switches = 0;
+  uint32_t *d_nbefore = nullptr;
   // ---- a partitioned PHY (nsgpu_wifil_create_dist / nsgpu_wifil_create_group): this handle is the host side
   // every rank replicates (the MAC's closures, the uids, GetState, the ends); `mem` are the partitions it runs —
   // one (RCCL: `comm`, the others on other GPUs) or all of them (a loopback group on this device) — each an engine
@@ -1746,6 +1838,7 @@ static int wl_create(const nsgpu_wifil_config *c, int64_t j0, int64_t nown, int6
   D.nlis = 0;
   h->lis_on.assign((size_t)N, 0);
   h->node_h.assign(c->node, c->node + N);
+  h->chan_h.assign(c->channel, c->channel + N);
 #undef WL_TRY
   D.sync_cap = sync_cap;
   D.ev_cap = ev_cap;
@@ -1819,6 +1912,8 @@ static int wl_check_bits(uint32_t e, const char *what) {
   if (!e) return NSGPU_OK;
   if (e & WE_TX_IN_TX)
     return set_error(NSGPU_ESTATE, "%s: SendPacket while transmitting (yans-wifi-phy.cc:508 NS_ASSERT)", what);
+  if (e & WE_TX_IN_SWITCHING)
+    return set_error(NSGPU_ESTATE, "%s: SendPacket while switching channels (yans-wifi-phy.cc:508 NS_ASSERT)", what);
   return set_error(NSGPU_ENOMEM, "%s: capacity exceeded (bits %u: 2 NiChanges ring, 4 Receive queue, 8 pending "
                                  "EndReceive records, 16 epoch lists, 32 CalculatePer chunk pool, 64 epoch notes)", what, e);
 }
@@ -1851,7 +1946,7 @@ extern "C" int nsgpu_wifil_send(nsgpu_wifil *h, uint64_t now, uint32_t uid_base,
   if (rc) return rc;
   const LTx t{now, dur, rate, phy, modclass, bw, preamble};
   WMir &mr = h->h_mir[phy];  // the sender's switch (k_wl_send's), in the host's copy of its state fields
-  if (!(mr.endTx > (int64_t)now)) {
+  if (!(mr.endTx > (int64_t)now) && !(mr.endSw > (int64_t)now)) {
     if (mr.rxing) mr.rxing = 0, mr.endRx = (int64_t)now;
     mr.endTx = (int64_t)now + dur;
   }
@@ -1928,8 +2023,13 @@ extern "C" int nsgpu_wifil_advance(nsgpu_wifil *h, uint64_t bound_ts, uint32_t b
   // epoch: the phys' waves, then the tail (PER products + sync ranks + the close), then the order behind it
   // (the notifying instantiation only while some phy notifies: the default path's kernel holds none of it)
   const bool noting = h->n_note_on != 0;
-  if (noting) hipLaunchKernelGGL(k_wl_stepw<true>, dim3(wl_grid(D.nown, 1)), dim3(64), 0, h->s, D, bound_ts, bound_uid, h->sb);
-  else hipLaunchKernelGGL(k_wl_stepw<false>, dim3(wl_grid(D.nown, 1)), dim3(64), 0, h->s, D, bound_ts, bound_uid, h->sb);
+  // (and the switching instantiation only once some phy has switched channels: until then today's kernels)
+  const bool switching = h->n_switches != 0;
+  const dim3 sg(wl_grid(D.nown, 1));
+  if (noting && switching) hipLaunchKernelGGL((k_wl_stepw<true, true>), sg, dim3(64), 0, h->s, D, bound_ts, bound_uid, h->sb);
+  else if (noting) hipLaunchKernelGGL((k_wl_stepw<true, false>), sg, dim3(64), 0, h->s, D, bound_ts, bound_uid, h->sb);
+  else if (switching) hipLaunchKernelGGL((k_wl_stepw<false, true>), sg, dim3(64), 0, h->s, D, bound_ts, bound_uid, h->sb);
+  else hipLaunchKernelGGL((k_wl_stepw<false, false>), sg, dim3(64), 0, h->s, D, bound_ts, bound_uid, h->sb);
   h->sb.n = 0;
 #ifdef NSGPU_PHASE_PROF
   hipLaunchKernelGGL(k_wl_prof_epoch, dim3(1), dim3(1), 0, h->s);
@@ -2122,6 +2222,80 @@ extern "C" int nsgpu_wifil_get_mobility(nsgpu_wifil *h, uint64_t now, uint32_t p
   return NSGPU_OK;
 }
 
+// WifiPhyStateHelper::GetState (wifi-phy-state-helper.cc:159-183) from a phy's mirrored fields.
+static uint32_t wl_state(const WMir &P, int64_t nw) {
+  return P.endTx > nw ? NSGPU_WIFIL_TX : P.rxing ? NSGPU_WIFIL_RX : P.endSw > nw ? NSGPU_WIFIL_SWITCHING
+         : P.endCca > nw ? NSGPU_WIFIL_CCA_BUSY : NSGPU_WIFIL_IDLE;
+}
+
+// YansWifiPhy::SetChannelNumber (nch) of `phy` from the host closure running at `now` (yans-wifi-phy.cc:327-374),
+// after every earlier send of that closure.  The outcome follows from the phy's state at `now`, which the mirror
+// holds (the runtime advanced the device to the closure; the closure's own sends are applied to it).  TX: nothing
+// is touched — ns-3 schedules the retry (:349-352), an event with a uid, so the caller does.  Otherwise: the batch is
+// flushed (its sends keep the receivers their channels had), then k_wl_rechan (when the number changes) and
+// k_wl_switch; the host's channel numbers, receiver counts and mirror follow.
+extern "C" int nsgpu_wifil_set_channel(nsgpu_wifil *h, uint64_t now, uint32_t phy, uint32_t nch, int64_t switch_delay_ns,
+                                       nsgpu_wifil_switch *out) {
+  if (!h || !out || phy >= h->D.nphy) return set_error(NSGPU_EINVAL, "nsgpu_wifil_set_channel: bad phy");
+  if (switch_delay_ns < 0) return set_error(NSGPU_EINVAL, "nsgpu_wifil_set_channel: negative ChannelSwitchDelay");
+  if (!h->mem.empty())
+    return set_error(NSGPU_ESTATE, "nsgpu_wifil_set_channel: channel switching is single-engine for now (a partitioned handle)");
+  WMir &mr = h->h_mir[phy];
+  const int64_t nw = (int64_t)now;
+  const uint32_t st = wl_state(mr, nw);
+  const bool init = now == 0;  // "this is not channel switch, this is initialization" (:330-336)
+  if (!init && st == NSGPU_WIFIL_SWITCHING)  // NS_ASSERT (!IsStateSwitching ()) (:338)
+    return set_error(NSGPU_ESTATE, "nsgpu_wifil_set_channel: phy %u is switching channels (yans-wifi-phy.cc:338 NS_ASSERT)", phy);
+  *out = nsgpu_wifil_switch{NSGPU_WIFIL_SWITCH_DONE, st, 0};
+  if (!init && st == NSGPU_WIFIL_TX) {
+    out->outcome = NSGPU_WIFIL_SWITCH_POSTPONED;
+    out->retry_delay = mr.endTx - nw;  // GetDelayUntilIdle ()
+    return NSGPU_OK;
+  }
+  if (init) out->outcome = NSGPU_WIFIL_SWITCH_INIT;
+  if (!h->d_nbefore) {
+    if (int rc = wl_alloc(h, &h->d_nbefore, 1)) return rc;
+    NSGPU_HIP(hipDeviceSynchronize());  // (once: the word's zeroing, on the null stream, before h->s reads it)
+  }
+  if (int rcf = wl_flush_sends(h)) return rcf;
+  const uint32_t old = h->chan_h[phy];
+  const bool moved = old != nch;
+  if (moved) {
+    hipLaunchKernelGGL(k_wl_rechan, dim3(wl_grid(h->D.nphy, 256)), dim3(256), 0, h->s, h->D, phy, old, nch, h->d_nbefore);
+    uint32_t on_new = 0;  // the receiver counts behind nsgpu_wifil_receivers
+    for (size_t i = 0; i < h->chan_h.size(); i++) {
+      if (i == phy) continue;
+      if (h->chan_h[i] == old) h->recv[i]--;
+      else if (h->chan_h[i] == nch) h->recv[i]++, on_new++;
+    }
+    h->recv[phy] = on_new;
+    h->chan_h[phy] = nch;
+  }
+  hipLaunchKernelGGL(k_wl_switch, dim3(1), dim3(1), 0, h->s, h->D, phy, nw, switch_delay_ns, nch, init ? 0u : 1u,
+                     moved ? 1u : 0u, h->d_nbefore);
+  NSGPU_HIP(hipGetLastError());
+  if (!init) {  // k_wl_switch's state changes, in the host's copy
+    if (mr.rxing) mr.rxing = 0, mr.endRx = nw;
+    if (nw < mr.endCca) mr.endCca = nw;
+    mr.endSw = nw + switch_delay_ns;
+    h->n_switches++;
+  }
+  return NSGPU_OK;
+}
+
+// GetChannelNumber () of `phy`, its m_startSwitching / m_endSwitching and its switching counters (one device trip).
+extern "C" int nsgpu_wifil_get_channel(nsgpu_wifil *h, uint32_t phy, nsgpu_wifil_channel *out) {
+  if (!h || !out || phy >= h->D.nphy) return set_error(NSGPU_EINVAL, "nsgpu_wifil_get_channel: bad phy");
+  if (!h->mem.empty())
+    return set_error(NSGPU_ESTATE, "nsgpu_wifil_get_channel: channel switching is single-engine for now (a partitioned handle)");
+  if (int rcf = wl_flush_sends(h)) return rcf;
+  LPhy p;
+  NSGPU_HIP(hipMemcpyAsync(&p, h->D.ps + phy, sizeof(LPhy), hipMemcpyDeviceToHost, h->s));
+  NSGPU_HIP(hipStreamSynchronize(h->s));
+  *out = nsgpu_wifil_channel{h->chan_h[phy], 0, p.startSw, p.endSw, p.switches, p.drop_switching};
+  return NSGPU_OK;
+}
+
 // WifiPhyStateHelper::GetState / GetDelayUntilIdle of `phy` at `now` (wifi-phy-state-helper.cc:122-183).
 extern "C" int nsgpu_wifil_get_state(nsgpu_wifil *h, uint32_t phy, uint64_t now, nsgpu_wifil_phy_state *out) {
   if (!h || !out || phy >= h->D.nphy) return set_error(NSGPU_EINVAL, "nsgpu_wifil_get_state: bad phy");
@@ -2129,7 +2303,7 @@ extern "C" int nsgpu_wifil_get_state(nsgpu_wifil *h, uint32_t phy, uint64_t now,
   // left them: every event before `now` has run (the runtime advanced the device to the running closure)
   const WMir P = h->h_mir[phy];
   const int64_t nw = (int64_t)now;
-  out->state = P.endTx > nw ? NSGPU_WIFIL_TX : P.rxing ? NSGPU_WIFIL_RX : P.endCca > nw ? NSGPU_WIFIL_CCA_BUSY : NSGPU_WIFIL_IDLE;
+  out->state = wl_state(P, nw);
   out->rxing = P.rxing;
   out->end_tx = P.endTx;
   out->end_rx = P.endRx;
@@ -2137,6 +2311,7 @@ extern "C" int nsgpu_wifil_get_state(nsgpu_wifil *h, uint32_t phy, uint64_t now,
   int64_t r = 0;
   if (out->state == NSGPU_WIFIL_RX) r = P.endRx - nw;
   else if (out->state == NSGPU_WIFIL_TX) r = P.endTx - nw;
+  else if (out->state == NSGPU_WIFIL_SWITCHING) r = P.endSw - nw;
   else if (out->state == NSGPU_WIFIL_CCA_BUSY) r = P.endCca - nw;
   out->delay_until_idle = r > 0 ? r : 0;
   return NSGPU_OK;
@@ -2375,7 +2550,7 @@ static int wlg_advance(nsgpu_wifil *G, uint64_t bts, uint32_t buid, uint32_t *ui
   const int P = (int)G->plo.size();
   // (1) every partition's epoch: the batched SendPackets, then its phys' events below the bound
   for (nsgpu_wifil *m : G->mem) {
-    if (m->D.nown) hipLaunchKernelGGL(k_wl_stepw<false>, dim3((unsigned)m->D.nown), dim3(64), 0, s, m->D, bts, buid, m->sb);
+    if (m->D.nown) hipLaunchKernelGGL((k_wl_stepw<false, false>), dim3((unsigned)m->D.nown), dim3(64), 0, s, m->D, bts, buid, m->sb);
     m->sb.n = 0;
   }
   NSGPU_HIP(hipGetLastError());

@@ -56,7 +56,8 @@ HipYansWifiPhy::HipYansWifiPhy ()
     m_rt (0),
     m_index (0),
     m_bound (false),
-    m_random (0.0, 1.0)
+    m_random (0.0, 1.0),
+    m_hipChannelNumber (1)
 {
 }
 
@@ -124,7 +125,7 @@ void
 HipYansWifiPhy::SendPacket (Ptr<const Packet> packet, WifiMode txMode, enum WifiPreamble preamble, uint8_t txPower)
 {
   NS_LOG_FUNCTION (this << packet << txMode << preamble << (uint32_t) txPower);
-  NS_ASSERT (!Helper ()->IsStateTx () && !IsStateTx ());
+  NS_ASSERT (!Helper ()->IsStateTx () && !IsStateTx () && !IsStateSwitching ());  // (:508)
   const Time txDuration = CalculateTxDuration (packet->GetSize (), txMode, preamble);
   NotifyTxBegin (packet);
   const uint32_t rate500 = txMode.GetDataRate () / 500000;
@@ -181,7 +182,50 @@ HipYansWifiPhy::IsStateTx (void)
 bool
 HipYansWifiPhy::IsStateSwitching (void)
 {
-  return false;  // (no channel switching on the device path)
+  return State ().state == NSGPU_WIFIL_SWITCHING;
+}
+
+// YansWifiPhy::SetChannelNumber (yans-wifi-phy.cc:327-374) on the device (nsgpu_sim_wifi_set_channel): the state
+// decision (:338-361), the cancelled EndReceive, EraseEvents and the channel lists are the device's; the state
+// helper's SwitchToChannelSwitching (:364: NotifySwitchingStart reaches DcfManager, the State trace) runs here, and a
+// switch postponed while transmitting is rescheduled here (:349-352), with the uid the reference's Schedule takes.
+void
+HipYansWifiPhy::SetChannelNumber (uint16_t nch)
+{
+  if (Simulator::Now () == Seconds (0))
+    {
+      // "this is not channel switch, this is initialization" (:330-336); attribute construction comes through here
+      YansWifiPhy::SetChannelNumber (nch);
+      m_hipChannelNumber = nch;
+      if (m_bound)
+        {
+          nsgpu_wifil_switch out;
+          NSGPU_RT (nsgpu_sim_wifi_set_channel (m_rt, m_index, nch, 0, &out));
+        }
+      return;
+    }
+  if (!m_bound)
+    {
+      NS_FATAL_ERROR ("HipYansWifiPhy: not attached (HipWifiBinding::Attach before Run)");
+    }
+  TimeValue delay;
+  GetAttribute ("ChannelSwitchDelay", delay);
+  nsgpu_wifil_switch out;
+  // (a call while SWITCHING is the reference's NS_ASSERT (!IsStateSwitching ()), :338: NSGPU_ESTATE, fatal here)
+  NSGPU_RT (nsgpu_sim_wifi_set_channel (m_rt, m_index, nch, delay.Get ().GetNanoSeconds (), &out));
+  if (out.outcome == NSGPU_WIFIL_SWITCH_POSTPONED)
+    {
+      Simulator::Schedule (NanoSeconds (out.retry_delay), &HipYansWifiPhy::SetChannelNumber, this, nch);
+      return;
+    }
+  Helper ()->SwitchToChannelSwitching (delay.Get ());
+  m_hipChannelNumber = nch;
+}
+
+uint16_t
+HipYansWifiPhy::GetChannelNumber (void) const
+{
+  return m_hipChannelNumber;
 }
 Time
 HipYansWifiPhy::GetDelayUntilIdle (void)
@@ -227,11 +271,12 @@ HipYansWifiPhy::OnNote (const nsgpu_wifil_note &note, Ptr<const Packet> sent)
     }
   else
     {
-      NotifyRxDrop (packet);  // (:440 / :451 / :477)
+      NotifyRxDrop (packet);  // (:421 while SWITCHING / :440 / :451 / :477)
     }
   if (note.cca_duration != 0)
     {
-      Helper ()->SwitchMaybeToCcaBusy (NanoSeconds (note.cca_duration));  // (:491-495)
+      // (:491-495; a SWITCHING drop reaches it when the frame outlasts m_endSwitching, :429-434)
+      Helper ()->SwitchMaybeToCcaBusy (NanoSeconds (note.cca_duration));
     }
 }
 

@@ -5,7 +5,7 @@
  *  - ns3::HipYansWifiPhy : YansWifiPhy — the MAC-facing half of a YansWifiPhy whose receive path runs on the
  *    device: SendPacket (yans-wifi-phy.cc:499-522) hands the frame to nsgpu_sim_wifi_send (the device makes
  *    YansWifiChannel::Send's Receive events with the runtime's next uids, yans-wifi-channel.cc:77-115), the state
- *    queries (IsStateIdle / Rx / Tx / CcaBusy, GetDelayUntilIdle: wifi-phy-state-helper.cc:122-183) read the
+ *    queries (IsStateIdle / Rx / Tx / CcaBusy / Switching, GetDelayUntilIdle: wifi-phy-state-helper.cc:122-183) read the
  *    device's state through nsgpu_sim_wifi_state, and EndReceive (yans-wifi-phy.cc:770-799) comes back to the host
  *    at its place in the event order (nsgpu_sim_wifi_set_end_handler): the m_random draw, the Rx traces and the
  *    MAC's receive callbacks run here, so their Schedule calls take the uids the reference's would.  The phy
@@ -64,6 +64,12 @@ public:
   virtual bool IsStateTx (void);
   virtual bool IsStateSwitching (void);
   virtual Time GetDelayUntilIdle (void);
+  /* YansWifiPhy::SetChannelNumber (yans-wifi-phy.cc:327-374) through nsgpu_sim_wifi_set_channel with the
+   * ChannelSwitchDelay attribute: at Now () == 0 the number alone; otherwise the device switches (or reports the
+   * switch postponed while transmitting, which is rescheduled here as :349-352 does) and the state helper's
+   * SwitchToChannelSwitching runs here, so NotifySwitchingStart reaches the listeners */
+  virtual void SetChannelNumber (uint16_t id);
+  virtual uint16_t GetChannelNumber (void) const;
 
   /* YansWifiPhy::EndReceive's host part, called by the runtime at the EndReceive's place (Now () = its time):
    * the m_random draw against the device's PER, then the traces and the MAC's callbacks (:783-798) */
@@ -85,6 +91,7 @@ private:
   bool m_bound;
   UniformVariable m_random;  // YansWifiPhy::m_random (:783)
   Ptr<WifiPhyStateHelper> m_hipState;  // YansWifiPhy::m_state (private there), through the "State" attribute
+  uint16_t m_hipChannelNumber;         // YansWifiPhy::m_channelNumber (private there)
 };
 
 class HipYansWifiPhyHelper : public YansWifiPhyHelper

@@ -190,6 +190,10 @@ SIGNATURES = {
     "nsgpu_sim_wifi_set_velocity": (C.c_int, [_vp, _u32, _vp]),
     "nsgpu_sim_wifi_pause": (C.c_int, [_vp, _u32, _u32]),
     "nsgpu_sim_wifi_get_mobility": (C.c_int, [_vp, _u32, _vp]),
+    "nsgpu_wifil_set_channel": (C.c_int, [_vp, _u64, _u32, _u32, C.c_int64, _vp]),
+    "nsgpu_wifil_get_channel": (C.c_int, [_vp, _u32, _vp]),
+    "nsgpu_sim_wifi_set_channel": (C.c_int, [_vp, _u32, _u32, C.c_int64, _vp]),
+    "nsgpu_sim_wifi_get_channel": (C.c_int, [_vp, _u32, _vp]),
     "nsgpu_p2p_group_create": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_void_p)]),
     "nsgpu_p2p_group_reset": (C.c_int, [_vp, _vp]),
     "nsgpu_p2p_group_run": (C.c_int, [_vp, _vp]),
@@ -784,6 +788,26 @@ class Sim:
         m = wifi.Mobility()
         check(lib().nsgpu_sim_wifi_get_mobility(self.h, phy, C.byref(m)))
         return tuple(m.pos), tuple(m.vel), bool(m.paused)
+
+    def wifi_set_channel(self, phy, nch, delay_ns):
+        """YansWifiPhy::SetChannelNumber (nch) of `phy` now, ChannelSwitchDelay = delay_ns (nsgpu_sim_wifi_set_channel).
+        While the phy transmits the switch is postponed: this schedules its own retry after GetDelayUntilIdle (), as
+        ns-3 does (Simulator::Schedule (GetDelayUntilIdle (), &SetChannelNumber, this, nch): one event, one uid).
+        Returns (outcome, previous state, retry delay ns): wifi.SWITCH_DONE / SWITCH_INIT / SWITCH_POSTPONED."""
+        import wifi
+        out = wifi.WifilSwitch()
+        check(lib().nsgpu_sim_wifi_set_channel(self.h, phy, nch, int(delay_ns), C.byref(out)))
+        if out.outcome == wifi.SWITCH_POSTPONED:
+            self.schedule(out.retry_delay, lambda: self.wifi_set_channel(phy, nch, delay_ns))
+        return out.outcome, out.prev_state, out.retry_delay
+
+    def wifi_get_channel(self, phy):
+        """`phy`'s channel record (nsgpu_sim_wifi_get_channel): dict of channel, start_switching, end_switching,
+        switches, drop_switching."""
+        import wifi
+        out = wifi.WifilChannel()
+        check(lib().nsgpu_sim_wifi_get_channel(self.h, phy, C.byref(out)))
+        return wifi.channel_record(out)
 
     def wifi_send(self, phy, size, dbm, mode, preamble):
         """YansWifiPhy::SendPacket of `phy` now (mode = (modclass, rate, bandwidth))."""

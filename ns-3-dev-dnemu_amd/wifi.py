@@ -260,9 +260,12 @@ def group_run(engines, stream=None):
 # ---- closed-loop PHY (nsgpu_wifil_*: SendPacket from host closures on nsgpu_sim) ----
 NIST, YANS = 0, 1  # nsgpu_wifil_error_model
 IDLE, RX, TX, CCA_BUSY = 0, 1, 2, 3  # nsgpu_wifil_state
+SWITCHING = 4  # (after LoopPhy.set_channel / Sim.wifi_set_channel, until m_endSwitching)
+SWITCH_DONE, SWITCH_INIT, SWITCH_POSTPONED = 0, 1, 2  # NSGPU_WIFIL_SWITCH_*
 WIFIL_END_DTYPE = np.dtype([("ts", "<u8"), ("uid", "<u4"), ("phy", "<u4"), ("snr", "<f8"), ("per", "<f8"),
                             ("tx", "<u4"), ("flags", "<u4"), ("rx_w", "<f8")])
 NOTE_SYNC, NOTE_DROP_RX, NOTE_DROP_TX, NOTE_DROP_ED = 0, 1, 2, 3  # NSGPU_WIFIL_NOTE_*
+NOTE_DROP_SWITCHING = 4
 WIFIL_NOTE_DTYPE = np.dtype([("ts", "<u8"), ("uid", "<u4"), ("phy", "<u4"), ("tx", "<u4"), ("kind", "<u4"),
                              ("state", "<u4"), ("pad_", "<u4"), ("rx_duration", "<i8"), ("cca_duration", "<i8")])
 
@@ -344,6 +347,21 @@ class WifilConfigStruct(C.Structure):
 class WifilPhyState(C.Structure):
     _fields_ = [("state", C.c_uint32), ("rxing", C.c_uint32), ("end_tx", C.c_int64), ("end_rx", C.c_int64),
                 ("end_cca_busy", C.c_int64), ("delay_until_idle", C.c_int64)]
+
+
+class WifilSwitch(C.Structure):  # nsgpu_wifil_switch
+    _fields_ = [("outcome", C.c_uint32), ("prev_state", C.c_uint32), ("retry_delay", C.c_int64)]
+
+
+class WifilChannel(C.Structure):  # nsgpu_wifil_channel
+    _fields_ = [("channel", C.c_uint32), ("pad_", C.c_uint32), ("start_switching", C.c_int64),
+                ("end_switching", C.c_int64), ("switches", C.c_uint64), ("drop_switching", C.c_uint64)]
+
+
+def channel_record(c):
+    """A WifilChannel as a dict of Python ints."""
+    return dict(channel=c.channel, start_switching=c.start_switching, end_switching=c.end_switching,
+                switches=c.switches, drop_switching=c.drop_switching)
 
 
 class Mobility(C.Structure):  # nsgpu_mobility (include/nsgpu_types.h)
@@ -451,6 +469,20 @@ class LoopPhy:
         m = Mobility()
         nsgpu.check(nsgpu.lib().nsgpu_wifil_get_mobility(self.h, int(now), phy, C.byref(m)))
         return tuple(m.pos), tuple(m.vel), bool(m.paused)
+
+    def set_channel(self, now, phy, nch, delay_ns):
+        """YansWifiPhy::SetChannelNumber (nch) of `phy` at `now` ns with ChannelSwitchDelay delay_ns
+        (nsgpu_wifil_set_channel): (outcome, previous state, retry delay ns).  SWITCH_POSTPONED (the phy transmits)
+        changes nothing: the caller retries after the delay (Sim.wifi_set_channel schedules that itself)."""
+        out = WifilSwitch()
+        nsgpu.check(nsgpu.lib().nsgpu_wifil_set_channel(self.h, int(now), phy, nch, int(delay_ns), C.byref(out)))
+        return out.outcome, out.prev_state, out.retry_delay
+
+    def get_channel(self, phy):
+        """nsgpu_wifil_get_channel: dict of channel, start_switching, end_switching, switches, drop_switching."""
+        out = WifilChannel()
+        nsgpu.check(nsgpu.lib().nsgpu_wifil_get_channel(self.h, phy, C.byref(out)))
+        return channel_record(out)
 
     def read_notes(self):
         """The notes of the epochs advanced since the last call (WIFIL_NOTE_DTYPE, (ts, uid) order)."""
