@@ -269,6 +269,27 @@ int nsgpu_wifil_get_mobility(nsgpu_wifil *h, uint64_t now, uint32_t phy, nsgpu_m
 int nsgpu_wifil_set_channel(nsgpu_wifil *h, uint64_t now, uint32_t phy, uint32_t nch, int64_t switch_delay_ns,
                             nsgpu_wifil_switch *out);
 int nsgpu_wifil_get_channel(nsgpu_wifil *h, uint32_t phy, nsgpu_wifil_channel *out);
+/* The loss chain of every later SendPacket: an extended chain (nsgpu_lossx, nsgpu_types.h) whose links may also be
+ * TwoRayGroundPropagationLossModel (propagation-loss-model.cc:323-409: both antennas' z + HeightAboveZ, Friis up to the
+ * crossover distance), ThreeLogDistancePropagationLossModel (:548-587) and MatrixPropagationLossModel (:730-796: the
+ * loss of the (sender, receiver) pair, keyed by phy index — how a hidden-terminal scenario is built — or DefaultLoss;
+ * the reference's default, DBL_MAX, gives 0 W).  lx == NULL: the config's chain again.  May be called before the first
+ * send and at any time between calls; a run-time MatrixPropagationLossModel::SetLoss is a call with the new entry list
+ * (the structure and its entries are copied: the caller's may go).  The staged sends are applied first, so every send
+ * keeps the powers of its own Now; the Matrix entries become a per-sender table (row[n_phy + 1], receivers ascending,
+ * of duplicates the last), uploaded in stream order behind every kernel that reads the table before it.  With
+ * constant-velocity mobility the heights TwoRayGround sees are the ones the send's position update left.  A run that
+ * never installs a chain launches the kernels it launched without this call.
+ * NSGPU_EINVAL, before anything is touched (an installed chain stays): n outside 0 .. NSGPU_MAX_LOSS_CHAIN, an unknown
+ * kind, two MATRIX links, an entry with a or b >= n_phy, entries without an array, a non-finite parameter (of those
+ * the kind reads) other than the Matrix default.  NSGPU_ESTATE: a partitioned handle (create_dist / create_group:
+ * single-engine for now).  The open-loop engine (nsgpu_wifi_run) and nsgpu_fanout_* keep the distance-only chain. */
+int nsgpu_wifil_set_loss(nsgpu_wifil *h, const nsgpu_lossx *lx);
+/* CalcRxPower (tx_dbm, a, b) over an extended chain, host only (no device is touched): phy a at pa sends, phy b at
+ * pb receives.  It builds nsgpu_wifil_set_loss's table and evaluates the function the kernels call — what a binding
+ * answers PropagationLossModel::CalcRxPower queries with.  The same NSGPU_EINVAL cases, without the phy bound. */
+int nsgpu_lossx_calc(const nsgpu_lossx *lx, uint32_t a, uint32_t b, const double pa[3], const double pb[3], double tx_dbm,
+                     double *rx_dbm);
 int nsgpu_wifil_read_ends(nsgpu_wifil *h, nsgpu_wifil_end *out, uint64_t cap, uint64_t *n);  /* since last read */
 int nsgpu_wifil_read_phys(nsgpu_wifil *h, nsgpu_wifi_phy_counters *out);                    /* n_phy */
 int nsgpu_wifil_pending(nsgpu_wifil *h, uint64_t *n, uint64_t *next_ts);
@@ -460,6 +481,10 @@ int nsgpu_sim_wifi_get_mobility(nsgpu_sim *s, uint32_t phy, nsgpu_mobility *out)
  * caller's (nsgpu.Sim.wifi_set_channel does).  nsgpu_sim_wifi_get_channel: nsgpu_wifil_get_channel. */
 int nsgpu_sim_wifi_set_channel(nsgpu_sim *s, uint32_t phy, uint32_t nch, int64_t switch_delay_ns, nsgpu_wifil_switch *out);
 int nsgpu_sim_wifi_get_channel(nsgpu_sim *s, uint32_t phy, nsgpu_wifil_channel *out);
+/* nsgpu_wifil_set_loss on the attached PHY from the running closure: the sends the closure has made keep the chain
+ * they were made under, its later ones and every later closure's take the new one (a run-time
+ * MatrixPropagationLossModel::SetLoss).  No PHY attached: NSGPU_ESTATE. */
+int nsgpu_sim_wifi_set_loss(nsgpu_sim *s, const nsgpu_lossx *lx);
 /* EndReceive hand-back (YansWifiPhy::EndReceive, yans-wifi-phy.cc:770-799): for every phy marked with
  * nsgpu_sim_wifi_listen, the runtime stops the device AT each of the phy's EndReceives (the event itself runs on
  * the device: CalculateSnrPer, the state switch) and calls fn (user, &end) right there in the (ts, uid) order,

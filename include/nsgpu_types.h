@@ -438,6 +438,25 @@ typedef struct nsgpu_mobility {
   uint32_t paused, pad_;   /* m_paused (a fresh ConstantVelocityMobilityModel is paused) */
 } nsgpu_mobility;
 
+/* The closed-loop PHY's extended loss chain (nsgpu_wifil_set_loss): the PropagationLossModels that are not a
+ * function of the distance alone, next to the nsgpu_loss_kind ones.  nsgpu_loss_model / nsgpu_loss_chain keep their
+ * layout (the oracle shares it); an extended chain is installed on a handle by a call of its own. */
+enum nsgpu_lossx_kind {            /* 0-4: the nsgpu_loss_kind values, same meaning, parameters in p[0..2] */
+  NSGPU_LOSSX_TWO_RAY_GROUND = 5,  /* p0 lambda, p1 system loss, p2 min distance, p3 HeightAboveZ   (:323-409) */
+  NSGPU_LOSSX_THREE_LOG      = 6,  /* p0-p2 distance0..2, p3-p5 exponent0..2, p6 reference loss     (:548-587) */
+  NSGPU_LOSSX_MATRIX         = 7   /* p0 DefaultLoss; entries in the nsgpu_lossx's table            (:781-796) */
+};
+typedef struct nsgpu_lossx_model { int32_t kind, pad_; double p[8]; } nsgpu_lossx_model;   /* 72 bytes */
+/* MatrixPropagationLossModel::SetLoss (a, b, loss, false) (:752-772): a, b are phy indices (ns-3 keys its map by
+ * MobilityModel pointer; a binding maps one to the other).  A symmetric SetLoss is two entries. */
+typedef struct nsgpu_lossx_entry { uint32_t a, b; double loss_db; } nsgpu_lossx_entry;
+typedef struct nsgpu_lossx {
+  int32_t n, pad_;                       /* links, <= NSGPU_MAX_LOSS_CHAIN; at most one MATRIX link */
+  nsgpu_lossx_model m[NSGPU_MAX_LOSS_CHAIN];
+  const nsgpu_lossx_entry *entry;        /* host pointer, any order; a later duplicate (a, b) wins, as SetLoss does */
+  uint64_t n_entry;
+} nsgpu_lossx;
+
 #ifdef __cplusplus
 }
 #endif

@@ -93,6 +93,86 @@ __host__ __device__ __forceinline__ double calc_rx_power(const nsgpu_loss_chain 
   return self;
 }
 
+// ---- the extended chain (nsgpu_lossx, nsgpu_wifil_set_loss): links that need more than the distance ----
+// MatrixPropagationLossModel's m_loss as a per-sender table: sender s's entries are col / loss [row[s], row[s + 1]),
+// col ascending and unique (the host builds it: lossx_table in nsgpu_wifil.hip).  All null: no entries.
+struct LossTable {
+  const uint32_t *row, *col;
+  const double *loss;
+};
+// One link's DoCalcRxPower from phy s (antenna at z = zs) to phy j (z = zj), `distance` apart: the reference's
+// statements in the reference's order (the library is built -ffp-contract=off: nothing contracts into an FMA).
+__host__ __device__ __forceinline__ double lossx_link(const nsgpu_lossx_model &m, const LossTable &tb, double tx,
+                                                      uint32_t s, uint32_t j, double zs, double zj, double distance) {
+  const double PI = 3.14159265358979323846;
+  switch (m.kind) {
+    case NSGPU_LOSSX_TWO_RAY_GROUND: {  // :339-409
+      const double m_lambda = m.p[0], m_systemLoss = m.p[1], m_minDistance = m.p[2], m_heightAboveZ = m.p[3];
+      if (distance <= m_minDistance) return tx;
+      double txAntHeight = zs + m_heightAboveZ;
+      double rxAntHeight = zj + m_heightAboveZ;
+      double dCross = (4 * PI * txAntHeight * rxAntHeight) / m_lambda;
+      double tmp = 0;
+      if (distance <= dCross) {  // Friis
+        double numerator = m_lambda * m_lambda;
+        tmp = PI * distance;
+        double denominator = 16 * tmp * tmp * m_systemLoss;
+        double pr = 10 * log10(numerator / denominator);
+        return tx + pr;
+      } else {  // two-ray path loss
+        tmp = txAntHeight * rxAntHeight;
+        double rayNumerator = tmp * tmp;
+        tmp = distance * distance;
+        double rayDenominator = tmp * tmp * m_systemLoss;
+        double rayPr = 10 * log10(rayNumerator / rayDenominator);
+        return tx + rayPr;
+      }
+    }
+    case NSGPU_LOSSX_THREE_LOG: {  // :548-587
+      const double m_distance0 = m.p[0], m_distance1 = m.p[1], m_distance2 = m.p[2];
+      const double m_exponent0 = m.p[3], m_exponent1 = m.p[4], m_exponent2 = m.p[5], m_referenceLoss = m.p[6];
+      double pathLossDb;
+      if (distance < m_distance0) {
+        pathLossDb = 0;
+      } else if (distance < m_distance1) {
+        pathLossDb = m_referenceLoss + 10 * m_exponent0 * log10(distance / m_distance0);
+      } else if (distance < m_distance2) {
+        pathLossDb = m_referenceLoss + 10 * m_exponent0 * log10(m_distance1 / m_distance0) +
+                     10 * m_exponent1 * log10(distance / m_distance1);
+      } else {
+        pathLossDb = m_referenceLoss + 10 * m_exponent0 * log10(m_distance1 / m_distance0) +
+                     10 * m_exponent1 * log10(m_distance2 / m_distance1) + 10 * m_exponent2 * log10(distance / m_distance2);
+      }
+      return tx - pathLossDb;
+    }
+    case NSGPU_LOSSX_MATRIX: {  // :781-796: m_loss.find (make_pair (a, b)), else m_default
+      if (tb.row) {
+        uint32_t lo = tb.row[s];
+        const uint32_t end = tb.row[s + 1];
+        uint32_t hi = end;
+        while (lo < hi) {  // the first column >= j
+          const uint32_t mid = lo + (hi - lo) / 2;
+          if (tb.col[mid] < j) lo = mid + 1;
+          else hi = mid;
+        }
+        if (lo < end && tb.col[lo] == j) return tx - tb.loss[lo];
+      }
+      return tx - m.p[0];
+    }
+    default: {  // the nsgpu_loss_kind links: loss_link itself
+      const nsgpu_loss_model o{m.kind, 0, m.p[0], m.p[1], m.p[2]};
+      return loss_link(o, tx, distance);
+    }
+  }
+}
+// PropagationLossModel::CalcRxPower over an extended chain (:64-74).
+__host__ __device__ __forceinline__ double calc_rx_power_x(const nsgpu_lossx_model *m, int n, const LossTable &tb, double tx,
+                                                           uint32_t s, uint32_t j, double zs, double zj, double distance) {
+  double self = tx;
+  for (int i = 0; i < n; i++) self = lossx_link(m[i], tb, self, s, j, zs, zj, distance);
+  return self;
+}
+
 // Event key order (scheduler.h:105-121): (ts, uid).
 __host__ __device__ __forceinline__ bool key_less(uint64_t ats, uint32_t auid, uint64_t bts, uint32_t buid) {
   return ats < bts || (ats == bts && auid < buid);

@@ -803,6 +803,13 @@ int nsgpu_sim_wifi_get_channel(nsgpu_sim *s, uint32_t phy, nsgpu_wifil_channel *
   return nsgpu_wifil_get_channel(s->wifi, phy, out);
 }
 
+// The attached PHY's loss chain from the running closure on (nsgpu_wifil_set_loss): the closure's earlier sends keep
+// the chain they were made under.
+int nsgpu_sim_wifi_set_loss(nsgpu_sim *s, const nsgpu_lossx *lx) {
+  if (!s || !s->wifi) return set_error(NSGPU_ESTATE, "nsgpu_sim_wifi_set_loss: no Wi-Fi PHY attached");
+  return nsgpu_wifil_set_loss(s->wifi, lx);
+}
+
 // WifiPhyStateHelper::GetState of `phy` at Now (the device has run every event before the running closure).
 int nsgpu_sim_wifi_state(nsgpu_sim *s, uint32_t phy, nsgpu_wifil_phy_state *out) {
   if (!s || !s->wifi) return set_error(NSGPU_ESTATE, "nsgpu_sim_wifi_state: no Wi-Fi PHY attached");

@@ -25,6 +25,7 @@
 // Receive queue (sorted by (arrival, uid)) and up to LPE_CAP pending EndReceive records.
 #include <algorithm>
 #include <atomic>
+#include <cmath>
 #include <cstddef>
 #include <cstdio>
 #include <cstring>
@@ -109,6 +110,12 @@ struct LEck {  // an end record's chunks: ck[start, start + n) (n = NONE: its PE
   double w;  // rxPowerW
 };
 
+struct LossX {  // an installed extended chain (nsgpu_wifil_set_loss), device-resident: the links and the Matrix table
+  int32_t n, pad;
+  nsgpu_lossx_model m[NSGPU_MAX_LOSS_CHAIN];
+  LossTable tb;
+};
+
 struct WDev {
   int64_t nphy;
   const double *x, *y, *z;
@@ -164,6 +171,9 @@ struct WDev {
   // constant-velocity mobility (nsgpu_wifil_set_mobility): a record per phy, sized at the first install (null
   // until then); k_wl_move, launched ahead of a send's k_wl_rx only while some phy has a model, updates x / y / z
   WMob *mob;
+  // the extended loss chain (nsgpu_wifil_set_loss): null until one is installed; only k_wl_send<true> / k_wl_rx<true>,
+  // launched while one is, read it
+  const LossX *lx;
 };
 // The epoch's dispatched events are appended to EV_STRIPES lists (phy j's to stripe j % EV_STRIPES): one
 // counter a phy's event would serialize ~10^4 atomics an epoch on one line.
@@ -397,14 +407,19 @@ __device__ __forceinline__ uint32_t wave_incscan32(uint32_t v) {
 }
 
 // YansWifiChannel::Send's delivery of transmission t (index k, from the closure's uid base) to phy j (not the
-// sender): its Receive — ConstantSpeed delay, the loss chain + RxGain, DbmToW, the receiver loop's uid.
+// sender): its Receive — ConstantSpeed delay, the loss chain + RxGain, DbmToW, the receiver loop's uid.  LX: the
+// chain is the installed extended one (D.lx: links that take the two phys and their heights); <false> is the
+// config's chain and never names D.lx.
+template <bool LX>
 __device__ __forceinline__ bool reception(const WDev &D, int64_t j, const LTx &t, uint32_t k, double dbm, uint32_t base,
                                           LRx &out) {
   const uint32_t s = t.phy;
   if (D.chan[j] != D.chan[s]) return false;  // other channels get nothing (yans-wifi-channel.cc:88-91)
   const double dist = distance3(D.x[s], D.y[s], D.z[s], D.x[j], D.y[j], D.z[j]);
   const uint64_t at = t.ts + (uint64_t)seconds_to_ts(dist / D.speed);  // ConstantSpeed delay (propagation-delay-model.cc:90-96)
-  const double dBm = calc_rx_power(D.loss, dbm, dist) + D.rx_gain_db;      // StartReceivePacket: rxPowerDbm += RxGain
+  double dBm;
+  if constexpr (LX) dBm = calc_rx_power_x(D.lx->m, D.lx->n, D.lx->tb, dbm, s, (uint32_t)j, D.z[s], D.z[j], dist) + D.rx_gain_db;
+  else dBm = calc_rx_power(D.loss, dbm, dist) + D.rx_gain_db;              // StartReceivePacket: rxPowerDbm += RxGain
   const double w = pow(10.0, dBm / 10.0) / 1000.0;                         // DbmToW (yans-wifi-phy.cc:727-732)
   out = LRx{at, base + D.chan_rank[j] - (j > (int64_t)s ? 1u : 0u), k, w, t.dur};  // the receiver loop's Schedule order
   return true;
@@ -1351,6 +1366,7 @@ __global__ void k_wl_zero(const WDev D) {
 __global__ void k_wl_set(uint32_t *p, uint32_t v) { *p = v; }
 
 // SendPacket of phy s at (ts): the sender's state switch (thread s) and one Receive per receiver.
+template <bool LX>
 __global__ __launch_bounds__(256) void k_wl_send(const WDev D, uint32_t k, LTx t, double dbm, uint32_t base) {
   const int64_t j = D.j0 + (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (blockIdx.x == 0 && threadIdx.x == 0) D.tx[k] = t;  // (every partition holds every transmission)
@@ -1377,7 +1393,7 @@ __global__ __launch_bounds__(256) void k_wl_send(const WDev D, uint32_t k, LTx t
     return;
   }
   LRx e;
-  if (!reception(D, j, t, k, dbm, base, e)) return;
+  if (!reception<LX>(D, j, t, k, dbm, base, e)) return;
   const uint64_t at = e.at;
   const uint32_t uid = e.uid;
   LPhy &P = D.ps[j];
@@ -1400,12 +1416,13 @@ __global__ __launch_bounds__(256) void k_wl_send(const WDev D, uint32_t k, LTx t
 // The Receives of one SendPacket (YansWifiChannel::Send's loop), computed when the closure sends — while the
 // host goes on — into the batch's row of D.rxb; the next epoch's k_wl_stepw queues them.  Thread 0 records
 // the transmission.
+template <bool LX>
 __global__ __launch_bounds__(256) void k_wl_rx(const WDev D, LRx *row, LTx t, uint32_t k, double dbm, uint32_t base) {
   const int64_t j = D.j0 + (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (blockIdx.x == 0 && threadIdx.x == 0) D.tx[k] = t;
   if (j >= D.j0 + D.nown) return;
   LRx e{};
-  if (j == (int64_t)t.phy || !reception(D, j, t, k, dbm, base, e)) e.at = ~0ull;
+  if (j == (int64_t)t.phy || !reception<LX>(D, j, t, k, dbm, base, e)) e.at = ~0ull;
   row[j] = e;
 }
 
@@ -1656,6 +1673,12 @@ struct nsgpu_wifil {
   std::vector<uint32_t> chan_h;
   uint64_t n_switches = 0;
   uint32_t *d_nbefore = nullptr;
+  // the extended loss chain (nsgpu_wifil_set_loss): one device block [LossX | loss | row | col] of lx_cap bytes, written
+  // on `s` from the pinned block lx_pin (lx_up: the last upload, waited for before lx_pin is written again); D.lx
+  // names the device block while a chain is installed
+  uint8_t *lx_dev = nullptr, *lx_pin = nullptr;
+  size_t lx_cap = 0;
+  hipEvent_t lx_up = nullptr;
   // ---- a partitioned PHY (nsgpu_wifil_create_dist / nsgpu_wifil_create_group): this handle is the host side
   // every rank replicates (the MAC's closures, the uids, GetState, the ends); `mem` are the partitions it runs —
   // one (RCCL: `comm`, the others on other GPUs) or all of them (a loopback group on this device) — each an engine
@@ -1723,6 +1746,9 @@ extern "C" int nsgpu_wifil_destroy(nsgpu_wifil *h) {
   }
   if (h->h_digtot) (void)hipHostFree(h->h_digtot);
   for (void *p : h->allocs) (void)hipFree(p);
+  if (h->lx_dev) (void)hipFree(h->lx_dev);
+  if (h->lx_pin) (void)hipHostFree(h->lx_pin);
+  if (h->lx_up) (void)hipEventDestroy(h->lx_up);
   if (h->h_stat) (void)hipHostFree(h->h_stat);
   if (h->h_mir) (void)hipHostFree(h->h_mir);
   if (h->h_pend) (void)hipHostFree(h->h_pend);
@@ -1922,8 +1948,9 @@ static int wl_check(nsgpu_wifil *h, const char *what) { return wl_check_bits(h->
 // The batched SendPackets as k_wl_send launches (before anything that reads the phys or moves one).
 static int wl_flush_sends(nsgpu_wifil *h) {
   const unsigned g = wl_grid(h->D.nown, 256);
+  const auto kern = h->D.lx ? k_wl_send<true> : k_wl_send<false>;  // (an extended chain is installed: its instantiation)
   for (uint32_t i = 0; i < h->sb.n; i++)
-    hipLaunchKernelGGL(k_wl_send, dim3(g), dim3(256), 0, h->s, h->D, h->sb.k0 + i, h->sb.t[i], h->sb.dbm[i], h->sb.base[i]);
+    hipLaunchKernelGGL(kern, dim3(g), dim3(256), 0, h->s, h->D, h->sb.k0 + i, h->sb.t[i], h->sb.dbm[i], h->sb.base[i]);
   h->sb.n = 0;
   NSGPU_HIP(hipGetLastError());
   return NSGPU_OK;
@@ -1974,7 +2001,7 @@ static int wl_queue_send(nsgpu_wifil *h, const LTx &t, double dbm, uint32_t uid_
   }
   const uint32_t k = (uint32_t)h->n_tx++;
   if (h->sb.n == 0) h->sb.k0 = k;
-  hipLaunchKernelGGL(k_wl_rx, dim3(wl_grid(h->D.nown, 256)), dim3(256), 0, h->s, h->D,
+  hipLaunchKernelGGL(h->D.lx ? k_wl_rx<true> : k_wl_rx<false>, dim3(wl_grid(h->D.nown, 256)), dim3(256), 0, h->s, h->D,
                      h->D.rxb + (uint64_t)h->sb.n * h->D.nphy, t, k, dbm, uid_base);
   NSGPU_HIP(hipGetLastError());
   h->sb.t[h->sb.n] = t;
@@ -2293,6 +2320,134 @@ extern "C" int nsgpu_wifil_get_channel(nsgpu_wifil *h, uint32_t phy, nsgpu_wifil
   NSGPU_HIP(hipMemcpyAsync(&p, h->D.ps + phy, sizeof(LPhy), hipMemcpyDeviceToHost, h->s));
   NSGPU_HIP(hipStreamSynchronize(h->s));
   *out = nsgpu_wifil_channel{h->chan_h[phy], 0, p.startSw, p.endSw, p.switches, p.drop_switching};
+  return NSGPU_OK;
+}
+
+// ---- the extended loss chain (nsgpu_wifil_set_loss, nsgpu_lossx_calc) ----
+// What makes a nsgpu_lossx unusable (n_phy < 0: no bound on the entries' phys); nothing is touched before it passes.
+static int lossx_check(const nsgpu_lossx *lx, int64_t n_phy, const char *what) {
+  if (lx->n < 0 || lx->n > NSGPU_MAX_LOSS_CHAIN) return set_error(NSGPU_EINVAL, "%s: %d links (0 .. %d)", what, lx->n, NSGPU_MAX_LOSS_CHAIN);
+  int matrices = 0;
+  for (int i = 0; i < lx->n; i++) {
+    const nsgpu_lossx_model &m = lx->m[i];
+    if (m.kind < 0 || m.kind > NSGPU_LOSSX_MATRIX) return set_error(NSGPU_EINVAL, "%s: link %d has unknown kind %d", what, i, m.kind);
+    if (m.kind == NSGPU_LOSSX_MATRIX) {  // (its one parameter, DefaultLoss, may be anything: the reference's is DBL_MAX)
+      if (++matrices > 1) return set_error(NSGPU_EINVAL, "%s: more than one MATRIX link", what);
+      continue;
+    }
+    const int np = m.kind == NSGPU_LOSSX_THREE_LOG ? 7 : m.kind == NSGPU_LOSSX_TWO_RAY_GROUND ? 4 : 3;
+    for (int q = 0; q < np; q++)
+      if (!std::isfinite(m.p[q])) return set_error(NSGPU_EINVAL, "%s: link %d's p%d is not finite", what, i, q);
+  }
+  if (lx->n_entry > 0xffffffffull) return set_error(NSGPU_EINVAL, "%s: more than 2^32 - 1 entries (the table's offsets are 32-bit)", what);
+  if (lx->n_entry && !lx->entry) return set_error(NSGPU_EINVAL, "%s: %llu entries and no entry array", what, (unsigned long long)lx->n_entry);
+  if (n_phy >= 0)
+    for (uint64_t e = 0; e < lx->n_entry; e++)
+      if (lx->entry[e].a >= n_phy || lx->entry[e].b >= n_phy)
+        return set_error(NSGPU_EINVAL, "%s: entry %llu names phy (%u, %u) of %lld", what, (unsigned long long)e, lx->entry[e].a,
+                         lx->entry[e].b, (long long)n_phy);
+  return NSGPU_OK;
+}
+static bool lossx_has_matrix(const nsgpu_lossx *lx) {
+  for (int i = 0; i < lx->n; i++)
+    if (lx->m[i].kind == NSGPU_LOSSX_MATRIX) return true;
+  return false;
+}
+// MatrixPropagationLossModel's map as the per-sender table of LossTable: row[n_phy + 1], then each sender's receivers
+// ascending with their losses; of several entries for one (a, b) the last one given stays (SetLoss overwrites, :762-765).
+static void lossx_table(const nsgpu_lossx *lx, int64_t n_phy, std::vector<uint32_t> &row, std::vector<uint32_t> &col,
+                        std::vector<double> &loss) {
+  std::vector<uint64_t> ord((size_t)lx->n_entry);
+  for (uint64_t e = 0; e < lx->n_entry; e++) ord[e] = e;
+  const nsgpu_lossx_entry *en = lx->entry;
+  std::stable_sort(ord.begin(), ord.end(), [en](uint64_t p, uint64_t q) {
+    return en[p].a != en[q].a ? en[p].a < en[q].a : en[p].b < en[q].b;
+  });
+  row.assign((size_t)n_phy + 1, 0);
+  col.clear();
+  loss.clear();
+  for (size_t i = 0; i < ord.size(); i++) {
+    const nsgpu_lossx_entry &x = en[ord[i]];
+    if (i + 1 < ord.size() && en[ord[i + 1]].a == x.a && en[ord[i + 1]].b == x.b) continue;  // (a later one follows)
+    col.push_back(x.b);
+    loss.push_back(x.loss_db);
+    row[(size_t)x.a + 1]++;
+  }
+  for (int64_t s = 0; s < n_phy; s++) row[(size_t)s + 1] += row[(size_t)s];
+}
+
+// CalcRxPower (tx_dbm, a, b) over an extended chain on the host: the table nsgpu_wifil_set_loss builds, the function
+// the kernels call.  pa / pb: the positions of phys a (the sender) and b.
+extern "C" int nsgpu_lossx_calc(const nsgpu_lossx *lx, uint32_t a, uint32_t b, const double pa[3], const double pb[3],
+                                double tx_dbm, double *rx_dbm) {
+  if (!lx || !pa || !pb || !rx_dbm) return set_error(NSGPU_EINVAL, "nsgpu_lossx_calc: null argument");
+  if (int rc = lossx_check(lx, -1, "nsgpu_lossx_calc")) return rc;
+  std::vector<uint32_t> row, col;
+  std::vector<double> loss;
+  LossTable tb{nullptr, nullptr, nullptr};
+  if (lossx_has_matrix(lx) && lx->n_entry) {
+    int64_t n_phy = (int64_t)std::max(a, b) + 1;
+    for (uint64_t e = 0; e < lx->n_entry; e++) n_phy = std::max<int64_t>(n_phy, (int64_t)std::max(lx->entry[e].a, lx->entry[e].b) + 1);
+    lossx_table(lx, n_phy, row, col, loss);
+    tb = LossTable{row.data(), col.data(), loss.data()};
+  }
+  const double dist = distance3(pa[0], pa[1], pa[2], pb[0], pb[1], pb[2]);  // a->GetDistanceFrom (b)
+  *rx_dbm = calc_rx_power_x(lx->m, lx->n, tb, tx_dbm, a, b, pa[2], pb[2], dist);
+  return NSGPU_OK;
+}
+
+// The handle's loss chain from now on (null: the config's again).  The batch is flushed first — k_wl_send launches,
+// which take the chain in force by value — so every send so far keeps the powers of its own Now.  The device block is
+// rewritten in stream order on h->s, the stream of every kernel that reads it: the copy runs after the last of them.
+// A larger block replaces it once the stream has drained.
+extern "C" int nsgpu_wifil_set_loss(nsgpu_wifil *h, const nsgpu_lossx *lx) {
+  if (!h) return set_error(NSGPU_EINVAL, "nsgpu_wifil_set_loss: null handle");
+  if (!h->mem.empty())
+    return set_error(NSGPU_ESTATE, "nsgpu_wifil_set_loss: the extended loss chain is single-engine for now (a partitioned handle)");
+  if (lx)
+    if (int rc = lossx_check(lx, h->D.nphy, "nsgpu_wifil_set_loss")) return rc;
+  if (int rcf = wl_flush_sends(h)) return rcf;
+  if (!lx) {
+    h->D.lx = nullptr;
+    return NSGPU_OK;
+  }
+  std::vector<uint32_t> row, col;
+  std::vector<double> loss;
+  const bool table = lossx_has_matrix(lx) && lx->n_entry;
+  if (table) lossx_table(lx, h->D.nphy, row, col, loss);
+  const size_t o_loss = sizeof(LossX), o_row = o_loss + loss.size() * sizeof(double),
+               o_col = o_row + row.size() * sizeof(uint32_t), size = o_col + col.size() * sizeof(uint32_t);
+  static_assert(sizeof(LossX) % 8 == 0, "the losses follow the links, 8-aligned");
+  if (size > h->lx_cap) {
+    NSGPU_HIP(hipStreamSynchronize(h->s));  // (no queued kernel reads the old block, no copy reads the old pinned one)
+    if (h->lx_dev) (void)hipFree(h->lx_dev);
+    if (h->lx_pin) (void)hipHostFree(h->lx_pin);
+    h->lx_dev = h->lx_pin = nullptr;
+    h->lx_cap = 0;
+    h->D.lx = nullptr;
+    const size_t cap = size + size / 2;  // (a table that grows entry by entry: not a new block each call)
+    NSGPU_HIP(hipMalloc((void **)&h->lx_dev, cap));
+    NSGPU_HIP(hipHostMalloc((void **)&h->lx_pin, cap, hipHostMallocDefault));
+    h->lx_cap = cap;
+    if (!h->lx_up) NSGPU_HIP(hipEventCreateWithFlags(&h->lx_up, hipEventDisableTiming));
+  } else {
+    NSGPU_HIP(hipEventSynchronize(h->lx_up));  // (the last upload has left the pinned block)
+  }
+  LossX X{};
+  X.n = lx->n;
+  for (int i = 0; i < lx->n; i++) X.m[i] = lx->m[i];
+  if (table)
+    X.tb = LossTable{reinterpret_cast<const uint32_t *>(h->lx_dev + o_row), reinterpret_cast<const uint32_t *>(h->lx_dev + o_col),
+                     reinterpret_cast<const double *>(h->lx_dev + o_loss)};
+  std::memcpy(h->lx_pin, &X, sizeof(LossX));
+  if (table) {
+    std::memcpy(h->lx_pin + o_loss, loss.data(), loss.size() * sizeof(double));
+    std::memcpy(h->lx_pin + o_row, row.data(), row.size() * sizeof(uint32_t));
+    std::memcpy(h->lx_pin + o_col, col.data(), col.size() * sizeof(uint32_t));
+  }
+  NSGPU_HIP(hipMemcpyAsync(h->lx_dev, h->lx_pin, size, hipMemcpyHostToDevice, h->s));
+  NSGPU_HIP(hipEventRecord(h->lx_up, h->s));
+  h->D.lx = reinterpret_cast<const LossX *>(h->lx_dev);
   return NSGPU_OK;
 }
 

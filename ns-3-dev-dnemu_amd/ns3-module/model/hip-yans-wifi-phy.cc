@@ -347,6 +347,8 @@ HipWifiBinding::HipWifiBinding ()
   : m_engine (0),
     m_rt (0)
 {
+  m_lossx = nsgpu_lossx ();
+  m_lossx.n = -1;  // (no extended chain: Attach's chain is in force)
 }
 
 HipWifiBinding::~HipWifiBinding ()
@@ -362,6 +364,7 @@ HipWifiBinding::DoDispose (void)
       nsgpu_sim_wifi_set_note_handler (m_rt, 0, 0);
     }
   m_phys.clear ();
+  m_mobs.clear ();
   m_tx.clear ();
   if (m_engine)
     {
@@ -448,6 +451,71 @@ HipWifiBinding::CourseChange (std::string context, Ptr<const MobilityModel> mobi
     }
 }
 
+// The kept chain to the device, from the running event on (or from the start, before Run).
+void
+HipWifiBinding::IssueLoss (void)
+{
+  NS_ASSERT (m_rt != 0 && m_lossx.n >= 0);
+  m_lossx.entry = m_lossEntries.empty () ? 0 : &m_lossEntries[0];
+  m_lossx.n_entry = m_lossEntries.size ();
+  NSGPU_RT (nsgpu_sim_wifi_set_loss (m_rt, &m_lossx));
+}
+
+void
+HipWifiBinding::SetLoss (const nsgpu_lossx &lossx)
+{
+  m_lossx = lossx;
+  m_lossEntries.assign (lossx.entry, lossx.entry + lossx.n_entry);
+  IssueLoss ();
+}
+
+void
+HipWifiBinding::SetMatrixLoss (Ptr<MobilityModel> a, Ptr<MobilityModel> b, double loss, bool symmetric)
+{
+  NS_ASSERT (a != 0 && b != 0);
+  bool matrix = false;
+  for (int32_t i = 0; i < m_lossx.n; i++)
+    {
+      matrix = matrix || m_lossx.m[i].kind == NSGPU_LOSSX_MATRIX;
+    }
+  if (!matrix)
+    {
+      NS_FATAL_ERROR ("HipWifiBinding::SetMatrixLoss: the chain in force has no Matrix link (SetLoss first)");
+    }
+  for (uint32_t i = 0; i < m_mobs.size (); i++)
+    {
+      for (uint32_t j = 0; j < m_mobs.size (); j++)
+        {
+          if (i == j || m_mobs[i] != a || m_mobs[j] != b)
+            {
+              continue;
+            }
+          const nsgpu_lossx_entry ab = { i, j, loss };
+          m_lossEntries.push_back (ab);
+          if (symmetric)  // SetLoss (mb, ma, loss, false) (:768-771)
+            {
+              const nsgpu_lossx_entry ba = { j, i, loss };
+              m_lossEntries.push_back (ba);
+            }
+        }
+    }
+  IssueLoss ();
+}
+
+double
+HipWifiBinding::CalcRxPower (double txPowerDbm, uint32_t a, uint32_t b) const
+{
+  NS_ASSERT (a < m_mobs.size () && b < m_mobs.size () && m_lossx.n >= 0);
+  const Vector va = m_mobs[a]->GetPosition (), vb = m_mobs[b]->GetPosition ();
+  const double pa[3] = { va.x, va.y, va.z }, pb[3] = { vb.x, vb.y, vb.z };
+  nsgpu_lossx lx = m_lossx;
+  lx.entry = m_lossEntries.empty () ? 0 : &m_lossEntries[0];
+  lx.n_entry = m_lossEntries.size ();
+  double rx = 0;
+  NSGPU_RT (nsgpu_lossx_calc (&lx, a, b, pa, pb, txPowerDbm, &rx));
+  return rx;
+}
+
 void
 HipWifiBinding::Attach (Ptr<HipSimulatorImpl> impl, Ptr<YansWifiChannel> channel, const nsgpu_loss_chain &loss,
                         double speed, uint64_t txCap)
@@ -493,6 +561,7 @@ HipWifiBinding::Attach (Ptr<HipSimulatorImpl> impl, Ptr<YansWifiChannel> channel
           NS_FATAL_ERROR ("HipWifiBinding: the device path takes one set of PHY attributes per channel");
         }
       m_phys.push_back (phy);
+      m_mobs.push_back (mob);
     }
   if (n == 0)
     {

@@ -133,7 +133,21 @@ public:
    * EndReceives hand back */
   void RecordTx (Ptr<const Packet> packet, WifiMode mode, enum WifiPreamble preamble);
 
+  /* The channel's loss chain from Now () on, as an extended chain (nsgpu_sim_wifi_set_loss): links that may be
+   * TwoRayGround, ThreeLogDistance and Matrix next to the kinds Attach takes; the chain and its entries are kept
+   * (SetMatrixLoss edits them).  The entries name phys by their index in the channel's m_phyList. */
+  void SetLoss (const nsgpu_lossx &lossx);
+  /* MatrixPropagationLossModel::SetLoss (a, b, loss, symmetric) (propagation-loss-model.cc:752-772) on the chain's
+   * Matrix link, at Now (): the models are mapped to the attached phys that aggregate them (a model shared by
+   * several phys: every pair gets the entry), the entry list is extended (a later entry for a pair wins, as the
+   * reference's map assignment) and the chain re-issued.  Needs a chain with a Matrix link (SetLoss). */
+  void SetMatrixLoss (Ptr<MobilityModel> a, Ptr<MobilityModel> b, double loss, bool symmetric = true);
+  /* PropagationLossModel::CalcRxPower (txPowerDbm, a, b) between two attached phys under the chain SetLoss
+   * installed, on the host (nsgpu_lossx_calc) */
+  double CalcRxPower (double txPowerDbm, uint32_t a, uint32_t b) const;
+
 private:
+  void IssueLoss (void);
   virtual void DoDispose (void);
   static void EndHandBack (void *user, const nsgpu_wifil_end *end);
   static void NoteHandBack (void *user, const nsgpu_wifil_note *note);
@@ -148,6 +162,9 @@ private:
   };
   std::vector<Ptr<HipYansWifiPhy> > m_phys;
   std::vector<Tx> m_tx;
+  std::vector<Ptr<MobilityModel> > m_mobs;        // per phy: its node's mobility model (SetMatrixLoss's keys)
+  nsgpu_lossx m_lossx;                            // the extended chain in force (n = -1: Attach's chain)
+  std::vector<nsgpu_lossx_entry> m_lossEntries;   // its Matrix entries, in SetLoss order
   nsgpu_wifil *m_engine;
   nsgpu_sim *m_rt;
 };

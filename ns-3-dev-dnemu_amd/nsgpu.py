@@ -35,6 +35,19 @@ class LossChain(C.Structure):
     _fields_ = [("n", C.c_int32), ("pad_", C.c_int32), ("m", LossModel * 4)]
 
 
+class LossxModel(C.Structure):  # nsgpu_lossx_model
+    _fields_ = [("kind", C.c_int32), ("pad_", C.c_int32), ("p", C.c_double * 8)]
+
+
+class LossxEntry(C.Structure):  # nsgpu_lossx_entry: MatrixPropagationLossModel::SetLoss (a, b, loss_db, false), phy indices
+    _fields_ = [("a", C.c_uint32), ("b", C.c_uint32), ("loss_db", C.c_double)]
+
+
+class Lossx(C.Structure):  # nsgpu_lossx
+    _fields_ = [("n", C.c_int32), ("pad_", C.c_int32), ("m", LossxModel * 4), ("entry", C.c_void_p),
+                ("n_entry", C.c_uint64)]
+
+
 class HoldStats(C.Structure):
     _fields_ = [("dispatched", C.c_uint64), ("holds", C.c_uint64), ("final_ts", C.c_uint64),
                 ("digest", C.c_uint64), ("rounds", C.c_uint64), ("max_batch", C.c_uint32),
@@ -47,6 +60,8 @@ RX_RECORD_DTYPE = np.dtype([("ts", "<u8"), ("uid", "<u4"), ("context", "<u4"), (
                             ("pad_", "<u4"), ("rx_dbm", "<f8")])
 
 LOSS_NONE, LOSS_LOG_DISTANCE, LOSS_FRIIS, LOSS_FIXED_RSS, LOSS_RANGE = 0, 1, 2, 3, 4
+# the extended chain's further kinds (nsgpu_lossx_kind; 0-4 are the LOSS_* above)
+LOSSX_TWO_RAY_GROUND, LOSSX_THREE_LOG, LOSSX_MATRIX = 5, 6, 7
 
 # symbol -> (restype, argtypes); the list is also what tests check the .so exports.
 _vp, _i64, _u64, _u32, _i32, _d = C.c_void_p, C.c_int64, C.c_uint64, C.c_uint32, C.c_int32, C.c_double
@@ -194,6 +209,9 @@ SIGNATURES = {
     "nsgpu_wifil_get_channel": (C.c_int, [_vp, _u32, _vp]),
     "nsgpu_sim_wifi_set_channel": (C.c_int, [_vp, _u32, _u32, C.c_int64, _vp]),
     "nsgpu_sim_wifi_get_channel": (C.c_int, [_vp, _u32, _vp]),
+    "nsgpu_wifil_set_loss": (C.c_int, [_vp, _vp]),
+    "nsgpu_sim_wifi_set_loss": (C.c_int, [_vp, _vp]),
+    "nsgpu_lossx_calc": (C.c_int, [_vp, _u32, _u32, _vp, _vp, _d, _vp]),
     "nsgpu_p2p_group_create": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_void_p)]),
     "nsgpu_p2p_group_reset": (C.c_int, [_vp, _vp]),
     "nsgpu_p2p_group_run": (C.c_int, [_vp, _vp]),
@@ -348,6 +366,39 @@ def loss_chain(*models):
     for i, (k, a, b, c) in enumerate(models):
         ch.m[i].kind, ch.m[i].p0, ch.m[i].p1, ch.m[i].p2 = k, a, b, c
     return ch
+
+
+def lossx(*links, entries=()):
+    """An extended loss chain (nsgpu_lossx) for LoopPhy.set_loss / Sim.wifi_set_loss / lossx_calc: links are
+    (kind, p0, p1, ...) tuples — LOSS_* kinds with their three parameters, LOSSX_TWO_RAY_GROUND (lambda, system loss,
+    min distance, HeightAboveZ), LOSSX_THREE_LOG (distance0..2, exponent0..2, reference loss), LOSSX_MATRIX
+    (DefaultLoss) — and entries the Matrix link's (a, b, loss_db) triples (phy indices; a symmetric SetLoss is two;
+    a later duplicate wins).  The structure keeps its entry array alive."""
+    lx = Lossx()
+    lx.n = len(links)
+    if len(links) > 4:
+        raise ValueError("at most 4 links (NSGPU_MAX_LOSS_CHAIN)")
+    for i, link in enumerate(links):
+        lx.m[i].kind = int(link[0])
+        for q, v in enumerate(link[1:]):
+            lx.m[i].p[q] = float(v)
+    entries = list(entries)
+    arr = (LossxEntry * max(len(entries), 1))()
+    for i, (a, b, loss_db) in enumerate(entries):
+        arr[i].a, arr[i].b, arr[i].loss_db = int(a), int(b), float(loss_db)
+    lx._entries = arr
+    lx.entry = C.addressof(arr) if entries else None
+    lx.n_entry = len(entries)
+    return lx
+
+
+def lossx_calc(lx, a, b, pa, pb, tx_dbm):
+    """CalcRxPower (tx_dbm, a, b) over an extended chain on the host (nsgpu_lossx_calc; no GPU): phy a at pa sends,
+    phy b at pb receives; dBm."""
+    out = C.c_double()
+    check(lib().nsgpu_lossx_calc(C.byref(lx), a, b, (C.c_double * 3)(*pa), (C.c_double * 3)(*pb), float(tx_dbm),
+                                 C.byref(out)))
+    return out.value
 
 
 # ---------------- operations ----------------
@@ -800,6 +851,11 @@ class Sim:
         if out.outcome == wifi.SWITCH_POSTPONED:
             self.schedule(out.retry_delay, lambda: self.wifi_set_channel(phy, nch, delay_ns))
         return out.outcome, out.prev_state, out.retry_delay
+
+    def wifi_set_loss(self, lx):
+        """The attached PHY's loss chain from now on (nsgpu_sim_wifi_set_loss): a nsgpu.lossx (...) — the running
+        closure's earlier sends keep theirs — or None: the config's chain again."""
+        check(lib().nsgpu_sim_wifi_set_loss(self.h, None if lx is None else C.byref(lx)))
 
     def wifi_get_channel(self, phy):
         """`phy`'s channel record (nsgpu_sim_wifi_get_channel): dict of channel, start_switching, end_switching,

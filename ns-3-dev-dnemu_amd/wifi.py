@@ -484,6 +484,11 @@ class LoopPhy:
         nsgpu.check(nsgpu.lib().nsgpu_wifil_get_channel(self.h, phy, C.byref(out)))
         return channel_record(out)
 
+    def set_loss(self, lx):
+        """The loss chain of every later SendPacket (nsgpu_wifil_set_loss): a nsgpu.lossx (...) — TwoRayGround,
+        ThreeLogDistance and Matrix links next to the config's kinds — or None: the config's chain again."""
+        nsgpu.check(nsgpu.lib().nsgpu_wifil_set_loss(self.h, None if lx is None else C.byref(lx)))
+
     def read_notes(self):
         """The notes of the epochs advanced since the last call (WIFIL_NOTE_DTYPE, (ts, uid) order)."""
         n = C.c_uint64()
