@@ -237,6 +237,46 @@ int nsgpu_wifil_set_velocity(nsgpu_wifil *h, uint64_t now, uint32_t phy, const d
 int nsgpu_wifil_pause(nsgpu_wifil *h, uint64_t now, uint32_t phy, uint32_t paused);
 int nsgpu_wifil_set_position_at(nsgpu_wifil *h, uint64_t now, uint32_t phy, double x, double y, double z);
 int nsgpu_wifil_get_mobility(nsgpu_wifil *h, uint64_t now, uint32_t phy, nsgpu_mobility *out);
+/* Waypoint and ConstantAcceleration mobility on the device: the reference's two other deterministic models
+ * (waypoint-mobility-model.cc, constant-acceleration-mobility-model.cc), which draw no random numbers.  A phy has at
+ * most one model — constant velocity (above), waypoint or acceleration — and installing one replaces whatever it
+ * had.  The phys that update at a SendPacket are the same as above; a waypoint phy runs WaypointMobilityModel::Update
+ * (:114-173) there — its whole list is on the device, so a path of any number of legs needs no host call — and an
+ * acceleration phy DoGetPosition (:51-58: base + v t + a t^2 / 2 from m_baseTime, nothing accumulates).  A run with
+ * neither model launches the kernels it launched without this interface.  Every call runs in stream order with the
+ * sends, after the closure's earlier sends:
+ *   set_waypoints   a fresh WaypointMobilityModel after AddWaypoint (wp[0]) ... AddWaypoint (wp[n - 1]) (:82-100):
+ *                   m_current = m_next = wp[0] — the phy is at wp[0].pos at once — and the rest queued.  Times
+ *                   strictly ascending, else NSGPU_EINVAL with nothing touched (the reference aborts).  n == 0
+ *                   removes the model: a constant position where the last update left the phy;
+ *   add_waypoint    AddWaypoint at run time.  A time not above the last one added since the install (or since
+ *                   end_waypoints, after which any time starts a new path): NSGPU_EINVAL, nothing touched;
+ *   end_waypoints   EndMobility (:203-209): the queue cleared, m_current.time = m_next.time = 0, m_first = true;
+ *   get_waypoints   Update at now, then m_current, m_next, m_velocity, m_first and WaypointsLeft ().  The velocity
+ *                   is the one that Update left (DoGetVelocity makes none of its own, :211-214);
+ *   set_acceleration                installs *a (pos / vel / acc / base_time); NULL removes the model likewise;
+ *   set_velocity_and_acceleration   SetVelocityAndAcceleration (:70-78): m_basePosition = DoGetPosition (),
+ *                                   m_baseTime = now, then the two vectors;
+ *   get_acceleration                the base fields, and DoGetPosition () / DoGetVelocity () at now (computed, no
+ *                                   state changes);
+ *   set_position_at (above)         on a waypoint phy DoSetPosition (:181-201, InitialPositionIsWaypoint false):
+ *                                   Update, m_current.time = max (now, m_next.time), the position, m_velocity = 0
+ *                                   — the phy sits there until m_next.time and then jumps to m_next; on an
+ *                                   acceleration phy DoSetPosition (:61-67): m_baseVelocity = DoGetVelocity (),
+ *                                   m_baseTime = now, the position; the acceleration is kept.
+ * add_waypoint / end_waypoints / get_waypoints on a phy without a waypoint model, set_velocity_and_acceleration /
+ * get_acceleration on one without an acceleration model, set_velocity / pause / get_mobility on a phy with either
+ * (it has no constant-velocity model) and the untimed nsgpu_wifil_set_position on a phy with either: NSGPU_ESTATE.
+ * phy >= n_phy: NSGPU_EINVAL before anything is sized.  A partitioned handle refuses set_waypoints and
+ * set_acceleration with NSGPU_EINVAL. */
+int nsgpu_wifil_set_waypoints(nsgpu_wifil *h, uint32_t phy, const nsgpu_waypoint *wp, uint64_t n);
+int nsgpu_wifil_add_waypoint(nsgpu_wifil *h, uint32_t phy, const nsgpu_waypoint *wp);
+int nsgpu_wifil_end_waypoints(nsgpu_wifil *h, uint32_t phy);
+int nsgpu_wifil_get_waypoints(nsgpu_wifil *h, uint64_t now, uint32_t phy, nsgpu_waypoint_state *out);
+int nsgpu_wifil_set_acceleration(nsgpu_wifil *h, uint32_t phy, const nsgpu_accel *a);
+int nsgpu_wifil_set_velocity_and_acceleration(nsgpu_wifil *h, uint64_t now, uint32_t phy, const double v[3],
+                                              const double a[3]);
+int nsgpu_wifil_get_acceleration(nsgpu_wifil *h, uint64_t now, uint32_t phy, nsgpu_accel *out);
 /* Channel switching on the device: YansWifiPhy::SetChannelNumber (nch) of phy from the host closure running at `now`
  * (yans-wifi-phy.cc:327-374), in stream order with the sends and after every earlier send of the closure.
  * switch_delay_ns is the ChannelSwitchDelay attribute (an argument: nsgpu_wifil_config is the oracle's too).  The
@@ -475,6 +515,15 @@ int nsgpu_sim_wifi_set_mobility(nsgpu_sim *s, uint32_t phy, const nsgpu_mobility
 int nsgpu_sim_wifi_set_velocity(nsgpu_sim *s, uint32_t phy, const double v[3]);
 int nsgpu_sim_wifi_pause(nsgpu_sim *s, uint32_t phy, uint32_t paused);
 int nsgpu_sim_wifi_get_mobility(nsgpu_sim *s, uint32_t phy, nsgpu_mobility *out);
+/* waypoint and acceleration mobility of the attached PHY's phys (nsgpu_wifil_set_waypoints and its neighbours) from
+ * the running closure, the timed ones at Now () */
+int nsgpu_sim_wifi_set_waypoints(nsgpu_sim *s, uint32_t phy, const nsgpu_waypoint *wp, uint64_t n);
+int nsgpu_sim_wifi_add_waypoint(nsgpu_sim *s, uint32_t phy, const nsgpu_waypoint *wp);
+int nsgpu_sim_wifi_end_waypoints(nsgpu_sim *s, uint32_t phy);
+int nsgpu_sim_wifi_get_waypoints(nsgpu_sim *s, uint32_t phy, nsgpu_waypoint_state *out);
+int nsgpu_sim_wifi_set_acceleration(nsgpu_sim *s, uint32_t phy, const nsgpu_accel *a);
+int nsgpu_sim_wifi_set_velocity_and_acceleration(nsgpu_sim *s, uint32_t phy, const double v[3], const double a[3]);
+int nsgpu_sim_wifi_get_acceleration(nsgpu_sim *s, uint32_t phy, nsgpu_accel *out);
 /* YansWifiPhy::SetChannelNumber of the attached PHY's phy from the running closure (nsgpu_wifil_set_channel at
  * Now ()).  NSGPU_WIFIL_SWITCH_POSTPONED: the caller schedules its retry closure after out->retry_delay, as ns-3's
  * Simulator::Schedule (GetDelayUntilIdle (), &SetChannelNumber, this, nch) — the closure and its uid are the

@@ -457,6 +457,36 @@ typedef struct nsgpu_lossx {
   uint64_t n_entry;
 } nsgpu_lossx;
 
+/* The closed-loop PHY's two other deterministic mobility models (nsgpu_wifil_set_waypoints / _set_acceleration and
+ * their neighbours); nsgpu_mobility above keeps its layout and its calls.
+ *
+ * Waypoint (src/mobility/model/waypoint.h): a time in ns and a position. */
+typedef struct nsgpu_waypoint {
+  uint64_t time;           /* ns */
+  double pos[3];
+} nsgpu_waypoint;          /* 32 bytes */
+/* What nsgpu_wifil_get_waypoints returns: WaypointMobilityModel's members after the Update of a position read
+ * (waypoint-mobility-model.h: m_current, m_next, m_velocity, m_first; WaypointsLeft ()).  m_next.time is signed in
+ * the reference: Update sets it to Seconds (-1) when the list has run out (:134), which next_ended carries. */
+typedef struct nsgpu_waypoint_state {
+  uint64_t cur_time;       /* m_current.time, ns */
+  double cur_pos[3];       /* m_current.position: the phy's position */
+  uint64_t next_time;      /* m_next.time, ns (0 when next_ended) */
+  double next_pos[3];      /* m_next.position */
+  double vel[3];           /* m_velocity, as the position's Update left it (DoGetVelocity makes no Update, :211-214) */
+  uint32_t next_ended;     /* 1: m_next.time == Seconds (-1) */
+  uint32_t first;          /* m_first: set again by EndMobility */
+  uint32_t left, pad_;     /* WaypointsLeft (): m_waypoints.size () */
+} nsgpu_waypoint_state;    /* 104 bytes */
+/* ConstantAccelerationMobilityModel's members (constant-acceleration-mobility-model.h).  set_acceleration reads
+ * pos / vel / acc / base_time as m_basePosition / m_baseVelocity / m_acceleration / m_baseTime; get_acceleration
+ * returns the same four and, in now_pos / now_vel, DoGetPosition () / DoGetVelocity () at the call's `now`. */
+typedef struct nsgpu_accel {
+  double pos[3], vel[3], acc[3];
+  int64_t base_time;       /* ns */
+  double now_pos[3], now_vel[3];   /* (get only; ignored by set) */
+} nsgpu_accel;             /* 128 bytes */
+
 #ifdef __cplusplus
 }
 #endif

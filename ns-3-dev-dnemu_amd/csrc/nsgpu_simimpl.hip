@@ -791,6 +791,38 @@ int nsgpu_sim_wifi_get_mobility(nsgpu_sim *s, uint32_t phy, nsgpu_mobility *out)
   if (!s || !s->wifi) return set_error(NSGPU_ESTATE, "nsgpu_sim_wifi_get_mobility: no Wi-Fi PHY attached");
   return nsgpu_wifil_get_mobility(s->wifi, s->cur_ts, phy, out);
 }
+// Waypoint and acceleration mobility of the attached PHY's phys from the running closure (the timed calls at Now).
+#define NSGPU_SIM_WIFI(name) \
+  if (!s || !s->wifi) return set_error(NSGPU_ESTATE, "nsgpu_sim_wifi_" name ": no Wi-Fi PHY attached")
+int nsgpu_sim_wifi_set_waypoints(nsgpu_sim *s, uint32_t phy, const nsgpu_waypoint *wp, uint64_t n) {
+  NSGPU_SIM_WIFI("set_waypoints");
+  return nsgpu_wifil_set_waypoints(s->wifi, phy, wp, n);
+}
+int nsgpu_sim_wifi_add_waypoint(nsgpu_sim *s, uint32_t phy, const nsgpu_waypoint *wp) {
+  NSGPU_SIM_WIFI("add_waypoint");
+  return nsgpu_wifil_add_waypoint(s->wifi, phy, wp);
+}
+int nsgpu_sim_wifi_end_waypoints(nsgpu_sim *s, uint32_t phy) {
+  NSGPU_SIM_WIFI("end_waypoints");
+  return nsgpu_wifil_end_waypoints(s->wifi, phy);
+}
+int nsgpu_sim_wifi_get_waypoints(nsgpu_sim *s, uint32_t phy, nsgpu_waypoint_state *out) {
+  NSGPU_SIM_WIFI("get_waypoints");
+  return nsgpu_wifil_get_waypoints(s->wifi, s->cur_ts, phy, out);
+}
+int nsgpu_sim_wifi_set_acceleration(nsgpu_sim *s, uint32_t phy, const nsgpu_accel *a) {
+  NSGPU_SIM_WIFI("set_acceleration");
+  return nsgpu_wifil_set_acceleration(s->wifi, phy, a);
+}
+int nsgpu_sim_wifi_set_velocity_and_acceleration(nsgpu_sim *s, uint32_t phy, const double v[3], const double a[3]) {
+  NSGPU_SIM_WIFI("set_velocity_and_acceleration");
+  return nsgpu_wifil_set_velocity_and_acceleration(s->wifi, s->cur_ts, phy, v, a);
+}
+int nsgpu_sim_wifi_get_acceleration(nsgpu_sim *s, uint32_t phy, nsgpu_accel *out) {
+  NSGPU_SIM_WIFI("get_acceleration");
+  return nsgpu_wifil_get_acceleration(s->wifi, s->cur_ts, phy, out);
+}
+#undef NSGPU_SIM_WIFI
 
 // YansWifiPhy::SetChannelNumber of `phy` from the running closure (at Now).  A postponed switch (the phy
 // transmits) is reported with its delay: the retry is a closure of the caller's, scheduled by the caller.

@@ -32,6 +32,7 @@
 #include <vector>
 #include "nsgpu_device.h"
 #include "nsgpu_internal.h"
+#include "nsgpu_waypool.h"
 
 namespace nsgpu {
 namespace {
@@ -101,6 +102,20 @@ struct WMob {  // a phy's ConstantVelocityHelper (constant-velocity-helper.h) ne
   uint32_t flags, pad;   // MOB_ON: a model is installed (clear: a constant-position phy); MOB_PAUSED: m_paused
 };
 constexpr uint32_t MOB_ON = 1, MOB_PAUSED = 2;
+struct WPath {  // a phy's WaypointMobilityModel or ConstantAccelerationMobilityModel (kind) next to its position
+  uint32_t kind, first;    // PATH_NONE / PATH_WAY / PATH_ACC; waypoint: m_first
+  uint32_t off, head, cnt, pad;  // waypoint: m_waypoints is D.wpool[off + head, off + cnt) (the pop advances head)
+  int64_t cur_t, next_t;   // waypoint: m_current.time, m_next.time (signed: Seconds (-1) ends the path); acceleration:
+                           //   m_baseTime in cur_t
+  double p[3], v[3], a[3];  // waypoint: m_next.position, m_velocity (m_current.position is D.x / y / z);
+                            //   acceleration: m_basePosition, m_baseVelocity, m_acceleration
+};
+constexpr uint32_t PATH_NONE = 0, PATH_WAY = 1, PATH_ACC = 2;
+constexpr int64_t WAY_ENDED = -1000000000;  // Seconds (-1.0)
+constexpr int WP_CHUNK = 8;
+struct WpChunk {  // waypoints carried to the pool as a kernel argument (k_wl_wput): no staging buffer to outlive
+  nsgpu_waypoint w[WP_CHUNK];
+};
 struct LCk {  // one chunk of an EndReceive's CalculatePer walk, evaluated by k_wl_mid: the noise before it,
   double noise;  // and (duration << 1) | (1: the PLCP header mode)
   int64_t dm;
@@ -174,6 +189,11 @@ struct WDev {
   // the extended loss chain (nsgpu_wifil_set_loss): null until one is installed; only k_wl_send<true> / k_wl_rx<true>,
   // launched while one is, read it
   const LossX *lx;
+  // waypoint / acceleration mobility (nsgpu_wifil_set_waypoints / _set_acceleration): a record per phy and the one
+  // pool every phy's waypoint list lives in, null until the first install of either; only k_wl_move<true>, launched
+  // while some phy has such a model, and the one-thread host calls read them
+  WPath *path;
+  nsgpu_waypoint *wpool;
 };
 // The epoch's dispatched events are appended to EV_STRIPES lists (phy j's to stripe j % EV_STRIPES): one
 // counter a phy's event would serialize ~10^4 atomics an epoch on one line.
@@ -370,6 +390,78 @@ __device__ __forceinline__ void mob_update(const WDev &D, int64_t j, int64_t now
   x[j] += m.vx * deltaS;
   y[j] += m.vy * deltaS;
   z[j] += m.vz * deltaS;
+}
+// WaypointMobilityModel::Update (waypoint-mobility-model.cc:114-173) of phy j at `now`, statement by statement
+// (NotifyCourseChange has no listener here).  m_current.position is D.x / y / z [j]; the divisions are IEEE double
+// divisions, the products and sums round one by one.  One call may cross several waypoints: the loop pops at most
+// the queue's length.
+__device__ __forceinline__ void way_update(const WDev &D, int64_t j, int64_t now) {
+  WPath &m = D.path[j];
+  int64_t cur_t = m.cur_t, next_t = m.next_t;
+  if (now < cur_t) return;                                     // :119-122
+  double *const x = const_cast<double *>(D.x), *const y = const_cast<double *>(D.y), *const z = const_cast<double *>(D.z);
+  double cx = x[j], cy = y[j], cz = z[j];
+  double nx = m.p[0], ny = m.p[1], nz = m.p[2], vx = m.v[0], vy = m.v[1], vz = m.v[2];
+  uint32_t head = m.head;
+  const uint32_t cnt = m.cnt;
+  bool done = false;
+  while (now >= next_t) {                                      // :124
+    if (head == cnt) {                                         // :126 m_waypoints.empty ()
+      if (cur_t <= next_t) {                                   // :128 ('<=': a path of one waypoint)
+        next_t = WAY_ENDED;                                    // :134
+        cx = nx, cy = ny, cz = nz;                             // :135
+        cur_t = now;                                           // :136
+        vx = vy = vz = 0.0;                                    // :137
+      } else {
+        cur_t = now;                                           // :142
+      }
+      done = true;                                             // :145 return
+      break;
+    }
+    cur_t = next_t, cx = nx, cy = ny, cz = nz;                 // :148 m_current = m_next
+    const nsgpu_waypoint w = D.wpool[m.off + head];            // :149-150 front (), pop_front ()
+    head++;
+    next_t = (int64_t)w.time, nx = w.pos[0], ny = w.pos[1], nz = w.pos[2];
+    const double t_span = get_seconds(D, next_t - cur_t);      // :153
+    vx = (nx - cx) / t_span;                                   // :155-157
+    vy = (ny - cy) / t_span;
+    vz = (nz - cz) / t_span;
+  }
+  if (!done && now > cur_t) {                                  // :160
+    const double t_diff = get_seconds(D, now - cur_t);         // :162
+    cx += vx * t_diff;                                         // :163-165
+    cy += vy * t_diff;
+    cz += vz * t_diff;
+    cur_t = now;                                               // :166
+  }
+  x[j] = cx, y[j] = cy, z[j] = cz;
+  m.cur_t = cur_t, m.next_t = next_t, m.head = head;
+  m.p[0] = nx, m.p[1] = ny, m.p[2] = nz, m.v[0] = vx, m.v[1] = vy, m.v[2] = vz;
+}
+// ConstantAccelerationMobilityModel::DoGetPosition / DoGetVelocity (constant-acceleration-mobility-model.cc:41-58)
+// of phy j's record at `now`: (base + v t) + a (t t 0.5), each product and sum rounded.
+__device__ __forceinline__ void acc_position(const WDev &D, const WPath &m, int64_t now, double out[3]) {
+  const double t = get_seconds(D, now - m.cur_t);
+  const double half_t_square = t * t * 0.5;
+  for (int c = 0; c < 3; c++) out[c] = m.p[c] + m.v[c] * t + m.a[c] * half_t_square;
+}
+__device__ __forceinline__ void acc_velocity(const WDev &D, const WPath &m, int64_t now, double out[3]) {
+  const double t = get_seconds(D, now - m.cur_t);
+  for (int c = 0; c < 3; c++) out[c] = m.v[c] + m.a[c] * t;
+}
+// A waypoint or acceleration phy's position read at a send.  An acceleration phy stores nothing but the position it
+// evaluated: on another channel than the sender's its D.x / y / z stay stale, which nobody reads until the phy is
+// next on a sender's channel, and this rewrites them then (nsgpu_wifil_get_acceleration computes, it never reads
+// them).
+__device__ __forceinline__ void path_update(const WDev &D, int64_t j, int64_t now) {
+  const WPath &m = D.path[j];
+  if (m.kind == PATH_WAY) {
+    way_update(D, j, now);
+  } else {
+    double p[3];
+    acc_position(D, m, now, p);
+    const_cast<double *>(D.x)[j] = p[0], const_cast<double *>(D.y)[j] = p[1], const_cast<double *>(D.z)[j] = p[2];
+  }
 }
 // InterferenceHelper::CalculateChunkSuccessRate — interference-helper.cc:244-255
 __device__ double chunk(const WDev &D, double snir, int64_t duration, const Mode &m) {
@@ -1432,12 +1524,118 @@ __global__ __launch_bounds__(256) void k_wl_rx(const WDev D, LRx *row, LTx t, ui
 // sender when there is at least one of them (upd_sender; its later updates of the same send have a zero delta);
 // phys on other channels keep their m_lastUpdate.  One lane per phy, launched ahead of the send's k_wl_rx — whose
 // every lane reads the sender's position, so the update is not made in place there — and only while some phy has
-// a model: a run without one launches k_wl_rx alone, as before.
+// a model: a run without one launches k_wl_rx alone, as before.  PX: some phy has a waypoint or acceleration model
+// (D.path is sized); its lane runs that model's Update / DoGetPosition in place of mob_update.  <false>, launched
+// while no phy has one, is the kernel as it was.
+template <bool PX>
 __global__ __launch_bounds__(256) void k_wl_move(const WDev D, uint32_t s, int64_t now, uint32_t upd_sender) {
   const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (j >= D.nphy) return;
   if (j == (int64_t)s ? !upd_sender : D.chan[j] != D.chan[s]) return;
+  if constexpr (PX) {
+    if (D.path[j].kind != PATH_NONE) {
+      path_update(D, j, now);
+      return;
+    }
+  }
   mob_update(D, j, now);
+}
+// Waypoints into the pool, in stream order: behind every kernel that may read the segment's old count, ahead of the
+// k_wl_path call that publishes the new one.
+__global__ void k_wl_wput(nsgpu_waypoint *dst, WpChunk c, uint32_t n) {
+  if (threadIdx.x < n) dst[threadIdx.x] = c.w[threadIdx.x];
+}
+// A host call on one phy's waypoint or acceleration model (one thread, in stream order with the sends, as k_wl_mob).
+//   PATH_WAY_INSTALL  a fresh model after AddWaypoint (a.w) and `cnt` more queued at D.wpool[off, off + cnt)
+//                     (waypoint-mobility-model.cc:82-100: m_first = false, m_current = m_next = waypoint)
+//   PATH_WAY_ADD      AddWaypoint: the first of a path (m_first) as above, else the slot cnt - 1 of the segment — now
+//                     at `off` — is the new back of the queue
+//   PATH_WAY_END      EndMobility (:203-209); Time (numeric_limits<uint64_t>::infinity ()) is Time (0)
+//   PATH_WAY_GET      Update, then the members; PATH_SET_POSITION: either model's DoSetPosition
+//   PATH_ACC_INSTALL / PATH_ACC_SET (SetVelocityAndAcceleration, :70-78) / PATH_ACC_GET;  PATH_REMOVE
+enum PathOp : uint32_t { PATH_WAY_INSTALL, PATH_WAY_ADD, PATH_WAY_END, PATH_WAY_GET, PATH_SET_POSITION, PATH_ACC_INSTALL,
+                         PATH_ACC_SET, PATH_ACC_GET, PATH_REMOVE };
+struct PathArg {
+  nsgpu_waypoint w;     // INSTALL / ADD: the waypoint; SET_POSITION: w.pos
+  double v[3], a[3];    // ACC_INSTALL / ACC_SET
+  int64_t base_time;    // ACC_INSTALL
+  uint32_t off, cnt;    // the waypoint segment's place and the slots written
+};
+union PathOut {
+  nsgpu_waypoint_state way;
+  nsgpu_accel acc;
+};
+__global__ void k_wl_path(const WDev D, uint32_t op, uint32_t j, int64_t now, PathArg a, PathOut *out) {
+  WPath &m = D.path[j];
+  double *const x = const_cast<double *>(D.x), *const y = const_cast<double *>(D.y), *const z = const_cast<double *>(D.z);
+  switch (op) {
+    case PATH_WAY_INSTALL:
+      m = WPath{};
+      m.kind = PATH_WAY, m.first = 1;
+      [[fallthrough]];
+    case PATH_WAY_ADD:
+      m.off = a.off, m.cnt = a.cnt;
+      if (m.first) {  // :84-88
+        m.first = 0;
+        m.cur_t = m.next_t = (int64_t)a.w.time;
+        x[j] = m.p[0] = a.w.pos[0], y[j] = m.p[1] = a.w.pos[1], z[j] = m.p[2] = a.w.pos[2];
+      }
+      break;
+    case PATH_WAY_END:
+      m.head = m.cnt;  // m_waypoints.clear ()
+      m.cur_t = m.next_t = 0;
+      m.first = 1;
+      break;
+    case PATH_WAY_GET: {
+      way_update(D, j, now);
+      nsgpu_waypoint_state &o = out->way;
+      const bool ended = m.next_t == WAY_ENDED;
+      o = nsgpu_waypoint_state{(uint64_t)m.cur_t, {x[j], y[j], z[j]}, ended ? 0ull : (uint64_t)m.next_t,
+                               {m.p[0], m.p[1], m.p[2]}, {m.v[0], m.v[1], m.v[2]}, ended ? 1u : 0u, m.first,
+                               m.cnt - m.head, 0};
+      break;
+    }
+    case PATH_SET_POSITION:
+      if (m.kind == PATH_WAY) {  // DoSetPosition (:181-201), m_initialPositionIsWaypoint false
+        way_update(D, j, now);
+        m.cur_t = now > m.next_t ? now : m.next_t;
+        m.v[0] = m.v[1] = m.v[2] = 0.0;
+      } else {  // DoSetPosition (constant-acceleration-mobility-model.cc:61-67)
+        double v[3];
+        acc_velocity(D, m, now, v);
+        m.v[0] = v[0], m.v[1] = v[1], m.v[2] = v[2];
+        m.cur_t = now;
+        m.p[0] = a.w.pos[0], m.p[1] = a.w.pos[1], m.p[2] = a.w.pos[2];
+      }
+      x[j] = a.w.pos[0], y[j] = a.w.pos[1], z[j] = a.w.pos[2];
+      break;
+    case PATH_ACC_INSTALL:
+      m = WPath{};
+      m.kind = PATH_ACC;
+      m.cur_t = a.base_time;
+      for (int c = 0; c < 3; c++) m.p[c] = a.w.pos[c], m.v[c] = a.v[c], m.a[c] = a.a[c];
+      break;
+    case PATH_ACC_SET: {
+      double p[3];
+      acc_position(D, m, now, p);
+      m.cur_t = now;
+      for (int c = 0; c < 3; c++) m.p[c] = p[c], m.v[c] = a.v[c], m.a[c] = a.a[c];
+      break;
+    }
+    case PATH_ACC_GET: {
+      nsgpu_accel &o = out->acc;
+      for (int c = 0; c < 3; c++) o.pos[c] = m.p[c], o.vel[c] = m.v[c], o.acc[c] = m.a[c];
+      o.base_time = m.cur_t;
+      acc_position(D, m, now, o.now_pos);
+      acc_velocity(D, m, now, o.now_vel);
+      break;
+    }
+    default: {  // PATH_REMOVE: a constant position where the last update left the phy
+      const uint32_t off = m.off;  // (the segment stays the phy's)
+      m = WPath{};
+      m.off = off;
+    }
+  }
 }
 // A host call on one phy's model, in stream order with the sends (one thread, as k_wl_set):
 // install / remove (nsgpu_wifil_set_mobility), ConstantVelocityMobilityModel::SetVelocity
@@ -1667,6 +1865,14 @@ struct nsgpu_wifil {
   std::vector<uint8_t> mob_on;
   uint64_t n_mob = 0;
   nsgpu_mobility *d_mobout = nullptr;
+  // waypoint / acceleration mobility: every phy's model kind (PATH_*; their count picks k_wl_move's instantiation),
+  // the waypoint phys' lists and segments of the pool D.wpool (nsgpu_waypool.h; the pool is not in `allocs`: it is
+  // replaced when it grows), and the device word the two reads come back through
+  std::vector<uint8_t> path_kind;
+  uint64_t n_path = 0;
+  std::vector<WaySeg> seg;
+  WayPool wpool;
+  PathOut *d_pathout = nullptr;
   // channel switching (nsgpu_wifil_set_channel): every phy's current channel number (the receiver counts in `recv`
   // follow it), the switches made (non-zero: the epochs launch the SW instantiation) and k_wl_rechan's count word
   // (allocated at the first call)
@@ -1746,6 +1952,7 @@ extern "C" int nsgpu_wifil_destroy(nsgpu_wifil *h) {
   }
   if (h->h_digtot) (void)hipHostFree(h->h_digtot);
   for (void *p : h->allocs) (void)hipFree(p);
+  if (h->D.wpool) (void)hipFree(h->D.wpool);
   if (h->lx_dev) (void)hipFree(h->lx_dev);
   if (h->lx_pin) (void)hipHostFree(h->lx_pin);
   if (h->lx_up) (void)hipEventDestroy(h->lx_up);
@@ -1990,14 +2197,15 @@ static int wl_queue_send(nsgpu_wifil *h, const LTx &t, double dbm, uint32_t uid_
     int rcf = wl_flush_sends(h);
     if (rcf) return rcf;
   }
-  if (h->n_mob) {
+  if (h->n_mob || h->n_path) {
     // Mobility and the batch: a flushed send's receptions are re-derived by k_wl_send from the positions held at
     // the flush, so the batch is flushed before anything that can change a position — this send's updates here,
     // and every nsgpu_wifil_set_mobility / _set_velocity / _pause / _set_position_at / _get_mobility (as
     // nsgpu_wifil_set_position always did).  Each send is then applied from the positions of its own send.
     if (int rcf = wl_flush_sends(h)) return rcf;
-    hipLaunchKernelGGL(k_wl_move, dim3(wl_grid(h->D.nphy, 256)), dim3(256), 0, h->s, h->D, t.phy, (int64_t)t.ts,
-                       h->recv[t.phy] ? 1u : 0u);
+    // (the waypoint / acceleration instantiation only while some phy has such a model)
+    hipLaunchKernelGGL(h->n_path ? k_wl_move<true> : k_wl_move<false>, dim3(wl_grid(h->D.nphy, 256)), dim3(256), 0, h->s, h->D,
+                       t.phy, (int64_t)t.ts, h->recv[t.phy] ? 1u : 0u);
   }
   const uint32_t k = (uint32_t)h->n_tx++;
   if (h->sb.n == 0) h->sb.k0 = k;
@@ -2161,6 +2369,8 @@ extern "C" int nsgpu_wifil_flush(nsgpu_wifil *h, uint64_t *digest) {
 }
 
 static bool wl_mobile(const nsgpu_wifil *h, uint32_t phy) { return phy < h->mob_on.size() && h->mob_on[phy]; }
+// (the phy's waypoint / acceleration model: PATH_NONE, PATH_WAY or PATH_ACC)
+static uint32_t wl_pathed(const nsgpu_wifil *h, uint32_t phy) { return phy < h->path_kind.size() ? h->path_kind[phy] : PATH_NONE; }
 
 // MobilityModel::SetPosition of `phy`'s node (mobility-model.cc SetPosition -> DoSetPosition; e.g. a host closure
 // at run time): YansWifiChannel::Send reads the positions at each send (yans-wifi-channel.cc:92-96), so the
@@ -2171,6 +2381,9 @@ extern "C" int nsgpu_wifil_set_position(nsgpu_wifil *h, uint32_t phy, double x, 
   if (wl_mobile(h, phy))
     return set_error(NSGPU_ESTATE, "nsgpu_wifil_set_position: phy %u has a constant-velocity model, whose SetPosition "
                                    "sets m_lastUpdate: use nsgpu_wifil_set_position_at", phy);
+  if (wl_pathed(h, phy))
+    return set_error(NSGPU_ESTATE, "nsgpu_wifil_set_position: phy %u has a waypoint or acceleration model, whose "
+                                   "DoSetPosition reads Now: use nsgpu_wifil_set_position_at", phy);
   if (!h->mem.empty()) {  // (every partition holds every position)
     for (nsgpu_wifil *m : h->mem)
       if (int rcm = nsgpu_wifil_set_position(m, phy, x, y, z)) return rcm;
@@ -2193,6 +2406,18 @@ static int wl_mob_op(nsgpu_wifil *h, uint32_t op, uint32_t phy, uint64_t now, co
   return NSGPU_OK;
 }
 
+// The constant-velocity records, sized at the first install of any model (k_wl_move reads them for every phy that has
+// no waypoint / acceleration model).
+static int wl_mob_size(nsgpu_wifil *h) {
+  if (!h->mob_on.empty()) return NSGPU_OK;
+  int rc = wl_alloc(h, &h->D.mob, (size_t)h->D.nphy);
+  if (!rc) rc = wl_alloc(h, &h->d_mobout, 1);
+  if (rc) return rc;
+  h->mob_on.assign((size_t)h->D.nphy, 0);
+  return NSGPU_OK;
+}
+static int wl_path_remove(nsgpu_wifil *h, uint32_t phy);
+
 // Installs ConstantVelocityHelper state on `phy` (m == NULL: removes it; the phy stays where it is, a constant
 // position again).  The records are sized at the first install, as nsgpu_wifil_notify sizes its flags.
 extern "C" int nsgpu_wifil_set_mobility(nsgpu_wifil *h, uint32_t phy, const nsgpu_mobility *m) {
@@ -2201,13 +2426,12 @@ extern "C" int nsgpu_wifil_set_mobility(nsgpu_wifil *h, uint32_t phy, const nsgp
     return set_error(NSGPU_EINVAL, "nsgpu_wifil_set_mobility: mobility is single-engine for now (a partitioned handle)");
   if (h->mob_on.empty()) {
     if (!m) return NSGPU_OK;
-    int rc = wl_alloc(h, &h->D.mob, (size_t)h->D.nphy);
-    if (!rc) rc = wl_alloc(h, &h->d_mobout, 1);
-    if (rc) return rc;
-    h->mob_on.assign((size_t)h->D.nphy, 0);
+    if (int rc = wl_mob_size(h)) return rc;
   }
   const uint8_t v = m ? 1 : 0;
   if (!v && !h->mob_on[phy]) return NSGPU_OK;
+  if (v && wl_pathed(h, phy))  // (one model per phy: this one replaces its waypoint / acceleration model)
+    if (int rc = wl_path_remove(h, phy)) return rc;
   if (int rc = wl_mob_op(h, v ? MOB_INSTALL : MOB_REMOVE, phy, 0, m ? *m : nsgpu_mobility{})) return rc;
   if (h->mob_on[phy] != v) {
     h->mob_on[phy] = v;
@@ -2215,6 +2439,8 @@ extern "C" int nsgpu_wifil_set_mobility(nsgpu_wifil *h, uint32_t phy, const nsgp
   }
   return NSGPU_OK;
 }
+
+static int wl_path_op(nsgpu_wifil *h, uint32_t op, uint32_t phy, uint64_t now, const PathArg &a);
 
 extern "C" int nsgpu_wifil_set_velocity(nsgpu_wifil *h, uint64_t now, uint32_t phy, const double v[3]) {
   if (!h || !v || phy >= h->D.nphy) return set_error(NSGPU_EINVAL, "nsgpu_wifil_set_velocity: bad phy");
@@ -2234,6 +2460,11 @@ extern "C" int nsgpu_wifil_pause(nsgpu_wifil *h, uint64_t now, uint32_t phy, uin
 
 extern "C" int nsgpu_wifil_set_position_at(nsgpu_wifil *h, uint64_t now, uint32_t phy, double x, double y, double z) {
   if (!h || phy >= h->D.nphy) return set_error(NSGPU_EINVAL, "nsgpu_wifil_set_position_at: bad phy");
+  if (wl_pathed(h, phy)) {  // (WaypointMobilityModel / ConstantAccelerationMobilityModel::DoSetPosition)
+    PathArg a{};
+    a.w.pos[0] = x, a.w.pos[1] = y, a.w.pos[2] = z;
+    return wl_path_op(h, PATH_SET_POSITION, phy, now, a);
+  }
   if (!wl_mobile(h, phy)) return nsgpu_wifil_set_position(h, phy, x, y, z);  // (ConstantPositionMobilityModel: no time)
   nsgpu_mobility a{};
   a.pos[0] = x, a.pos[1] = y, a.pos[2] = z;
@@ -2245,6 +2476,172 @@ extern "C" int nsgpu_wifil_get_mobility(nsgpu_wifil *h, uint64_t now, uint32_t p
   if (!wl_mobile(h, phy)) return set_error(NSGPU_ESTATE, "nsgpu_wifil_get_mobility: phy %u has no mobility model", phy);
   if (int rc = wl_mob_op(h, MOB_GET, phy, now, nsgpu_mobility{})) return rc;
   NSGPU_HIP(hipMemcpyAsync(out, h->d_mobout, sizeof(nsgpu_mobility), hipMemcpyDeviceToHost, h->s));
+  NSGPU_HIP(hipStreamSynchronize(h->s));
+  return NSGPU_OK;
+}
+
+// ---- waypoint and acceleration mobility ----
+// One k_wl_path call on phy's model (the batch first, as wl_mob_op).
+static int wl_path_op(nsgpu_wifil *h, uint32_t op, uint32_t phy, uint64_t now, const PathArg &a) {
+  if (int rcf = wl_flush_sends(h)) return rcf;
+  hipLaunchKernelGGL(k_wl_path, dim3(1), dim3(1), 0, h->s, h->D, op, phy, (int64_t)now, a, h->d_pathout);
+  NSGPU_HIP(hipGetLastError());
+  return NSGPU_OK;
+}
+static int wl_path_remove(nsgpu_wifil *h, uint32_t phy) {
+  if (int rc = wl_path_op(h, PATH_REMOVE, phy, 0, PathArg{})) return rc;
+  h->path_kind[phy] = PATH_NONE;
+  h->n_path--;
+  return NSGPU_OK;
+}
+// The argument checks every install call makes, then the records (sized at the first install) and the phy's other
+// model, if any, removed: one model per phy.
+static int wl_path_begin(nsgpu_wifil *h, uint32_t phy, const char *what, bool install) {
+  if (!h || phy >= h->D.nphy) return set_error(NSGPU_EINVAL, "%s: bad phy", what);  // (before anything is sized)
+  if (!h->mem.empty())
+    return set_error(NSGPU_EINVAL, "%s: mobility is single-engine for now (a partitioned handle)", what);
+  if (!install) return NSGPU_OK;
+  if (h->path_kind.empty()) {
+    int rc = wl_mob_size(h);
+    if (!rc) rc = wl_alloc(h, &h->D.path, (size_t)h->D.nphy);
+    if (!rc) rc = wl_alloc(h, &h->d_pathout, 1);
+    if (rc) return rc;
+    h->path_kind.assign((size_t)h->D.nphy, PATH_NONE);
+    h->seg.resize((size_t)h->D.nphy);
+  }
+  if (h->mob_on[phy]) {
+    if (int rc = wl_mob_op(h, MOB_REMOVE, phy, 0, nsgpu_mobility{})) return rc;
+    h->mob_on[phy] = 0;
+    h->n_mob--;
+  }
+  return NSGPU_OK;
+}
+static void wl_path_mark(nsgpu_wifil *h, uint32_t phy, uint32_t kind) {
+  if (!h->path_kind[phy]) h->n_path++;
+  h->path_kind[phy] = (uint8_t)kind;
+}
+// Room for `need` slots in phy's segment of the pool (nsgpu_waypool.h), in stream order: a full pool is replaced once
+// the stream has drained (as the Matrix table grows: rare, and not on the send path), a full segment is copied to
+// the pool's end behind every kernel that reads the old one.
+static int wl_way_reserve(nsgpu_wifil *h, WaySeg &s, uint64_t need) {
+  const uint64_t old_end = h->wpool.end;
+  const WayPlan p = h->wpool.reserve(s, need);
+  if (p.grow) {
+    nsgpu_waypoint *np = nullptr;
+    NSGPU_HIP(hipStreamSynchronize(h->s));
+    NSGPU_HIP(hipMalloc((void **)&np, p.pool_cap * sizeof(nsgpu_waypoint)));
+    if (h->D.wpool) {
+      NSGPU_HIP(hipMemcpy(np, h->D.wpool, old_end * sizeof(nsgpu_waypoint), hipMemcpyDeviceToDevice));
+      NSGPU_HIP(hipFree(h->D.wpool));
+    }
+    h->D.wpool = np;
+  }
+  if (p.move)
+    NSGPU_HIP(hipMemcpyAsync(h->D.wpool + p.off, h->D.wpool + p.old_off, (size_t)s.cnt * sizeof(nsgpu_waypoint),
+                             hipMemcpyDeviceToDevice, h->s));
+  return NSGPU_OK;
+}
+// Waypoints into the slots [at, at + n) of the pool, WP_CHUNK a launch, carried as kernel arguments.
+static int wl_way_put(nsgpu_wifil *h, uint64_t at, const nsgpu_waypoint *wp, uint64_t n) {
+  for (uint64_t i = 0; i < n; i += WP_CHUNK) {
+    WpChunk c{};
+    const uint32_t k = (uint32_t)std::min<uint64_t>(WP_CHUNK, n - i);
+    std::copy(wp + i, wp + i + k, c.w);
+    hipLaunchKernelGGL(k_wl_wput, dim3(1), dim3(WP_CHUNK), 0, h->s, h->D.wpool + at + i, c, k);
+  }
+  NSGPU_HIP(hipGetLastError());
+  return NSGPU_OK;
+}
+
+extern "C" int nsgpu_wifil_set_waypoints(nsgpu_wifil *h, uint32_t phy, const nsgpu_waypoint *wp, uint64_t n) {
+  if (int rc = wl_path_begin(h, phy, "nsgpu_wifil_set_waypoints", false)) return rc;
+  if (n && !wp) return set_error(NSGPU_EINVAL, "nsgpu_wifil_set_waypoints: null");
+  if (n > 0xffffffffull || !ascending(wp, n))
+    return set_error(NSGPU_EINVAL, "nsgpu_wifil_set_waypoints: waypoints must be given in ascending time order "
+                                   "(waypoint-mobility-model.cc:91 NS_ABORT_MSG_IF)");
+  if (n == 0) return wl_pathed(h, phy) ? wl_path_remove(h, phy) : NSGPU_OK;
+  if (int rc = wl_path_begin(h, phy, "nsgpu_wifil_set_waypoints", true)) return rc;
+  if (int rcf = wl_flush_sends(h)) return rcf;
+  WaySeg &s = h->seg[phy];
+  s.cnt = 0;  // (a fresh model: nothing of the old list moves with the segment)
+  if (int rc = wl_way_reserve(h, s, n - 1)) return rc;
+  if (int rc = wl_way_put(h, s.off, wp + 1, n - 1)) return rc;
+  s.cnt = (uint32_t)(n - 1);
+  s.first = false, s.any = true, s.last = wp[n - 1].time;
+  s.list.assign(wp, wp + n);
+  PathArg a{};
+  a.w = wp[0], a.off = (uint32_t)s.off, a.cnt = s.cnt;
+  if (int rc = wl_path_op(h, PATH_WAY_INSTALL, phy, 0, a)) return rc;
+  wl_path_mark(h, phy, PATH_WAY);
+  return NSGPU_OK;
+}
+
+extern "C" int nsgpu_wifil_add_waypoint(nsgpu_wifil *h, uint32_t phy, const nsgpu_waypoint *wp) {
+  if (!h || !wp || phy >= h->D.nphy) return set_error(NSGPU_EINVAL, "nsgpu_wifil_add_waypoint: bad phy");
+  if (wl_pathed(h, phy) != PATH_WAY) return set_error(NSGPU_ESTATE, "nsgpu_wifil_add_waypoint: phy %u has no waypoint model", phy);
+  WaySeg &s = h->seg[phy];
+  if (!s.first && s.any && wp->time <= s.last)
+    return set_error(NSGPU_EINVAL, "nsgpu_wifil_add_waypoint: waypoints must be added in ascending time order "
+                                   "(waypoint-mobility-model.cc:91 NS_ABORT_MSG_IF)");
+  if (int rcf = wl_flush_sends(h)) return rcf;
+  if (!s.first) {  // (queued: one slot, behind every kernel that may read the old count)
+    if (s.cnt == 0xffffffffu) return set_error(NSGPU_ENOMEM, "nsgpu_wifil_add_waypoint: 2^32 waypoints");
+    if (int rc = wl_way_reserve(h, s, (uint64_t)s.cnt + 1)) return rc;
+    if (int rc = wl_way_put(h, s.off + s.cnt, wp, 1)) return rc;
+    s.cnt++;
+  }
+  s.first = false, s.any = true, s.last = wp->time;
+  s.list.push_back(*wp);
+  PathArg a{};
+  a.w = *wp, a.off = (uint32_t)s.off, a.cnt = s.cnt;
+  return wl_path_op(h, PATH_WAY_ADD, phy, 0, a);
+}
+
+extern "C" int nsgpu_wifil_end_waypoints(nsgpu_wifil *h, uint32_t phy) {
+  if (!h || phy >= h->D.nphy) return set_error(NSGPU_EINVAL, "nsgpu_wifil_end_waypoints: bad phy");
+  if (wl_pathed(h, phy) != PATH_WAY) return set_error(NSGPU_ESTATE, "nsgpu_wifil_end_waypoints: phy %u has no waypoint model", phy);
+  WaySeg &s = h->seg[phy];
+  s.first = true, s.any = false;
+  return wl_path_op(h, PATH_WAY_END, phy, 0, PathArg{});
+}
+
+extern "C" int nsgpu_wifil_get_waypoints(nsgpu_wifil *h, uint64_t now, uint32_t phy, nsgpu_waypoint_state *out) {
+  if (!h || !out || phy >= h->D.nphy) return set_error(NSGPU_EINVAL, "nsgpu_wifil_get_waypoints: bad phy");
+  if (wl_pathed(h, phy) != PATH_WAY) return set_error(NSGPU_ESTATE, "nsgpu_wifil_get_waypoints: phy %u has no waypoint model", phy);
+  if (int rc = wl_path_op(h, PATH_WAY_GET, phy, now, PathArg{})) return rc;
+  NSGPU_HIP(hipMemcpyAsync(out, &h->d_pathout->way, sizeof(nsgpu_waypoint_state), hipMemcpyDeviceToHost, h->s));
+  NSGPU_HIP(hipStreamSynchronize(h->s));
+  return NSGPU_OK;
+}
+
+extern "C" int nsgpu_wifil_set_acceleration(nsgpu_wifil *h, uint32_t phy, const nsgpu_accel *acc) {
+  if (int rc = wl_path_begin(h, phy, "nsgpu_wifil_set_acceleration", false)) return rc;
+  if (!acc) return wl_pathed(h, phy) ? wl_path_remove(h, phy) : NSGPU_OK;
+  if (int rc = wl_path_begin(h, phy, "nsgpu_wifil_set_acceleration", true)) return rc;
+  PathArg a{};
+  for (int c = 0; c < 3; c++) a.w.pos[c] = acc->pos[c], a.v[c] = acc->vel[c], a.a[c] = acc->acc[c];
+  a.base_time = acc->base_time;
+  a.off = (uint32_t)h->seg[phy].off;
+  if (int rc = wl_path_op(h, PATH_ACC_INSTALL, phy, 0, a)) return rc;
+  wl_path_mark(h, phy, PATH_ACC);
+  return NSGPU_OK;
+}
+
+extern "C" int nsgpu_wifil_set_velocity_and_acceleration(nsgpu_wifil *h, uint64_t now, uint32_t phy, const double v[3],
+                                                         const double acc[3]) {
+  if (!h || !v || !acc || phy >= h->D.nphy) return set_error(NSGPU_EINVAL, "nsgpu_wifil_set_velocity_and_acceleration: bad phy");
+  if (wl_pathed(h, phy) != PATH_ACC)
+    return set_error(NSGPU_ESTATE, "nsgpu_wifil_set_velocity_and_acceleration: phy %u has no acceleration model", phy);
+  PathArg a{};
+  for (int c = 0; c < 3; c++) a.v[c] = v[c], a.a[c] = acc[c];
+  return wl_path_op(h, PATH_ACC_SET, phy, now, a);
+}
+
+extern "C" int nsgpu_wifil_get_acceleration(nsgpu_wifil *h, uint64_t now, uint32_t phy, nsgpu_accel *out) {
+  if (!h || !out || phy >= h->D.nphy) return set_error(NSGPU_EINVAL, "nsgpu_wifil_get_acceleration: bad phy");
+  if (wl_pathed(h, phy) != PATH_ACC) return set_error(NSGPU_ESTATE, "nsgpu_wifil_get_acceleration: phy %u has no acceleration model", phy);
+  if (int rc = wl_path_op(h, PATH_ACC_GET, phy, now, PathArg{})) return rc;
+  NSGPU_HIP(hipMemcpyAsync(out, &h->d_pathout->acc, sizeof(nsgpu_accel), hipMemcpyDeviceToHost, h->s));
   NSGPU_HIP(hipStreamSynchronize(h->s));
   return NSGPU_OK;
 }

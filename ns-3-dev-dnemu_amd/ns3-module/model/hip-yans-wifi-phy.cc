@@ -17,6 +17,8 @@
 #include "ns3/mobility-model.h"
 #include "ns3/constant-position-mobility-model.h"
 #include "ns3/constant-velocity-mobility-model.h"
+#include "ns3/waypoint-mobility-model.h"
+#include "ns3/constant-acceleration-mobility-model.h"
 #include "ns3/wifi-net-device.h"
 #include "ns3/node.h"
 #include "ns3/nist-error-rate-model.h"
@@ -516,6 +518,69 @@ HipWifiBinding::CalcRxPower (double txPowerDbm, uint32_t a, uint32_t b) const
   return rx;
 }
 
+// The model's own AddWaypoint first (it aborts on a time out of order, :91), then the device copies: the phys of the
+// channel that aggregate this model.  Before Attach the waypoints are kept for it.
+void
+HipWifiBinding::AddWaypoint (Ptr<Node> node, const Waypoint &waypoint)
+{
+  Ptr<WaypointMobilityModel> mob = node->GetObject<WaypointMobilityModel> ();
+  if (mob == 0)
+    {
+      NS_FATAL_ERROR ("HipWifiBinding::AddWaypoint: node " << node->GetId () << " has no WaypointMobilityModel");
+    }
+  mob->AddWaypoint (waypoint);
+  nsgpu_waypoint wp;
+  wp.time = static_cast<uint64_t> (waypoint.time.GetNanoSeconds ());
+  wp.pos[0] = waypoint.position.x, wp.pos[1] = waypoint.position.y, wp.pos[2] = waypoint.position.z;
+  m_wayFed[mob].push_back (wp);
+  for (uint32_t i = 0; m_rt != 0 && i < m_mobs.size (); i++)
+    {
+      if (m_mobs[i] == mob)
+        {
+          NSGPU_RT (nsgpu_sim_wifi_add_waypoint (m_rt, i, &wp));
+        }
+    }
+}
+
+void
+HipWifiBinding::SetVelocityAndAcceleration (Ptr<Node> node, const Vector &velocity, const Vector &acceleration)
+{
+  Ptr<ConstantAccelerationMobilityModel> mob = node->GetObject<ConstantAccelerationMobilityModel> ();
+  if (mob == 0)
+    {
+      NS_FATAL_ERROR ("HipWifiBinding::SetVelocityAndAcceleration: node " << node->GetId ()
+                      << " has no ConstantAccelerationMobilityModel");
+    }
+  const bool fed = m_accFed.find (mob) != m_accFed.end ();
+  mob->SetVelocityAndAcceleration (velocity, acceleration);
+  const Vector p = mob->GetPosition ();  // (m_basePosition: DoGetPosition () at m_baseTime = Now ())
+  nsgpu_accel a;
+  a.pos[0] = p.x, a.pos[1] = p.y, a.pos[2] = p.z;
+  a.vel[0] = velocity.x, a.vel[1] = velocity.y, a.vel[2] = velocity.z;
+  a.acc[0] = acceleration.x, a.acc[1] = acceleration.y, a.acc[2] = acceleration.z;
+  a.base_time = Simulator::Now ().GetNanoSeconds ();
+  for (int c = 0; c < 3; c++)
+    {
+      a.now_pos[c] = a.now_vel[c] = 0.0;
+    }
+  m_accFed[mob] = a;
+  for (uint32_t i = 0; m_rt != 0 && i < m_mobs.size (); i++)
+    {
+      if (m_mobs[i] != mob)
+        {
+          continue;
+        }
+      if (fed)  // (the device copy exists: its own DoGetPosition () becomes the base position, as on the host)
+        {
+          NSGPU_RT (nsgpu_sim_wifi_set_velocity_and_acceleration (m_rt, i, a.vel, a.acc));
+        }
+      else
+        {
+          NSGPU_RT (nsgpu_sim_wifi_set_acceleration (m_rt, i, &a));
+        }
+    }
+}
+
 void
 HipWifiBinding::Attach (Ptr<HipSimulatorImpl> impl, Ptr<YansWifiChannel> channel, const nsgpu_loss_chain &loss,
                         double speed, uint64_t txCap)
@@ -539,10 +604,19 @@ HipWifiBinding::Attach (Ptr<HipSimulatorImpl> impl, Ptr<YansWifiChannel> channel
         {
           moving[i] = mob;
         }
+      else if (DynamicCast<WaypointMobilityModel> (mob) != 0 && m_wayFed.find (mob) != m_wayFed.end ())
+        {
+          // (fed through AddWaypoint: its list is installed below)
+        }
+      else if (DynamicCast<ConstantAccelerationMobilityModel> (mob) != 0 && m_accFed.find (mob) != m_accFed.end ())
+        {
+          // (fed through SetVelocityAndAcceleration: its base state is installed below)
+        }
       else if (DynamicCast<ConstantPositionMobilityModel> (mob) == 0)
         {
           NS_FATAL_ERROR ("HipWifiBinding: phy " << i << "'s mobility model " << mob->GetInstanceTypeId ()
-                          << " is not on the device (ConstantPosition and ConstantVelocity are)");
+                          << " is not on the device (ConstantPosition and ConstantVelocity are; Waypoint and "
+                          "ConstantAcceleration when fed through HipWifiBinding::AddWaypoint / SetVelocityAndAcceleration)");
         }
       const Vector p = mob->GetPosition ();
       x[i] = p.x;
@@ -622,6 +696,16 @@ HipWifiBinding::Attach (Ptr<HipSimulatorImpl> impl, Ptr<YansWifiChannel> channel
           std::ostringstream os;
           os << i;
           moving[i]->TraceConnect ("CourseChange", os.str (), MakeCallback (&HipWifiBinding::CourseChange, this));
+        }
+      std::map<Ptr<MobilityModel>, std::vector<nsgpu_waypoint> >::const_iterator w = m_wayFed.find (m_mobs[i]);
+      if (w != m_wayFed.end ())
+        {
+          NSGPU_RT (nsgpu_sim_wifi_set_waypoints (m_rt, i, &w->second[0], w->second.size ()));
+        }
+      std::map<Ptr<MobilityModel>, nsgpu_accel>::const_iterator a = m_accFed.find (m_mobs[i]);
+      if (a != m_accFed.end ())
+        {
+          NSGPU_RT (nsgpu_sim_wifi_set_acceleration (m_rt, i, &a->second));
         }
     }
 }

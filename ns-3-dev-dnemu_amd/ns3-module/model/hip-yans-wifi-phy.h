@@ -36,6 +36,9 @@
 #include "ns3/object-factory.h"
 #include "ns3/packet.h"
 #include "ns3/mobility-model.h"
+#include "ns3/waypoint.h"
+#include "ns3/node.h"
+#include <map>
 #include "hip-simulator-impl.h"
 #include "nsgpu.h"
 #include <string>
@@ -122,8 +125,10 @@ public:
 
   /* After the topology is built, before Run: the channel's phys (every one a HipYansWifiPhy) on the device,
    * attached to impl's runtime.  A phy whose node aggregates a ConstantVelocityMobilityModel gets a device copy of
-   * it (nsgpu_sim_wifi_set_mobility) kept current through its CourseChange trace; a model other than
-   * ConstantPosition / ConstantVelocity is an NS_FATAL_ERROR.  YansWifiChannel keeps its loss / delay models private: the chain and the
+   * it (nsgpu_sim_wifi_set_mobility) kept current through its CourseChange trace.  A WaypointMobilityModel or a
+   * ConstantAccelerationMobilityModel is accepted for a node that was fed through AddWaypoint /
+   * SetVelocityAndAcceleration below (the stock classes expose neither the queue nor the acceleration); any other
+   * model is an NS_FATAL_ERROR.  YansWifiChannel keeps its loss / delay models private: the chain and the
    * ConstantSpeed speed are passed (DefaultLoss () is YansWifiChannelHelper::Default's, yans-wifi-helper.cc:134-140). */
   void Attach (Ptr<HipSimulatorImpl> impl, Ptr<YansWifiChannel> channel, const nsgpu_loss_chain &loss,
                double speed = 299792458.0, uint64_t txCap = 1u << 20);
@@ -146,6 +151,15 @@ public:
    * installed, on the host (nsgpu_lossx_calc) */
   double CalcRxPower (double txPowerDbm, uint32_t a, uint32_t b) const;
 
+  /* WaypointMobilityModel::AddWaypoint (waypoint) of node's model, forwarded to the model itself and to the device
+   * copy (nsgpu_sim_wifi_set_waypoints at Attach for what was added before it, nsgpu_sim_wifi_add_waypoint after):
+   * the script calls this in place of the model's own AddWaypoint, before or after Attach. */
+  void AddWaypoint (Ptr<Node> node, const Waypoint &waypoint);
+  /* ConstantAccelerationMobilityModel::SetVelocityAndAcceleration (velocity, acceleration) of node's model at Now (),
+   * forwarded the same way (nsgpu_sim_wifi_set_acceleration at Attach, nsgpu_sim_wifi_set_velocity_and_acceleration
+   * after). */
+  void SetVelocityAndAcceleration (Ptr<Node> node, const Vector &velocity, const Vector &acceleration);
+
 private:
   void IssueLoss (void);
   virtual void DoDispose (void);
@@ -165,6 +179,8 @@ private:
   std::vector<Ptr<MobilityModel> > m_mobs;        // per phy: its node's mobility model (SetMatrixLoss's keys)
   nsgpu_lossx m_lossx;                            // the extended chain in force (n = -1: Attach's chain)
   std::vector<nsgpu_lossx_entry> m_lossEntries;   // its Matrix entries, in SetLoss order
+  std::map<Ptr<MobilityModel>, std::vector<nsgpu_waypoint> > m_wayFed;  // AddWaypoint's, per model, in call order
+  std::map<Ptr<MobilityModel>, nsgpu_accel> m_accFed;   // SetVelocityAndAcceleration's last base state, per model
   nsgpu_wifil *m_engine;
   nsgpu_sim *m_rt;
 };

@@ -205,6 +205,20 @@ SIGNATURES = {
     "nsgpu_sim_wifi_set_velocity": (C.c_int, [_vp, _u32, _vp]),
     "nsgpu_sim_wifi_pause": (C.c_int, [_vp, _u32, _u32]),
     "nsgpu_sim_wifi_get_mobility": (C.c_int, [_vp, _u32, _vp]),
+    "nsgpu_wifil_set_waypoints": (C.c_int, [_vp, _u32, _vp, _u64]),
+    "nsgpu_wifil_add_waypoint": (C.c_int, [_vp, _u32, _vp]),
+    "nsgpu_wifil_end_waypoints": (C.c_int, [_vp, _u32]),
+    "nsgpu_wifil_get_waypoints": (C.c_int, [_vp, _u64, _u32, _vp]),
+    "nsgpu_wifil_set_acceleration": (C.c_int, [_vp, _u32, _vp]),
+    "nsgpu_wifil_set_velocity_and_acceleration": (C.c_int, [_vp, _u64, _u32, _vp, _vp]),
+    "nsgpu_wifil_get_acceleration": (C.c_int, [_vp, _u64, _u32, _vp]),
+    "nsgpu_sim_wifi_set_waypoints": (C.c_int, [_vp, _u32, _vp, _u64]),
+    "nsgpu_sim_wifi_add_waypoint": (C.c_int, [_vp, _u32, _vp]),
+    "nsgpu_sim_wifi_end_waypoints": (C.c_int, [_vp, _u32]),
+    "nsgpu_sim_wifi_get_waypoints": (C.c_int, [_vp, _u32, _vp]),
+    "nsgpu_sim_wifi_set_acceleration": (C.c_int, [_vp, _u32, _vp]),
+    "nsgpu_sim_wifi_set_velocity_and_acceleration": (C.c_int, [_vp, _u32, _vp, _vp]),
+    "nsgpu_sim_wifi_get_acceleration": (C.c_int, [_vp, _u32, _vp]),
     "nsgpu_wifil_set_channel": (C.c_int, [_vp, _u64, _u32, _u32, C.c_int64, _vp]),
     "nsgpu_wifil_get_channel": (C.c_int, [_vp, _u32, _vp]),
     "nsgpu_sim_wifi_set_channel": (C.c_int, [_vp, _u32, _u32, C.c_int64, _vp]),
@@ -839,6 +853,50 @@ class Sim:
         m = wifi.Mobility()
         check(lib().nsgpu_sim_wifi_get_mobility(self.h, phy, C.byref(m)))
         return tuple(m.pos), tuple(m.vel), bool(m.paused)
+
+    def wifi_set_waypoints(self, phy, wps):
+        """A fresh WaypointMobilityModel on `phy`'s node with the (time ns, position) pairs of wps added in order
+        (nsgpu_sim_wifi_set_waypoints); empty: the model is removed."""
+        import wifi
+        check(lib().nsgpu_sim_wifi_set_waypoints(self.h, phy, wifi.waypoint_array(wps), len(wps)))
+
+    def wifi_add_waypoint(self, phy, t, pos):
+        """WaypointMobilityModel::AddWaypoint of `phy`'s node from the running closure."""
+        import wifi
+        check(lib().nsgpu_sim_wifi_add_waypoint(self.h, phy, wifi.waypoint_array([(t, pos)])))
+
+    def wifi_end_waypoints(self, phy):
+        """WaypointMobilityModel::EndMobility of `phy`'s node."""
+        check(lib().nsgpu_sim_wifi_end_waypoints(self.h, phy))
+
+    def wifi_get_waypoints(self, phy):
+        """`phy`'s waypoint model now, after the Update of a position read: wifi.waypoint_record's dict."""
+        import wifi
+        s = wifi.WaypointState()
+        check(lib().nsgpu_sim_wifi_get_waypoints(self.h, phy, C.byref(s)))
+        return wifi.waypoint_record(s)
+
+    def wifi_set_acceleration(self, phy, pos, vel=(0.0, 0.0, 0.0), acc=(0.0, 0.0, 0.0), base_time=None):
+        """A ConstantAccelerationMobilityModel on `phy`'s node (base_time None: Now); pos None: removed."""
+        import wifi
+        if pos is None:
+            check(lib().nsgpu_sim_wifi_set_acceleration(self.h, phy, None))
+            return
+        a = wifi.Accel((C.c_double * 3)(*pos), (C.c_double * 3)(*vel), (C.c_double * 3)(*acc),
+                       int(self.now() if base_time is None else base_time))
+        check(lib().nsgpu_sim_wifi_set_acceleration(self.h, phy, C.byref(a)))
+
+    def wifi_set_velocity_and_acceleration(self, phy, vel, acc):
+        """ConstantAccelerationMobilityModel::SetVelocityAndAcceleration of `phy`'s node now."""
+        check(lib().nsgpu_sim_wifi_set_velocity_and_acceleration(self.h, phy, (C.c_double * 3)(*vel),
+                                                                 (C.c_double * 3)(*acc)))
+
+    def wifi_get_acceleration(self, phy):
+        """`phy`'s acceleration model now: wifi.accel_record's dict."""
+        import wifi
+        a = wifi.Accel()
+        check(lib().nsgpu_sim_wifi_get_acceleration(self.h, phy, C.byref(a)))
+        return wifi.accel_record(a)
 
     def wifi_set_channel(self, phy, nch, delay_ns):
         """YansWifiPhy::SetChannelNumber (nch) of `phy` now, ChannelSwitchDelay = delay_ns (nsgpu_sim_wifi_set_channel).

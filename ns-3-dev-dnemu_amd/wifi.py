@@ -369,6 +369,43 @@ class Mobility(C.Structure):  # nsgpu_mobility (include/nsgpu_types.h)
                 ("paused", C.c_uint32), ("pad_", C.c_uint32)]
 
 
+class Waypoint(C.Structure):  # nsgpu_waypoint
+    _fields_ = [("time", C.c_uint64), ("pos", C.c_double * 3)]
+
+
+class WaypointState(C.Structure):  # nsgpu_waypoint_state
+    _fields_ = [("cur_time", C.c_uint64), ("cur_pos", C.c_double * 3), ("next_time", C.c_uint64),
+                ("next_pos", C.c_double * 3), ("vel", C.c_double * 3), ("next_ended", C.c_uint32),
+                ("first", C.c_uint32), ("left", C.c_uint32), ("pad_", C.c_uint32)]
+
+
+class Accel(C.Structure):  # nsgpu_accel
+    _fields_ = [("pos", C.c_double * 3), ("vel", C.c_double * 3), ("acc", C.c_double * 3), ("base_time", C.c_int64),
+                ("now_pos", C.c_double * 3), ("now_vel", C.c_double * 3)]
+
+
+def waypoint_array(wps):
+    """[(time ns, (x, y, z))] as a ctypes array of Waypoint."""
+    arr = (Waypoint * max(len(wps), 1))()
+    for i, (t, p) in enumerate(wps):
+        arr[i].time = int(t)
+        arr[i].pos[:] = [float(c) for c in p]
+    return arr
+
+
+def waypoint_record(s):
+    """A WaypointState as a dict: cur / next as (time ns, position) — next's time None once the path has ended
+    (the reference's Seconds (-1)) — vel, first, left."""
+    return dict(cur=(s.cur_time, tuple(s.cur_pos)), next=(None if s.next_ended else s.next_time, tuple(s.next_pos)),
+                vel=tuple(s.vel), first=bool(s.first), left=s.left)
+
+
+def accel_record(a):
+    """An Accel as a dict: the base fields and DoGetPosition / DoGetVelocity at the read's time."""
+    return dict(pos=tuple(a.pos), vel=tuple(a.vel), acc=tuple(a.acc), base_time=a.base_time,
+                now_pos=tuple(a.now_pos), now_vel=tuple(a.now_vel))
+
+
 class LoopPhys:
     """The phys of a closed-loop run (nsgpu_wifil_config): positions, channels, nodes and the PHY /
     channel attributes (defaults as Scenario above; RxNoiseFigure 7 dB, NistErrorRateModel as
@@ -469,6 +506,45 @@ class LoopPhy:
         m = Mobility()
         nsgpu.check(nsgpu.lib().nsgpu_wifil_get_mobility(self.h, int(now), phy, C.byref(m)))
         return tuple(m.pos), tuple(m.vel), bool(m.paused)
+
+    def set_waypoints(self, phy, wps):
+        """A fresh WaypointMobilityModel on `phy` after AddWaypoint of every (time ns, position) of wps in order
+        (nsgpu_wifil_set_waypoints): the phy is at the first one's position at once.  Empty: the model is removed."""
+        nsgpu.check(nsgpu.lib().nsgpu_wifil_set_waypoints(self.h, phy, waypoint_array(wps), len(wps)))
+
+    def add_waypoint(self, phy, t, pos):
+        """WaypointMobilityModel::AddWaypoint of `phy`'s model (nsgpu_wifil_add_waypoint)."""
+        nsgpu.check(nsgpu.lib().nsgpu_wifil_add_waypoint(self.h, phy, waypoint_array([(t, pos)])))
+
+    def end_waypoints(self, phy):
+        """WaypointMobilityModel::EndMobility (nsgpu_wifil_end_waypoints)."""
+        nsgpu.check(nsgpu.lib().nsgpu_wifil_end_waypoints(self.h, phy))
+
+    def get_waypoints(self, now, phy):
+        """nsgpu_wifil_get_waypoints at `now` ns (Update, then the model's members): waypoint_record's dict."""
+        s = WaypointState()
+        nsgpu.check(nsgpu.lib().nsgpu_wifil_get_waypoints(self.h, int(now), phy, C.byref(s)))
+        return waypoint_record(s)
+
+    def set_acceleration(self, phy, pos, vel=(0.0, 0.0, 0.0), acc=(0.0, 0.0, 0.0), base_time=0):
+        """A ConstantAccelerationMobilityModel on `phy` (nsgpu_wifil_set_acceleration: m_basePosition,
+        m_baseVelocity, m_acceleration, m_baseTime in ns); pos None: the model is removed."""
+        if pos is None:
+            nsgpu.check(nsgpu.lib().nsgpu_wifil_set_acceleration(self.h, phy, None))
+            return
+        a = Accel((C.c_double * 3)(*pos), (C.c_double * 3)(*vel), (C.c_double * 3)(*acc), int(base_time))
+        nsgpu.check(nsgpu.lib().nsgpu_wifil_set_acceleration(self.h, phy, C.byref(a)))
+
+    def set_velocity_and_acceleration(self, now, phy, vel, acc):
+        """ConstantAccelerationMobilityModel::SetVelocityAndAcceleration at `now` ns."""
+        nsgpu.check(nsgpu.lib().nsgpu_wifil_set_velocity_and_acceleration(self.h, int(now), phy, (C.c_double * 3)(*vel),
+                                                                          (C.c_double * 3)(*acc)))
+
+    def get_acceleration(self, now, phy):
+        """nsgpu_wifil_get_acceleration at `now` ns: accel_record's dict (computed; no state changes)."""
+        a = Accel()
+        nsgpu.check(nsgpu.lib().nsgpu_wifil_get_acceleration(self.h, int(now), phy, C.byref(a)))
+        return accel_record(a)
 
     def set_channel(self, now, phy, nch, delay_ns):
         """YansWifiPhy::SetChannelNumber (nch) of `phy` at `now` ns with ChannelSwitchDelay delay_ns
