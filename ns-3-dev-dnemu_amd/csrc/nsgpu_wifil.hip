@@ -96,21 +96,18 @@ struct LSync {  // one sync of the epoch (its EndReceive's uid comes from the sy
   uint32_t suid, euid;
   uint32_t loc, pad;  // its pending EndReceive record: pe[loc]
 };
-struct WMob {  // a phy's ConstantVelocityHelper (constant-velocity-helper.h) next to its position D.x / y / z
-  double vx, vy, vz;     // m_velocity
-  int64_t last;          // m_lastUpdate, ns
-  uint32_t flags, pad;   // MOB_ON: a model is installed (clear: a constant-position phy); MOB_PAUSED: m_paused
-};
-constexpr uint32_t MOB_ON = 1, MOB_PAUSED = 2;
-struct WPath {  // a phy's WaypointMobilityModel or ConstantAccelerationMobilityModel (kind) next to its position
-  uint32_t kind, first;    // PATH_NONE / PATH_WAY / PATH_ACC; waypoint: m_first
+struct WMove {  // a phy's motion model (kind) next to its position D.x / y / z: a ConstantVelocityHelper
+                // (constant-velocity-helper.h), a WaypointMobilityModel or a ConstantAccelerationMobilityModel
+  uint32_t kind, flag;     // MOVE_NONE (a constant-position phy) / MOVE_VEL / MOVE_WAY / MOVE_ACC; constant velocity:
+                           //   m_paused; waypoint: m_first
   uint32_t off, head, cnt, pad;  // waypoint: m_waypoints is D.wpool[off + head, off + cnt) (the pop advances head)
-  int64_t cur_t, next_t;   // waypoint: m_current.time, m_next.time (signed: Seconds (-1) ends the path); acceleration:
-                           //   m_baseTime in cur_t
-  double p[3], v[3], a[3];  // waypoint: m_next.position, m_velocity (m_current.position is D.x / y / z);
-                            //   acceleration: m_basePosition, m_baseVelocity, m_acceleration
+  int64_t cur_t, next_t;   // constant velocity: m_lastUpdate in cur_t; waypoint: m_current.time, m_next.time (signed:
+                           //   Seconds (-1) ends the path); acceleration: m_baseTime in cur_t
+  double p[3], v[3], a[3];  // constant velocity: m_velocity in v (m_position is D.x / y / z); waypoint: m_next.position,
+                            //   m_velocity (m_current.position is D.x / y / z); acceleration: m_basePosition,
+                            //   m_baseVelocity, m_acceleration
 };
-constexpr uint32_t PATH_NONE = 0, PATH_WAY = 1, PATH_ACC = 2;
+constexpr uint32_t MOVE_NONE = 0, MOVE_VEL = 1, MOVE_WAY = 2, MOVE_ACC = 3;
 constexpr int64_t WAY_ENDED = -1000000000;  // Seconds (-1.0)
 constexpr int WP_CHUNK = 8;
 struct WpChunk {  // waypoints carried to the pool as a kernel argument (k_wl_wput): no staging buffer to outlive
@@ -183,16 +180,14 @@ struct WDev {
   const uint32_t *note_on;
   nsgpu_wifil_note *notes;
   uint64_t note_cap;
-  // constant-velocity mobility (nsgpu_wifil_set_mobility): a record per phy, sized at the first install (null
-  // until then); k_wl_move, launched ahead of a send's k_wl_rx only while some phy has a model, updates x / y / z
-  WMob *mob;
+  // mobility (nsgpu_wifil_set_mobility / _set_waypoints / _set_acceleration): a record per phy, sized at the first
+  // install of any model (null until then); k_wl_move, launched ahead of a send's k_wl_rx only while some phy has a
+  // model, updates x / y / z, and the one-thread host calls (k_wl_mop) read and write it
+  WMove *mov;
   // the extended loss chain (nsgpu_wifil_set_loss): null until one is installed; only k_wl_send<true> / k_wl_rx<true>,
   // launched while one is, read it
   const LossX *lx;
-  // waypoint / acceleration mobility (nsgpu_wifil_set_waypoints / _set_acceleration): a record per phy and the one
-  // pool every phy's waypoint list lives in, null until the first install of either; only k_wl_move<true>, launched
-  // while some phy has such a model, and the one-thread host calls read them
-  WPath *path;
+  // the one pool every phy's waypoint list lives in (WMove::off), null until the first waypoint install
   nsgpu_waypoint *wpool;
 };
 // The epoch's dispatched events are appended to EV_STRIPES lists (phy j's to stripe j % EV_STRIPES): one
@@ -378,25 +373,24 @@ __device__ __forceinline__ double get_seconds(const WDev &D, int64_t ts) {
 }
 // ConstantVelocityHelper::Update (constant-velocity-helper.cc:69-84) of phy j at `now`, restated literally: the
 // products and sums round one by one (the library is built -ffp-contract=off: no FMA), so the doubles depend on
-// the accumulation points exactly as the reference's do.  A phy without a model is untouched.
-__device__ __forceinline__ void mob_update(const WDev &D, int64_t j, int64_t now) {
-  WMob &m = D.mob[j];
-  if (!(m.flags & MOB_ON)) return;
-  const int64_t delta = now - m.last;  // Time deltaTime = now - m_lastUpdate
-  m.last = now;
-  if (m.flags & MOB_PAUSED) return;
+// the accumulation points exactly as the reference's do.
+__device__ __forceinline__ void vel_update(const WDev &D, int64_t j, int64_t now) {
+  WMove &m = D.mov[j];
+  const int64_t delta = now - m.cur_t;  // Time deltaTime = now - m_lastUpdate
+  m.cur_t = now;
+  if (m.flag) return;                   // m_paused
   const double deltaS = get_seconds(D, delta);
   double *const x = const_cast<double *>(D.x), *const y = const_cast<double *>(D.y), *const z = const_cast<double *>(D.z);
-  x[j] += m.vx * deltaS;
-  y[j] += m.vy * deltaS;
-  z[j] += m.vz * deltaS;
+  x[j] += m.v[0] * deltaS;
+  y[j] += m.v[1] * deltaS;
+  z[j] += m.v[2] * deltaS;
 }
 // WaypointMobilityModel::Update (waypoint-mobility-model.cc:114-173) of phy j at `now`, statement by statement
 // (NotifyCourseChange has no listener here).  m_current.position is D.x / y / z [j]; the divisions are IEEE double
 // divisions, the products and sums round one by one.  One call may cross several waypoints: the loop pops at most
 // the queue's length.
 __device__ __forceinline__ void way_update(const WDev &D, int64_t j, int64_t now) {
-  WPath &m = D.path[j];
+  WMove &m = D.mov[j];
   int64_t cur_t = m.cur_t, next_t = m.next_t;
   if (now < cur_t) return;                                     // :119-122
   double *const x = const_cast<double *>(D.x), *const y = const_cast<double *>(D.y), *const z = const_cast<double *>(D.z);
@@ -440,24 +434,27 @@ __device__ __forceinline__ void way_update(const WDev &D, int64_t j, int64_t now
 }
 // ConstantAccelerationMobilityModel::DoGetPosition / DoGetVelocity (constant-acceleration-mobility-model.cc:41-58)
 // of phy j's record at `now`: (base + v t) + a (t t 0.5), each product and sum rounded.
-__device__ __forceinline__ void acc_position(const WDev &D, const WPath &m, int64_t now, double out[3]) {
+__device__ __forceinline__ void acc_position(const WDev &D, const WMove &m, int64_t now, double out[3]) {
   const double t = get_seconds(D, now - m.cur_t);
   const double half_t_square = t * t * 0.5;
   for (int c = 0; c < 3; c++) out[c] = m.p[c] + m.v[c] * t + m.a[c] * half_t_square;
 }
-__device__ __forceinline__ void acc_velocity(const WDev &D, const WPath &m, int64_t now, double out[3]) {
+__device__ __forceinline__ void acc_velocity(const WDev &D, const WMove &m, int64_t now, double out[3]) {
   const double t = get_seconds(D, now - m.cur_t);
   for (int c = 0; c < 3; c++) out[c] = m.v[c] + m.a[c] * t;
 }
-// A waypoint or acceleration phy's position read at a send.  An acceleration phy stores nothing but the position it
+// Phy j's model brought up to date at `now` (a send's position read, or a host call's): the kind's Update /
+// DoGetPosition.  A phy without a model is untouched.  An acceleration phy stores nothing but the position it
 // evaluated: on another channel than the sender's its D.x / y / z stay stale, which nobody reads until the phy is
 // next on a sender's channel, and this rewrites them then (nsgpu_wifil_get_acceleration computes, it never reads
 // them).
-__device__ __forceinline__ void path_update(const WDev &D, int64_t j, int64_t now) {
-  const WPath &m = D.path[j];
-  if (m.kind == PATH_WAY) {
+__device__ __forceinline__ void move_update(const WDev &D, int64_t j, int64_t now) {
+  const WMove &m = D.mov[j];
+  if (m.kind == MOVE_VEL) {
+    vel_update(D, j, now);
+  } else if (m.kind == MOVE_WAY) {
     way_update(D, j, now);
-  } else {
+  } else if (m.kind == MOVE_ACC) {
     double p[3];
     acc_position(D, m, now, p);
     const_cast<double *>(D.x)[j] = p[0], const_cast<double *>(D.y)[j] = p[1], const_cast<double *>(D.z)[j] = p[2];
@@ -1524,79 +1521,59 @@ __global__ __launch_bounds__(256) void k_wl_rx(const WDev D, LRx *row, LTx t, ui
 // sender when there is at least one of them (upd_sender; its later updates of the same send have a zero delta);
 // phys on other channels keep their m_lastUpdate.  One lane per phy, launched ahead of the send's k_wl_rx — whose
 // every lane reads the sender's position, so the update is not made in place there — and only while some phy has
-// a model: a run without one launches k_wl_rx alone, as before.  PX: some phy has a waypoint or acceleration model
-// (D.path is sized); its lane runs that model's Update / DoGetPosition in place of mob_update.  <false>, launched
-// while no phy has one, is the kernel as it was.
-template <bool PX>
+// a model: a run without one launches k_wl_rx alone, as before.
 __global__ __launch_bounds__(256) void k_wl_move(const WDev D, uint32_t s, int64_t now, uint32_t upd_sender) {
   const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (j >= D.nphy) return;
   if (j == (int64_t)s ? !upd_sender : D.chan[j] != D.chan[s]) return;
-  if constexpr (PX) {
-    if (D.path[j].kind != PATH_NONE) {
-      path_update(D, j, now);
-      return;
-    }
-  }
-  mob_update(D, j, now);
+  move_update(D, j, now);
 }
 // Waypoints into the pool, in stream order: behind every kernel that may read the segment's old count, ahead of the
-// k_wl_path call that publishes the new one.
+// k_wl_mop call that publishes the new one.
 __global__ void k_wl_wput(nsgpu_waypoint *dst, WpChunk c, uint32_t n) {
   if (threadIdx.x < n) dst[threadIdx.x] = c.w[threadIdx.x];
 }
-// A host call on one phy's waypoint or acceleration model (one thread, in stream order with the sends, as k_wl_mob).
-//   PATH_WAY_INSTALL  a fresh model after AddWaypoint (a.w) and `cnt` more queued at D.wpool[off, off + cnt)
+// A host call on one phy's model (one thread, in stream order with the sends, as k_wl_set).  An install overwrites
+// whatever record the phy had: one model per phy.
+//   MOP_REMOVE        a constant position where the last update left the phy
+//   MOP_SET_POSITION  the kind's SetPosition / DoSetPosition
+//   MOP_VEL_INSTALL   ConstantVelocityHelper state (nsgpu_wifil_set_mobility); MOP_VEL_SET:
+//                     ConstantVelocityMobilityModel::SetVelocity (constant-velocity-mobility-model.cc:43-50);
+//                     MOP_VEL_PAUSE: Update + Pause / Unpause; MOP_VEL_GET: GetPosition + GetVelocity
+//                     (constant-velocity-helper.cc:51-60, DoGetPosition's Update first)
+//   MOP_WAY_INSTALL   a fresh model after AddWaypoint (a.w) and `cnt` more queued at D.wpool[off, off + cnt)
 //                     (waypoint-mobility-model.cc:82-100: m_first = false, m_current = m_next = waypoint)
-//   PATH_WAY_ADD      AddWaypoint: the first of a path (m_first) as above, else the slot cnt - 1 of the segment — now
+//   MOP_WAY_ADD       AddWaypoint: the first of a path (m_first) as above, else the slot cnt - 1 of the segment — now
 //                     at `off` — is the new back of the queue
-//   PATH_WAY_END      EndMobility (:203-209); Time (numeric_limits<uint64_t>::infinity ()) is Time (0)
-//   PATH_WAY_GET      Update, then the members; PATH_SET_POSITION: either model's DoSetPosition
-//   PATH_ACC_INSTALL / PATH_ACC_SET (SetVelocityAndAcceleration, :70-78) / PATH_ACC_GET;  PATH_REMOVE
-enum PathOp : uint32_t { PATH_WAY_INSTALL, PATH_WAY_ADD, PATH_WAY_END, PATH_WAY_GET, PATH_SET_POSITION, PATH_ACC_INSTALL,
-                         PATH_ACC_SET, PATH_ACC_GET, PATH_REMOVE };
-struct PathArg {
-  nsgpu_waypoint w;     // INSTALL / ADD: the waypoint; SET_POSITION: w.pos
-  double v[3], a[3];    // ACC_INSTALL / ACC_SET
-  int64_t base_time;    // ACC_INSTALL
+//   MOP_WAY_END       EndMobility (:203-209); Time (numeric_limits<uint64_t>::infinity ()) is Time (0)
+//   MOP_WAY_GET       Update, then the members
+//   MOP_ACC_INSTALL / MOP_ACC_SET (SetVelocityAndAcceleration, :70-78) / MOP_ACC_GET
+enum MoveOp : uint32_t { MOP_REMOVE, MOP_SET_POSITION, MOP_VEL_INSTALL, MOP_VEL_SET, MOP_VEL_PAUSE, MOP_VEL_GET,
+                         MOP_WAY_INSTALL, MOP_WAY_ADD, MOP_WAY_END, MOP_WAY_GET, MOP_ACC_INSTALL, MOP_ACC_SET, MOP_ACC_GET };
+struct MoveArg {
+  nsgpu_waypoint w;     // WAY_INSTALL / WAY_ADD: the waypoint; VEL_INSTALL / ACC_INSTALL / SET_POSITION: w.pos
+  double v[3], a[3];    // VEL_INSTALL / VEL_SET: v; ACC_INSTALL / ACC_SET: both
+  int64_t time;         // VEL_INSTALL: m_lastUpdate; ACC_INSTALL: m_baseTime
   uint32_t off, cnt;    // the waypoint segment's place and the slots written
+  uint32_t paused, pad;  // VEL_INSTALL / VEL_PAUSE: m_paused
 };
-union PathOut {
+union MoveOut {
+  nsgpu_mobility vel;
   nsgpu_waypoint_state way;
   nsgpu_accel acc;
 };
-__global__ void k_wl_path(const WDev D, uint32_t op, uint32_t j, int64_t now, PathArg a, PathOut *out) {
-  WPath &m = D.path[j];
+__global__ void k_wl_mop(const WDev D, uint32_t op, uint32_t j, int64_t now, MoveArg a, MoveOut *out) {
+  WMove &m = D.mov[j];
   double *const x = const_cast<double *>(D.x), *const y = const_cast<double *>(D.y), *const z = const_cast<double *>(D.z);
   switch (op) {
-    case PATH_WAY_INSTALL:
-      m = WPath{};
-      m.kind = PATH_WAY, m.first = 1;
-      [[fallthrough]];
-    case PATH_WAY_ADD:
-      m.off = a.off, m.cnt = a.cnt;
-      if (m.first) {  // :84-88
-        m.first = 0;
-        m.cur_t = m.next_t = (int64_t)a.w.time;
-        x[j] = m.p[0] = a.w.pos[0], y[j] = m.p[1] = a.w.pos[1], z[j] = m.p[2] = a.w.pos[2];
-      }
+    case MOP_REMOVE:
+      m = WMove{};
       break;
-    case PATH_WAY_END:
-      m.head = m.cnt;  // m_waypoints.clear ()
-      m.cur_t = m.next_t = 0;
-      m.first = 1;
-      break;
-    case PATH_WAY_GET: {
-      way_update(D, j, now);
-      nsgpu_waypoint_state &o = out->way;
-      const bool ended = m.next_t == WAY_ENDED;
-      o = nsgpu_waypoint_state{(uint64_t)m.cur_t, {x[j], y[j], z[j]}, ended ? 0ull : (uint64_t)m.next_t,
-                               {m.p[0], m.p[1], m.p[2]}, {m.v[0], m.v[1], m.v[2]}, ended ? 1u : 0u, m.first,
-                               m.cnt - m.head, 0};
-      break;
-    }
-    case PATH_SET_POSITION:
-      if (m.kind == PATH_WAY) {  // DoSetPosition (:181-201), m_initialPositionIsWaypoint false
+    case MOP_SET_POSITION:
+      if (m.kind == MOVE_VEL) {  // m_position = position; m_velocity = Vector (0, 0, 0); m_lastUpdate = Now ()
+        m.v[0] = m.v[1] = m.v[2] = 0.0;
+        m.cur_t = now;
+      } else if (m.kind == MOVE_WAY) {  // DoSetPosition (:181-201), m_initialPositionIsWaypoint false
         way_update(D, j, now);
         m.cur_t = now > m.next_t ? now : m.next_t;
         m.v[0] = m.v[1] = m.v[2] = 0.0;
@@ -1609,69 +1586,75 @@ __global__ void k_wl_path(const WDev D, uint32_t op, uint32_t j, int64_t now, Pa
       }
       x[j] = a.w.pos[0], y[j] = a.w.pos[1], z[j] = a.w.pos[2];
       break;
-    case PATH_ACC_INSTALL:
-      m = WPath{};
-      m.kind = PATH_ACC;
-      m.cur_t = a.base_time;
+    case MOP_VEL_INSTALL:
+      x[j] = a.w.pos[0], y[j] = a.w.pos[1], z[j] = a.w.pos[2];
+      m = WMove{};
+      m.kind = MOVE_VEL, m.flag = a.paused ? 1u : 0u;
+      m.cur_t = a.time;
+      m.v[0] = a.v[0], m.v[1] = a.v[1], m.v[2] = a.v[2];
+      break;
+    case MOP_VEL_SET:  // m_helper.Update (); m_helper.SetVelocity (speed); m_helper.Unpause ()
+      vel_update(D, j, now);
+      m.v[0] = a.v[0], m.v[1] = a.v[1], m.v[2] = a.v[2];
+      m.cur_t = now;
+      m.flag = 0;
+      break;
+    case MOP_VEL_PAUSE:
+      vel_update(D, j, now);
+      m.flag = a.paused ? 1u : 0u;
+      break;
+    case MOP_VEL_GET: {
+      vel_update(D, j, now);
+      const bool p = m.flag != 0;
+      out->vel = nsgpu_mobility{{x[j], y[j], z[j]}, {p ? 0.0 : m.v[0], p ? 0.0 : m.v[1], p ? 0.0 : m.v[2]}, m.cur_t,
+                                p ? 1u : 0u, 0};
+      break;
+    }
+    case MOP_WAY_INSTALL:
+      m = WMove{};
+      m.kind = MOVE_WAY, m.flag = 1;
+      [[fallthrough]];
+    case MOP_WAY_ADD:
+      m.off = a.off, m.cnt = a.cnt;
+      if (m.flag) {  // :84-88
+        m.flag = 0;
+        m.cur_t = m.next_t = (int64_t)a.w.time;
+        x[j] = m.p[0] = a.w.pos[0], y[j] = m.p[1] = a.w.pos[1], z[j] = m.p[2] = a.w.pos[2];
+      }
+      break;
+    case MOP_WAY_END:
+      m.head = m.cnt;  // m_waypoints.clear ()
+      m.cur_t = m.next_t = 0;
+      m.flag = 1;
+      break;
+    case MOP_WAY_GET: {
+      way_update(D, j, now);
+      nsgpu_waypoint_state &o = out->way;
+      const bool ended = m.next_t == WAY_ENDED;
+      o = nsgpu_waypoint_state{(uint64_t)m.cur_t, {x[j], y[j], z[j]}, ended ? 0ull : (uint64_t)m.next_t,
+                               {m.p[0], m.p[1], m.p[2]}, {m.v[0], m.v[1], m.v[2]}, ended ? 1u : 0u, m.flag,
+                               m.cnt - m.head, 0};
+      break;
+    }
+    case MOP_ACC_INSTALL:
+      m = WMove{};
+      m.kind = MOVE_ACC;
+      m.cur_t = a.time;
       for (int c = 0; c < 3; c++) m.p[c] = a.w.pos[c], m.v[c] = a.v[c], m.a[c] = a.a[c];
       break;
-    case PATH_ACC_SET: {
+    case MOP_ACC_SET: {
       double p[3];
       acc_position(D, m, now, p);
       m.cur_t = now;
       for (int c = 0; c < 3; c++) m.p[c] = p[c], m.v[c] = a.v[c], m.a[c] = a.a[c];
       break;
     }
-    case PATH_ACC_GET: {
+    default: {  // MOP_ACC_GET
       nsgpu_accel &o = out->acc;
       for (int c = 0; c < 3; c++) o.pos[c] = m.p[c], o.vel[c] = m.v[c], o.acc[c] = m.a[c];
       o.base_time = m.cur_t;
       acc_position(D, m, now, o.now_pos);
       acc_velocity(D, m, now, o.now_vel);
-      break;
-    }
-    default: {  // PATH_REMOVE: a constant position where the last update left the phy
-      const uint32_t off = m.off;  // (the segment stays the phy's)
-      m = WPath{};
-      m.off = off;
-    }
-  }
-}
-// A host call on one phy's model, in stream order with the sends (one thread, as k_wl_set):
-// install / remove (nsgpu_wifil_set_mobility), ConstantVelocityMobilityModel::SetVelocity
-// (constant-velocity-mobility-model.cc:43-50), Update + Pause / Unpause, ConstantVelocityHelper::SetPosition
-// (constant-velocity-helper.cc:43-49), and GetPosition + GetVelocity (:51-60, DoGetPosition's Update first).
-enum MobOp : uint32_t { MOB_INSTALL, MOB_REMOVE, MOB_SET_VELOCITY, MOB_PAUSE, MOB_SET_POSITION, MOB_GET };
-__global__ void k_wl_mob(const WDev D, uint32_t op, uint32_t j, int64_t now, nsgpu_mobility a, nsgpu_mobility *out) {
-  WMob &m = D.mob[j];
-  double *const x = const_cast<double *>(D.x), *const y = const_cast<double *>(D.y), *const z = const_cast<double *>(D.z);
-  switch (op) {
-    case MOB_INSTALL:
-      x[j] = a.pos[0], y[j] = a.pos[1], z[j] = a.pos[2];
-      m = WMob{a.vel[0], a.vel[1], a.vel[2], a.last_update, MOB_ON | (a.paused ? MOB_PAUSED : 0u), 0};
-      break;
-    case MOB_REMOVE:
-      m = WMob{};
-      break;
-    case MOB_SET_VELOCITY:  // m_helper.Update (); m_helper.SetVelocity (speed); m_helper.Unpause ()
-      mob_update(D, j, now);
-      m.vx = a.vel[0], m.vy = a.vel[1], m.vz = a.vel[2];
-      m.last = now;
-      m.flags &= ~MOB_PAUSED;
-      break;
-    case MOB_PAUSE:
-      mob_update(D, j, now);
-      m.flags = a.paused ? m.flags | MOB_PAUSED : m.flags & ~MOB_PAUSED;
-      break;
-    case MOB_SET_POSITION:  // m_position = position; m_velocity = Vector (0, 0, 0); m_lastUpdate = Now ()
-      x[j] = a.pos[0], y[j] = a.pos[1], z[j] = a.pos[2];
-      m.vx = m.vy = m.vz = 0.0;
-      m.last = now;
-      break;
-    default: {  // MOB_GET
-      mob_update(D, j, now);
-      const bool p = (m.flags & MOB_PAUSED) != 0;
-      *out = nsgpu_mobility{{x[j], y[j], z[j]}, {p ? 0.0 : m.vx, p ? 0.0 : m.vy, p ? 0.0 : m.vz}, m.last, p ? 1u : 0u, 0};
     }
   }
 }
@@ -1695,7 +1678,7 @@ __global__ __launch_bounds__(256) void k_wl_rechan(const WDev D, uint32_t j, uin
   if (c == old) rank[i] -= 1;       // (old != nch: the host launches this kernel only then)
   else if (c == nch) rank[i] += 1;
 }
-// k_wl_switch (one thread, as k_wl_mob): the switch itself when `sw` (Now != 0) — m_endRxEvent.Cancel () in RX
+// k_wl_switch (one thread, as k_wl_mop): the switch itself when `sw` (Now != 0) — m_endRxEvent.Cancel () in RX
 // (:343-347: the pending EndReceive stays queued, marked cancelled, as SendPacket-while-RX leaves it),
 // WifiPhyStateHelper::SwitchToChannelSwitching (wifi-phy-state-helper.cc:323-365: m_rxing = false, m_endRx = now from
 // RX; m_endCcaBusy trimmed to now; m_startSwitching, m_endSwitching), InterferenceHelper::EraseEvents
@@ -1860,19 +1843,14 @@ struct nsgpu_wifil {
   uint64_t n_note_on = 0;
   uint32_t *d_note_on = nullptr;
   std::vector<nsgpu_wifil_note> notes, notes_epoch;
-  // constant-velocity mobility: the phys with a model (a flag each; their count decides whether a send launches
-  // k_wl_move), and the device word nsgpu_wifil_get_mobility reads back
-  std::vector<uint8_t> mob_on;
-  uint64_t n_mob = 0;
-  nsgpu_mobility *d_mobout = nullptr;
-  // waypoint / acceleration mobility: every phy's model kind (PATH_*; their count picks k_wl_move's instantiation),
-  // the waypoint phys' lists and segments of the pool D.wpool (nsgpu_waypool.h; the pool is not in `allocs`: it is
-  // replaced when it grows), and the device word the two reads come back through
-  std::vector<uint8_t> path_kind;
-  uint64_t n_path = 0;
+  // mobility: every phy's model kind (MOVE_*; empty until the first install; the count of phys with one decides
+  // whether a send launches k_wl_move), the waypoint phys' lists and segments of the pool D.wpool (nsgpu_waypool.h;
+  // the pool is not in `allocs`: it is replaced when it grows), and the device word the three reads come back through
+  std::vector<uint8_t> mov_kind;
+  uint64_t n_mov = 0;
   std::vector<WaySeg> seg;
   WayPool wpool;
-  PathOut *d_pathout = nullptr;
+  MoveOut *d_movout = nullptr;
   // channel switching (nsgpu_wifil_set_channel): every phy's current channel number (the receiver counts in `recv`
   // follow it), the switches made (non-zero: the epochs launch the SW instantiation) and k_wl_rechan's count word
   // (allocated at the first call)
@@ -2197,15 +2175,14 @@ static int wl_queue_send(nsgpu_wifil *h, const LTx &t, double dbm, uint32_t uid_
     int rcf = wl_flush_sends(h);
     if (rcf) return rcf;
   }
-  if (h->n_mob || h->n_path) {
+  if (h->n_mov) {
     // Mobility and the batch: a flushed send's receptions are re-derived by k_wl_send from the positions held at
     // the flush, so the batch is flushed before anything that can change a position — this send's updates here,
-    // and every nsgpu_wifil_set_mobility / _set_velocity / _pause / _set_position_at / _get_mobility (as
-    // nsgpu_wifil_set_position always did).  Each send is then applied from the positions of its own send.
+    // and every host call on a phy's model (wl_move_op; as nsgpu_wifil_set_position always did).  Each send is then
+    // applied from the positions of its own send.
     if (int rcf = wl_flush_sends(h)) return rcf;
-    // (the waypoint / acceleration instantiation only while some phy has such a model)
-    hipLaunchKernelGGL(h->n_path ? k_wl_move<true> : k_wl_move<false>, dim3(wl_grid(h->D.nphy, 256)), dim3(256), 0, h->s, h->D,
-                       t.phy, (int64_t)t.ts, h->recv[t.phy] ? 1u : 0u);
+    hipLaunchKernelGGL(k_wl_move, dim3(wl_grid(h->D.nphy, 256)), dim3(256), 0, h->s, h->D, t.phy, (int64_t)t.ts,
+                       h->recv[t.phy] ? 1u : 0u);
   }
   const uint32_t k = (uint32_t)h->n_tx++;
   if (h->sb.n == 0) h->sb.k0 = k;
@@ -2368,9 +2345,8 @@ extern "C" int nsgpu_wifil_flush(nsgpu_wifil *h, uint64_t *digest) {
   return NSGPU_OK;
 }
 
-static bool wl_mobile(const nsgpu_wifil *h, uint32_t phy) { return phy < h->mob_on.size() && h->mob_on[phy]; }
-// (the phy's waypoint / acceleration model: PATH_NONE, PATH_WAY or PATH_ACC)
-static uint32_t wl_pathed(const nsgpu_wifil *h, uint32_t phy) { return phy < h->path_kind.size() ? h->path_kind[phy] : PATH_NONE; }
+// (the phy's mobility model: MOVE_NONE, MOVE_VEL, MOVE_WAY or MOVE_ACC)
+static uint32_t wl_kind(const nsgpu_wifil *h, uint32_t phy) { return phy < h->mov_kind.size() ? h->mov_kind[phy] : MOVE_NONE; }
 
 // MobilityModel::SetPosition of `phy`'s node (mobility-model.cc SetPosition -> DoSetPosition; e.g. a host closure
 // at run time): YansWifiChannel::Send reads the positions at each send (yans-wifi-channel.cc:92-96), so the
@@ -2378,12 +2354,9 @@ static uint32_t wl_pathed(const nsgpu_wifil *h, uint32_t phy) { return phy < h->
 // the sends.
 extern "C" int nsgpu_wifil_set_position(nsgpu_wifil *h, uint32_t phy, double x, double y, double z) {
   if (!h || phy >= h->D.nphy) return set_error(NSGPU_EINVAL, "nsgpu_wifil_set_position: bad phy");
-  if (wl_mobile(h, phy))
-    return set_error(NSGPU_ESTATE, "nsgpu_wifil_set_position: phy %u has a constant-velocity model, whose SetPosition "
-                                   "sets m_lastUpdate: use nsgpu_wifil_set_position_at", phy);
-  if (wl_pathed(h, phy))
-    return set_error(NSGPU_ESTATE, "nsgpu_wifil_set_position: phy %u has a waypoint or acceleration model, whose "
-                                   "DoSetPosition reads Now: use nsgpu_wifil_set_position_at", phy);
+  if (wl_kind(h, phy))
+    return set_error(NSGPU_ESTATE, "nsgpu_wifil_set_position: phy %u has a mobility model, whose SetPosition reads Now: "
+                                   "use nsgpu_wifil_set_position_at", phy);
   if (!h->mem.empty()) {  // (every partition holds every position)
     for (nsgpu_wifil *m : h->mem)
       if (int rcm = nsgpu_wifil_set_position(m, phy, x, y, z)) return rcm;
@@ -2398,128 +2371,81 @@ extern "C" int nsgpu_wifil_set_position(nsgpu_wifil *h, uint32_t phy, double x, 
   return NSGPU_OK;
 }
 
-// One k_wl_mob call on phy's model (the batch first: see wl_queue_send).
-static int wl_mob_op(nsgpu_wifil *h, uint32_t op, uint32_t phy, uint64_t now, const nsgpu_mobility &a) {
+// ---- mobility: constant velocity, waypoints, constant acceleration ----
+// One k_wl_mop call on phy's model (the batch first: see wl_queue_send).  The host's copy of the record's kind, and
+// the count of phys with a model, follow the op: an install sets the kind, the remove clears it.
+static int wl_move_op(nsgpu_wifil *h, uint32_t op, uint32_t phy, uint64_t now, const MoveArg &a) {
   if (int rcf = wl_flush_sends(h)) return rcf;
-  hipLaunchKernelGGL(k_wl_mob, dim3(1), dim3(1), 0, h->s, h->D, op, phy, (int64_t)now, a, h->d_mobout);
+  hipLaunchKernelGGL(k_wl_mop, dim3(1), dim3(1), 0, h->s, h->D, op, phy, (int64_t)now, a, h->d_movout);
   NSGPU_HIP(hipGetLastError());
+  uint8_t &kind = h->mov_kind[phy];
+  const uint8_t is = op == MOP_REMOVE ? MOVE_NONE : op == MOP_VEL_INSTALL ? MOVE_VEL : op == MOP_WAY_INSTALL ? MOVE_WAY
+                     : op == MOP_ACC_INSTALL ? MOVE_ACC : kind;
+  h->n_mov += (is != MOVE_NONE) - (kind != MOVE_NONE);
+  kind = is;
   return NSGPU_OK;
 }
-
-// The constant-velocity records, sized at the first install of any model (k_wl_move reads them for every phy that has
-// no waypoint / acceleration model).
-static int wl_mob_size(nsgpu_wifil *h) {
-  if (!h->mob_on.empty()) return NSGPU_OK;
-  int rc = wl_alloc(h, &h->D.mob, (size_t)h->D.nphy);
-  if (!rc) rc = wl_alloc(h, &h->d_mobout, 1);
-  if (rc) return rc;
-  h->mob_on.assign((size_t)h->D.nphy, 0);
-  return NSGPU_OK;
-}
-static int wl_path_remove(nsgpu_wifil *h, uint32_t phy);
-
-// Installs ConstantVelocityHelper state on `phy` (m == NULL: removes it; the phy stays where it is, a constant
-// position again).  The records are sized at the first install, as nsgpu_wifil_notify sizes its flags.
-extern "C" int nsgpu_wifil_set_mobility(nsgpu_wifil *h, uint32_t phy, const nsgpu_mobility *m) {
-  if (!h || phy >= h->D.nphy) return set_error(NSGPU_EINVAL, "nsgpu_wifil_set_mobility: bad phy");  // (before anything is sized)
+// The argument checks every install / remove call makes first and, ahead of an install, the records: sized at the
+// first install of any model, as nsgpu_wifil_notify sizes its flags.
+static int wl_move_begin(nsgpu_wifil *h, uint32_t phy, const char *what, bool install) {
+  if (!h || phy >= h->D.nphy) return set_error(NSGPU_EINVAL, "%s: bad phy", what);  // (before anything is sized)
   if (!h->mem.empty())
-    return set_error(NSGPU_EINVAL, "nsgpu_wifil_set_mobility: mobility is single-engine for now (a partitioned handle)");
-  if (h->mob_on.empty()) {
-    if (!m) return NSGPU_OK;
-    if (int rc = wl_mob_size(h)) return rc;
-  }
-  const uint8_t v = m ? 1 : 0;
-  if (!v && !h->mob_on[phy]) return NSGPU_OK;
-  if (v && wl_pathed(h, phy))  // (one model per phy: this one replaces its waypoint / acceleration model)
-    if (int rc = wl_path_remove(h, phy)) return rc;
-  if (int rc = wl_mob_op(h, v ? MOB_INSTALL : MOB_REMOVE, phy, 0, m ? *m : nsgpu_mobility{})) return rc;
-  if (h->mob_on[phy] != v) {
-    h->mob_on[phy] = v;
-    h->n_mob += v ? 1 : (uint64_t)-1;
-  }
+    return set_error(NSGPU_EINVAL, "%s: mobility is single-engine for now (a partitioned handle)", what);
+  if (!install || !h->mov_kind.empty()) return NSGPU_OK;
+  int rc = wl_alloc(h, &h->D.mov, (size_t)h->D.nphy);
+  if (!rc) rc = wl_alloc(h, &h->d_movout, 1);
+  if (rc) return rc;
+  h->mov_kind.assign((size_t)h->D.nphy, MOVE_NONE);
+  h->seg.resize((size_t)h->D.nphy);
   return NSGPU_OK;
 }
 
-static int wl_path_op(nsgpu_wifil *h, uint32_t op, uint32_t phy, uint64_t now, const PathArg &a);
+// Installs ConstantVelocityHelper state on `phy`, in place of whatever model it had (m == NULL: removes a
+// constant-velocity model; the phy stays where it is, a constant position again).
+extern "C" int nsgpu_wifil_set_mobility(nsgpu_wifil *h, uint32_t phy, const nsgpu_mobility *m) {
+  if (int rc = wl_move_begin(h, phy, "nsgpu_wifil_set_mobility", m != nullptr)) return rc;
+  if (!m) return wl_kind(h, phy) == MOVE_VEL ? wl_move_op(h, MOP_REMOVE, phy, 0, MoveArg{}) : NSGPU_OK;
+  MoveArg a{};
+  for (int c = 0; c < 3; c++) a.w.pos[c] = m->pos[c], a.v[c] = m->vel[c];
+  a.time = m->last_update, a.paused = m->paused;
+  return wl_move_op(h, MOP_VEL_INSTALL, phy, 0, a);
+}
 
 extern "C" int nsgpu_wifil_set_velocity(nsgpu_wifil *h, uint64_t now, uint32_t phy, const double v[3]) {
   if (!h || !v || phy >= h->D.nphy) return set_error(NSGPU_EINVAL, "nsgpu_wifil_set_velocity: bad phy");
-  if (!wl_mobile(h, phy)) return set_error(NSGPU_ESTATE, "nsgpu_wifil_set_velocity: phy %u has no mobility model", phy);
-  nsgpu_mobility a{};
-  a.vel[0] = v[0], a.vel[1] = v[1], a.vel[2] = v[2];
-  return wl_mob_op(h, MOB_SET_VELOCITY, phy, now, a);
+  if (wl_kind(h, phy) != MOVE_VEL) return set_error(NSGPU_ESTATE, "nsgpu_wifil_set_velocity: phy %u has no mobility model", phy);
+  MoveArg a{};
+  a.v[0] = v[0], a.v[1] = v[1], a.v[2] = v[2];
+  return wl_move_op(h, MOP_VEL_SET, phy, now, a);
 }
 
 extern "C" int nsgpu_wifil_pause(nsgpu_wifil *h, uint64_t now, uint32_t phy, uint32_t paused) {
   if (!h || phy >= h->D.nphy) return set_error(NSGPU_EINVAL, "nsgpu_wifil_pause: bad phy");
-  if (!wl_mobile(h, phy)) return set_error(NSGPU_ESTATE, "nsgpu_wifil_pause: phy %u has no mobility model", phy);
-  nsgpu_mobility a{};
+  if (wl_kind(h, phy) != MOVE_VEL) return set_error(NSGPU_ESTATE, "nsgpu_wifil_pause: phy %u has no mobility model", phy);
+  MoveArg a{};
   a.paused = paused;
-  return wl_mob_op(h, MOB_PAUSE, phy, now, a);
+  return wl_move_op(h, MOP_VEL_PAUSE, phy, now, a);
 }
 
+// The phy's model's SetPosition at `now` (ConstantVelocityHelper::SetPosition, constant-velocity-helper.cc:43-49;
+// WaypointMobilityModel / ConstantAccelerationMobilityModel::DoSetPosition).
 extern "C" int nsgpu_wifil_set_position_at(nsgpu_wifil *h, uint64_t now, uint32_t phy, double x, double y, double z) {
   if (!h || phy >= h->D.nphy) return set_error(NSGPU_EINVAL, "nsgpu_wifil_set_position_at: bad phy");
-  if (wl_pathed(h, phy)) {  // (WaypointMobilityModel / ConstantAccelerationMobilityModel::DoSetPosition)
-    PathArg a{};
-    a.w.pos[0] = x, a.w.pos[1] = y, a.w.pos[2] = z;
-    return wl_path_op(h, PATH_SET_POSITION, phy, now, a);
-  }
-  if (!wl_mobile(h, phy)) return nsgpu_wifil_set_position(h, phy, x, y, z);  // (ConstantPositionMobilityModel: no time)
-  nsgpu_mobility a{};
-  a.pos[0] = x, a.pos[1] = y, a.pos[2] = z;
-  return wl_mob_op(h, MOB_SET_POSITION, phy, now, a);
+  if (!wl_kind(h, phy)) return nsgpu_wifil_set_position(h, phy, x, y, z);  // (ConstantPositionMobilityModel: no time)
+  MoveArg a{};
+  a.w.pos[0] = x, a.w.pos[1] = y, a.w.pos[2] = z;
+  return wl_move_op(h, MOP_SET_POSITION, phy, now, a);
 }
 
 extern "C" int nsgpu_wifil_get_mobility(nsgpu_wifil *h, uint64_t now, uint32_t phy, nsgpu_mobility *out) {
   if (!h || !out || phy >= h->D.nphy) return set_error(NSGPU_EINVAL, "nsgpu_wifil_get_mobility: bad phy");
-  if (!wl_mobile(h, phy)) return set_error(NSGPU_ESTATE, "nsgpu_wifil_get_mobility: phy %u has no mobility model", phy);
-  if (int rc = wl_mob_op(h, MOB_GET, phy, now, nsgpu_mobility{})) return rc;
-  NSGPU_HIP(hipMemcpyAsync(out, h->d_mobout, sizeof(nsgpu_mobility), hipMemcpyDeviceToHost, h->s));
+  if (wl_kind(h, phy) != MOVE_VEL) return set_error(NSGPU_ESTATE, "nsgpu_wifil_get_mobility: phy %u has no mobility model", phy);
+  if (int rc = wl_move_op(h, MOP_VEL_GET, phy, now, MoveArg{})) return rc;
+  NSGPU_HIP(hipMemcpyAsync(out, &h->d_movout->vel, sizeof(nsgpu_mobility), hipMemcpyDeviceToHost, h->s));
   NSGPU_HIP(hipStreamSynchronize(h->s));
   return NSGPU_OK;
 }
 
-// ---- waypoint and acceleration mobility ----
-// One k_wl_path call on phy's model (the batch first, as wl_mob_op).
-static int wl_path_op(nsgpu_wifil *h, uint32_t op, uint32_t phy, uint64_t now, const PathArg &a) {
-  if (int rcf = wl_flush_sends(h)) return rcf;
-  hipLaunchKernelGGL(k_wl_path, dim3(1), dim3(1), 0, h->s, h->D, op, phy, (int64_t)now, a, h->d_pathout);
-  NSGPU_HIP(hipGetLastError());
-  return NSGPU_OK;
-}
-static int wl_path_remove(nsgpu_wifil *h, uint32_t phy) {
-  if (int rc = wl_path_op(h, PATH_REMOVE, phy, 0, PathArg{})) return rc;
-  h->path_kind[phy] = PATH_NONE;
-  h->n_path--;
-  return NSGPU_OK;
-}
-// The argument checks every install call makes, then the records (sized at the first install) and the phy's other
-// model, if any, removed: one model per phy.
-static int wl_path_begin(nsgpu_wifil *h, uint32_t phy, const char *what, bool install) {
-  if (!h || phy >= h->D.nphy) return set_error(NSGPU_EINVAL, "%s: bad phy", what);  // (before anything is sized)
-  if (!h->mem.empty())
-    return set_error(NSGPU_EINVAL, "%s: mobility is single-engine for now (a partitioned handle)", what);
-  if (!install) return NSGPU_OK;
-  if (h->path_kind.empty()) {
-    int rc = wl_mob_size(h);
-    if (!rc) rc = wl_alloc(h, &h->D.path, (size_t)h->D.nphy);
-    if (!rc) rc = wl_alloc(h, &h->d_pathout, 1);
-    if (rc) return rc;
-    h->path_kind.assign((size_t)h->D.nphy, PATH_NONE);
-    h->seg.resize((size_t)h->D.nphy);
-  }
-  if (h->mob_on[phy]) {
-    if (int rc = wl_mob_op(h, MOB_REMOVE, phy, 0, nsgpu_mobility{})) return rc;
-    h->mob_on[phy] = 0;
-    h->n_mob--;
-  }
-  return NSGPU_OK;
-}
-static void wl_path_mark(nsgpu_wifil *h, uint32_t phy, uint32_t kind) {
-  if (!h->path_kind[phy]) h->n_path++;
-  h->path_kind[phy] = (uint8_t)kind;
-}
 // Room for `need` slots in phy's segment of the pool (nsgpu_waypool.h), in stream order: a full pool is replaced once
 // the stream has drained (as the Matrix table grows: rare, and not on the send path), a full segment is copied to
 // the pool's end behind every kernel that reads the old one.
@@ -2554,13 +2480,13 @@ static int wl_way_put(nsgpu_wifil *h, uint64_t at, const nsgpu_waypoint *wp, uin
 }
 
 extern "C" int nsgpu_wifil_set_waypoints(nsgpu_wifil *h, uint32_t phy, const nsgpu_waypoint *wp, uint64_t n) {
-  if (int rc = wl_path_begin(h, phy, "nsgpu_wifil_set_waypoints", false)) return rc;
+  if (int rc = wl_move_begin(h, phy, "nsgpu_wifil_set_waypoints", n != 0)) return rc;
   if (n && !wp) return set_error(NSGPU_EINVAL, "nsgpu_wifil_set_waypoints: null");
   if (n > 0xffffffffull || !ascending(wp, n))
     return set_error(NSGPU_EINVAL, "nsgpu_wifil_set_waypoints: waypoints must be given in ascending time order "
                                    "(waypoint-mobility-model.cc:91 NS_ABORT_MSG_IF)");
-  if (n == 0) return wl_pathed(h, phy) ? wl_path_remove(h, phy) : NSGPU_OK;
-  if (int rc = wl_path_begin(h, phy, "nsgpu_wifil_set_waypoints", true)) return rc;
+  if (n == 0)  // (a waypoint or an acceleration model: either goes)
+    return wl_kind(h, phy) >= MOVE_WAY ? wl_move_op(h, MOP_REMOVE, phy, 0, MoveArg{}) : NSGPU_OK;
   if (int rcf = wl_flush_sends(h)) return rcf;
   WaySeg &s = h->seg[phy];
   s.cnt = 0;  // (a fresh model: nothing of the old list moves with the segment)
@@ -2569,16 +2495,14 @@ extern "C" int nsgpu_wifil_set_waypoints(nsgpu_wifil *h, uint32_t phy, const nsg
   s.cnt = (uint32_t)(n - 1);
   s.first = false, s.any = true, s.last = wp[n - 1].time;
   s.list.assign(wp, wp + n);
-  PathArg a{};
+  MoveArg a{};
   a.w = wp[0], a.off = (uint32_t)s.off, a.cnt = s.cnt;
-  if (int rc = wl_path_op(h, PATH_WAY_INSTALL, phy, 0, a)) return rc;
-  wl_path_mark(h, phy, PATH_WAY);
-  return NSGPU_OK;
+  return wl_move_op(h, MOP_WAY_INSTALL, phy, 0, a);
 }
 
 extern "C" int nsgpu_wifil_add_waypoint(nsgpu_wifil *h, uint32_t phy, const nsgpu_waypoint *wp) {
   if (!h || !wp || phy >= h->D.nphy) return set_error(NSGPU_EINVAL, "nsgpu_wifil_add_waypoint: bad phy");
-  if (wl_pathed(h, phy) != PATH_WAY) return set_error(NSGPU_ESTATE, "nsgpu_wifil_add_waypoint: phy %u has no waypoint model", phy);
+  if (wl_kind(h, phy) != MOVE_WAY) return set_error(NSGPU_ESTATE, "nsgpu_wifil_add_waypoint: phy %u has no waypoint model", phy);
   WaySeg &s = h->seg[phy];
   if (!s.first && s.any && wp->time <= s.last)
     return set_error(NSGPU_EINVAL, "nsgpu_wifil_add_waypoint: waypoints must be added in ascending time order "
@@ -2592,56 +2516,53 @@ extern "C" int nsgpu_wifil_add_waypoint(nsgpu_wifil *h, uint32_t phy, const nsgp
   }
   s.first = false, s.any = true, s.last = wp->time;
   s.list.push_back(*wp);
-  PathArg a{};
+  MoveArg a{};
   a.w = *wp, a.off = (uint32_t)s.off, a.cnt = s.cnt;
-  return wl_path_op(h, PATH_WAY_ADD, phy, 0, a);
+  return wl_move_op(h, MOP_WAY_ADD, phy, 0, a);
 }
 
 extern "C" int nsgpu_wifil_end_waypoints(nsgpu_wifil *h, uint32_t phy) {
   if (!h || phy >= h->D.nphy) return set_error(NSGPU_EINVAL, "nsgpu_wifil_end_waypoints: bad phy");
-  if (wl_pathed(h, phy) != PATH_WAY) return set_error(NSGPU_ESTATE, "nsgpu_wifil_end_waypoints: phy %u has no waypoint model", phy);
+  if (wl_kind(h, phy) != MOVE_WAY) return set_error(NSGPU_ESTATE, "nsgpu_wifil_end_waypoints: phy %u has no waypoint model", phy);
   WaySeg &s = h->seg[phy];
   s.first = true, s.any = false;
-  return wl_path_op(h, PATH_WAY_END, phy, 0, PathArg{});
+  return wl_move_op(h, MOP_WAY_END, phy, 0, MoveArg{});
 }
 
 extern "C" int nsgpu_wifil_get_waypoints(nsgpu_wifil *h, uint64_t now, uint32_t phy, nsgpu_waypoint_state *out) {
   if (!h || !out || phy >= h->D.nphy) return set_error(NSGPU_EINVAL, "nsgpu_wifil_get_waypoints: bad phy");
-  if (wl_pathed(h, phy) != PATH_WAY) return set_error(NSGPU_ESTATE, "nsgpu_wifil_get_waypoints: phy %u has no waypoint model", phy);
-  if (int rc = wl_path_op(h, PATH_WAY_GET, phy, now, PathArg{})) return rc;
-  NSGPU_HIP(hipMemcpyAsync(out, &h->d_pathout->way, sizeof(nsgpu_waypoint_state), hipMemcpyDeviceToHost, h->s));
+  if (wl_kind(h, phy) != MOVE_WAY) return set_error(NSGPU_ESTATE, "nsgpu_wifil_get_waypoints: phy %u has no waypoint model", phy);
+  if (int rc = wl_move_op(h, MOP_WAY_GET, phy, now, MoveArg{})) return rc;
+  NSGPU_HIP(hipMemcpyAsync(out, &h->d_movout->way, sizeof(nsgpu_waypoint_state), hipMemcpyDeviceToHost, h->s));
   NSGPU_HIP(hipStreamSynchronize(h->s));
   return NSGPU_OK;
 }
 
 extern "C" int nsgpu_wifil_set_acceleration(nsgpu_wifil *h, uint32_t phy, const nsgpu_accel *acc) {
-  if (int rc = wl_path_begin(h, phy, "nsgpu_wifil_set_acceleration", false)) return rc;
-  if (!acc) return wl_pathed(h, phy) ? wl_path_remove(h, phy) : NSGPU_OK;
-  if (int rc = wl_path_begin(h, phy, "nsgpu_wifil_set_acceleration", true)) return rc;
-  PathArg a{};
+  if (int rc = wl_move_begin(h, phy, "nsgpu_wifil_set_acceleration", acc != nullptr)) return rc;
+  if (!acc)  // (a waypoint or an acceleration model: either goes)
+    return wl_kind(h, phy) >= MOVE_WAY ? wl_move_op(h, MOP_REMOVE, phy, 0, MoveArg{}) : NSGPU_OK;
+  MoveArg a{};
   for (int c = 0; c < 3; c++) a.w.pos[c] = acc->pos[c], a.v[c] = acc->vel[c], a.a[c] = acc->acc[c];
-  a.base_time = acc->base_time;
-  a.off = (uint32_t)h->seg[phy].off;
-  if (int rc = wl_path_op(h, PATH_ACC_INSTALL, phy, 0, a)) return rc;
-  wl_path_mark(h, phy, PATH_ACC);
-  return NSGPU_OK;
+  a.time = acc->base_time;
+  return wl_move_op(h, MOP_ACC_INSTALL, phy, 0, a);
 }
 
 extern "C" int nsgpu_wifil_set_velocity_and_acceleration(nsgpu_wifil *h, uint64_t now, uint32_t phy, const double v[3],
                                                          const double acc[3]) {
   if (!h || !v || !acc || phy >= h->D.nphy) return set_error(NSGPU_EINVAL, "nsgpu_wifil_set_velocity_and_acceleration: bad phy");
-  if (wl_pathed(h, phy) != PATH_ACC)
+  if (wl_kind(h, phy) != MOVE_ACC)
     return set_error(NSGPU_ESTATE, "nsgpu_wifil_set_velocity_and_acceleration: phy %u has no acceleration model", phy);
-  PathArg a{};
+  MoveArg a{};
   for (int c = 0; c < 3; c++) a.v[c] = v[c], a.a[c] = acc[c];
-  return wl_path_op(h, PATH_ACC_SET, phy, now, a);
+  return wl_move_op(h, MOP_ACC_SET, phy, now, a);
 }
 
 extern "C" int nsgpu_wifil_get_acceleration(nsgpu_wifil *h, uint64_t now, uint32_t phy, nsgpu_accel *out) {
   if (!h || !out || phy >= h->D.nphy) return set_error(NSGPU_EINVAL, "nsgpu_wifil_get_acceleration: bad phy");
-  if (wl_pathed(h, phy) != PATH_ACC) return set_error(NSGPU_ESTATE, "nsgpu_wifil_get_acceleration: phy %u has no acceleration model", phy);
-  if (int rc = wl_path_op(h, PATH_ACC_GET, phy, now, PathArg{})) return rc;
-  NSGPU_HIP(hipMemcpyAsync(out, &h->d_pathout->acc, sizeof(nsgpu_accel), hipMemcpyDeviceToHost, h->s));
+  if (wl_kind(h, phy) != MOVE_ACC) return set_error(NSGPU_ESTATE, "nsgpu_wifil_get_acceleration: phy %u has no acceleration model", phy);
+  if (int rc = wl_move_op(h, MOP_ACC_GET, phy, now, MoveArg{})) return rc;
+  NSGPU_HIP(hipMemcpyAsync(out, &h->d_movout->acc, sizeof(nsgpu_accel), hipMemcpyDeviceToHost, h->s));
   NSGPU_HIP(hipStreamSynchronize(h->s));
   return NSGPU_OK;
 }

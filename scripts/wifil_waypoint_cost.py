@@ -2,8 +2,8 @@
 100x100 closed loop with the C MAC stand-in (bench.WifiLoop.run_native), Stop argv[1] s (default 0.03), in one
 process: no model, every phy on a constant-velocity model, every phy on an 8-leg waypoint list (nine waypoints spread
 over the run, so every phy crosses waypoints on the device with no host call), and none again — us per epoch (wall
-time of Simulator::Run over the nsgpu_wifil_advance calls).  While any phy has a waypoint model every SendPacket
-launches k_wl_move<true> ahead of its k_wl_rx.  Then the time of one nsgpu_wifil_add_waypoint call on an idle engine
+time of Simulator::Run over the nsgpu_wifil_advance calls).  While any phy has a model of any kind every SendPacket
+launches k_wl_move ahead of its k_wl_rx.  Then the time of one nsgpu_wifil_add_waypoint call on an idle engine
 (the enqueue of two one-block launches; the stream is drained once at the end).  The first and the last run (no
 model) must give the same digest."""
 import os

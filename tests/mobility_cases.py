@@ -1,5 +1,6 @@
-"""Scenarios of the constant-velocity mobility tests (tests/test_mobility_cpu.py, tests/test_gpu_wifi_mobility.py)
-and how the unchanged oracle pins the device.
+"""Scenarios of the constant-velocity mobility tests (tests/test_mobility_cpu.py, tests/test_gpu_wifi_mobility.py),
+how the unchanged oracle pins the device, and the plan and the device driver every mobility test shares
+(tests/waypoint_cases.py holds the scenarios with waypoint and acceleration models).
 
 nsref.wifil_replay (..., moves=...) schedules the sends, then MobilityModel::SetPosition closures, then Stop.
   expected run: for every event of the scenario in dispatch order — a send k: one move at ts[k] - 1 per phy whose
@@ -9,12 +10,17 @@ nsref.wifil_replay (..., moves=...) schedules the sends, then MobilityModel::Set
     at the place of every move, in the same schedule order — a no-op for a send's moves, the real call
     (wifi_set_velocity / wifi_pause / wifi_set_position / wifi_get_mobility) for a course change — so the uids,
     the dispatch count and the epochs' cuts are those of the expected run.
-The static control is the expected run with every move carrying the phy's position at setup."""
+The static control is the expected run with every move carrying the phy's position at setup.
+
+A case: dict (phys, specs, sends, course, stop_ns[, burst]).  specs[j]: None (constant position) | cv (vel, paused,
+last_update) | ("wp", [(t ns, pos)]) | ("acc", vel, acc) (m_basePosition: the phy's setup position, m_baseTime 0).
+course: the events of waypoint_ref.walk other than sends."""
 import numpy as np
 
 import nsref
 import wifi
-from mobility_ref import CvModel, send_updates, walk
+from mobility_ref import CvModel, send_updates
+from waypoint_ref import AccelModel, WaypointModel, walk
 
 SIZE, DBM, MODE, PREAMBLE = 200, 16.0206, wifi.DSSS_1M, wifi.PREAMBLE_LONG
 PHY_FIELDS = ("rx", "sync", "drop_rx", "drop_tx", "drop_ed", "cca_switches", "end", "end_cancelled")
@@ -30,10 +36,13 @@ def velocities(rng, n, vmax=150.0):
     return [tuple(float(c) for c in rng.uniform(-vmax, vmax, 3) * (1.0, 1.0, 0.1)) for _ in range(n)]
 
 
+def cv(vel, paused=False, last_update=0):
+    """A constant-velocity spec."""
+    return ("cv", tuple(vel), paused, last_update)
+
+
 def make(x, y, z, channel, specs, sends, course=(), stop_ns=None):
-    """specs[j]: None (constant position) or dict (vel, paused, last_update).  sends: [(ts, phy)] in schedule
-    order, ts not decreasing.  course: events of
-    mobility_ref.walk other than sends."""
+    """sends: [(ts, phy)] in schedule order, ts not decreasing."""
     ph = wifi.LoopPhys(x, y, z, channel=channel, tx_cap=1024)
     sends = [(int(t), int(p)) for t, p in sends]
     stop_ns = int(stop_ns if stop_ns is not None else sends[-1][0] + 30_000_000)
@@ -46,9 +55,9 @@ def grid_case(seed, channel=None, course=(), n_sends=36):
     rng = np.random.default_rng(seed)
     x, y, z = wifi.grid(4, 60.0)
     vel = velocities(rng, 16)
-    specs = [dict(vel=v, paused=False, last_update=0) for v in vel]
-    specs[2]["vel"] = (0.0, 0.0, 0.0)
-    specs[6]["paused"] = True
+    specs = [cv(v) for v in vel]
+    specs[2] = cv((0.0, 0.0, 0.0))
+    specs[6] = cv(vel[6], paused=True)
     specs[11] = None
     ts = send_times(rng, n_sends)
     return make(x, y, z, channel, specs, [(ts[k], 5 * k % 16) for k in range(n_sends)], course)
@@ -66,7 +75,7 @@ def block_edge_case(seed):
     rng = np.random.default_rng(seed)
     i = np.arange(300)
     x, y, z = (i % 20) * 60.0, (i // 20) * 60.0, np.zeros(300)
-    specs = [dict(vel=v, paused=False, last_update=0) for v in velocities(rng, 300)]
+    specs = [cv(v) for v in velocities(rng, 300)]
     ts = send_times(rng, 12)
     return make(x, y, z, None, specs, [(ts[k], 83 * k % 300) for k in range(12)])
 
@@ -93,8 +102,8 @@ def burst_case(seed):
     closures."""
     rng = np.random.default_rng(seed)
     x, y, z = wifi.grid(4, 60.0)
-    specs = [dict(vel=v, paused=False, last_update=0) for v in velocities(rng, 16)]
-    specs[0]["vel"] = (150.0, 140.0, 0.0)
+    specs = [cv(v) for v in velocities(rng, 16)]
+    specs[0] = cv((150.0, 140.0, 0.0))
     t0 = 40_000_000
     sends = [(t0, p) for p in range(10)] + [(t0 + 55_000_123, 0), (t0 + 101_000_456, 13)]
     c = make(x, y, z, None, specs, sends, course=[("pos", t0, 0, (900.0, 700.0, 0.0))])
@@ -114,29 +123,36 @@ def events_of(case):
 
 def models_of(case):
     ph = case["phys"]
-    return [None if s is None else CvModel((ph.x[j], ph.y[j], ph.z[j]), s["vel"], s["paused"], s["last_update"])
-            for j, s in enumerate(case["specs"])]
+    out = []
+    for j, s in enumerate(case["specs"]):
+        p = (float(ph.x[j]), float(ph.y[j]), float(ph.z[j]))
+        out.append(None if s is None else CvModel(p, *s[1:]) if s[0] == "cv" else WaypointModel(s[1]) if s[0] == "wp"
+                   else AccelModel(p, s[1], s[2], base_time=0))
+    return out
 
 
 def plan(case, update_rule=send_updates):
-    """Walks the restatement over the scenario.  Returns dict: events, records (mobility_ref.walk's), moves (the
-    expected run's), slots (the device run's closure per move: None or the course event), final (every model's
-    (position, velocity) at the final accumulation point stop_ns), models."""
+    """Walks the restatements over the scenario.  Returns dict: events, records ((event, {phy: position after it}) per
+    event), reads (per record: what a *_get returned, else None), moves (the expected run's), slots (the device run's
+    closure per move: None, or (course event, the phy's position after it)), final ({phy: the model's read at the
+    final accumulation point stop_ns}), models (as the walk left them)."""
     ph = case["phys"]
     models = models_of(case)
     events = events_of(case)
-    records = walk(models, ph.channel, events, update_rule)
+    start = [(float(ph.x[j]), float(ph.y[j]), float(ph.z[j])) for j in range(ph.n_phy)]
+    walked = walk(models, ph.channel, events, update_rule, positions=start)
     moves, slots = [], []
-    for ev, touched in records:
+    for ev, touched, _read in walked:
         if ev[0] == "send":
             for j in sorted(touched):
                 moves.append((ev[1] - 1, j, touched[j]))
                 slots.append(None)
         else:
             moves.append((ev[1], ev[2], touched[ev[2]]))
-            slots.append(ev)
+            slots.append((ev, touched[ev[2]]))
     final = {j: m.get(case["stop_ns"]) for j, m in enumerate(models) if m is not None}
-    return dict(events=events, records=records, moves=moves, slots=slots, final=final, models=models)
+    return dict(events=events, records=[(ev, touched) for ev, touched, _read in walked],
+                reads=[read for _ev, _touched, read in walked], moves=moves, slots=slots, final=final, models=models)
 
 
 def run_oracle(case, moves, log_cap=1 << 16):
@@ -195,15 +211,31 @@ def closed_form(case):
     for j, sp in enumerate(case["specs"]):
         if sp is None:
             continue
-        v = (0.0, 0.0, 0.0) if sp["paused"] else sp["vel"]
+        v = (0.0, 0.0, 0.0) if sp[2] else sp[1]
         out[j] = ((float(ph.x[j]) + v[0] * s, float(ph.y[j]) + v[1] * s, float(ph.z[j]) + v[2] * s), v)
     return out
 
 
 # ---------------------------------------------------------------- the device run
+def install(lp, j, spec, pos):
+    if spec[0] == "cv":
+        lp.set_mobility(j, pos, spec[1], paused=spec[2], last_update=spec[3])
+    elif spec[0] == "wp":
+        lp.set_waypoints(j, spec[1])
+    else:
+        lp.set_acceleration(j, pos, spec[1], spec[2], base_time=0)
+
+
+def read_final(lp, now, j, kind):
+    if kind == "cv":
+        return lp.get_mobility(now, j)[:2]
+    return lp.get_waypoints(now, j) if kind == "wp" else lp.get_acceleration(now, j)
+
+
 def run_device(case, pl, log_cap=1 << 16, listen=(), notify=(), prepare=None):
-    """The scenario on the device PHY with native mobility.  Returns (log, ends, phys, tot, final, reads, notes, keep):
-    final = {phy: (position, velocity)} from get_mobility at stop_ns, reads = the mid-run wifi_get_mobility results."""
+    """The scenario on the device PHY with the models installed.  Returns dict: four (log, ends, phys, tot: for
+    equal_oracle), final ({phy: the read of its model's kind at stop_ns}), reads ([(event, result)] of the mid-run
+    reads), notes, sim, lp."""
     import nsgpu
     ph = case["phys"]
     sim = nsgpu.Sim()
@@ -212,9 +244,11 @@ def run_device(case, pl, log_cap=1 << 16, listen=(), notify=(), prepare=None):
     sim.set_log(log_cap)
     if prepare:
         prepare(sim, lp)
+    kind = {}
     for j, s in enumerate(case["specs"]):
         if s is not None:
-            lp.set_mobility(j, (ph.x[j], ph.y[j], ph.z[j]), s["vel"], paused=s["paused"], last_update=s["last_update"])
+            install(lp, j, s, (ph.x[j], ph.y[j], ph.z[j]))
+            kind[j] = s[0]
     handbacks = []
     if listen:
         sim.wifi_set_end_handler(lambda e: handbacks.append((int(e["ts"]), int(e["uid"]))))
@@ -222,46 +256,86 @@ def run_device(case, pl, log_cap=1 << 16, listen=(), notify=(), prepare=None):
             sim.wifi_listen(p)
     for p in notify:
         sim.wifi_notify(p)
-    reads = []
+    reads, failures = [], []
 
-    def course(ev):
-        kind, _t, phy = ev[0], ev[1], ev[2]
+    def course(slot):
+        ev, after = slot
+        k, _t, phy = ev[0], ev[1], ev[2]
         assert sim.now() == ev[1]
-        if kind == "vel":
-            sim.wifi_set_velocity(phy, ev[3])
-        elif kind == "pause":
-            sim.wifi_pause(phy, ev[3])
-        elif kind == "pos":
+        if k == "pos":
             sim.wifi_set_position(phy, *ev[3])
-        else:
+        elif k == "vel":
+            sim.wifi_set_velocity(phy, ev[3])
+        elif k == "pause":
+            sim.wifi_pause(phy, ev[3])
+        elif k == "get":
             reads.append((ev, sim.wifi_get_mobility(phy)))
+        elif k == "wp_add":
+            sim.wifi_add_waypoint(phy, *ev[3])
+        elif k == "wp_end":
+            sim.wifi_end_waypoints(phy)
+        elif k == "wp_get":
+            reads.append((ev, sim.wifi_get_waypoints(phy)))
+        elif k == "acc_set":
+            sim.wifi_set_velocity_and_acceleration(phy, ev[3], ev[4])
+        elif k == "acc_get":
+            reads.append((ev, sim.wifi_get_acceleration(phy)))
+        elif k == "install_wp":
+            sim.wifi_set_waypoints(phy, ev[3])
+            kind[phy] = "wp"
+        elif k == "install_acc":
+            sim.wifi_set_acceleration(phy, ev[3], ev[4], ev[5])
+            kind[phy] = "acc"
+        elif k == "install_cv":  # (ConstantVelocityHelper takes its position with the install: where the phy is)
+            lp.set_mobility(phy, after, ev[3], paused=False, last_update=sim.now())
+            kind[phy] = "cv"
+        elif k == "remove":
+            if kind[phy] == "wp":
+                sim.wifi_set_waypoints(phy, [])
+            elif kind[phy] == "acc":
+                sim.wifi_set_acceleration(phy, None)
+            else:
+                lp.set_mobility(phy, None, None)
+            del kind[phy]
+        else:
+            raise ValueError(k)
+
+    def guarded(fn):
+        def run():
+            try:
+                fn()
+            except BaseException as e:  # (an exception does not cross the C callback: keep it for the test)
+                failures.append(e)
+        return run
 
     send = lambda p: sim.wifi_send(p, SIZE, DBM, MODE, PREAMBLE)
     nb = case.get("burst", 0)
-    inline = [ev for ev in case["course"] if nb and ev[1] == case["sends"][0][0]]
+    inline = [s for s in pl["slots"] if s is not None and nb and s[0][1] == case["sends"][0][0]]
     for k, (t, p) in enumerate(case["sends"]):
-        if k == 0 and nb:  # one closure makes the first nb sends; the others' places are held by no-ops
-            sim.schedule(t, lambda: [send(q) for _t, q in case["sends"][:nb]] + [course(ev) for ev in inline])
-        elif k < nb:
+        if k == 0 and nb:  # one closure makes the first nb sends, then the course calls of their time
+            sim.schedule(t, guarded(lambda: [send(q) for _t, q in case["sends"][:nb]] + [course(s) for s in inline]))
+        elif k < nb:  # (the others' places are held by no-ops)
             sim.schedule(t, lambda: None)
         else:
-            sim.schedule(t, (lambda p=p: lambda: send(p))())
+            sim.schedule(t, guarded((lambda p=p: lambda: send(p))()))
     for (t, _j, _p), slot in zip(pl["moves"], pl["slots"]):
-        sim.schedule(t, (lambda: None) if slot is None or slot in inline else (lambda ev=slot: lambda: course(ev))())
+        sim.schedule(t, (lambda: None) if slot is None or slot in inline else guarded((lambda s=slot: lambda: course(s))()))
     sim.stop(case["stop_ns"])
     sim.run()
+    assert not failures, failures
     digest = sim.host_stats()[2]
     k = min(sim.dispatched(), log_cap)
     log = (sim.log[0][:k].copy(), sim.log[1][:k].copy(), sim.log[2][:k].copy())
     tot = dict(dispatched=sim.dispatched(), digest=digest, next_uid=sim.next_uid(), handbacks=handbacks)
-    final = {j: lp.get_mobility(case["stop_ns"], j)[:2] for j in pl["final"]}
-    return log, lp.read_ends(), lp.read_phys(), tot, final, reads, lp.read_notes(), (sim, lp)
+    final = {j: read_final(lp, case["stop_ns"], j, kd) for j, kd in kind.items()}
+    return dict(four=(log, lp.read_ends(), lp.read_phys(), tot), final=final, reads=reads, notes=lp.read_notes(), sim=sim,
+                lp=lp)
 
 
 def equal_oracle(g, o):
     """The device run against the expected run: full pop log, dispatch count, digest, next uid, per-phy counters, end
     records' integer fields exactly; snr / per / rx_w as the closed-loop tests compare them (device libm vs glibc)."""
-    glog, gends, gphys, gtot = g[:4]
+    glog, gends, gphys, gtot = g
     olog, oends, ophys, otot = o
     for f in ("dispatched", "digest", "next_uid"):
         assert gtot[f] == otot[f], (f, gtot[f], otot[f])

@@ -25,9 +25,9 @@ def check(case, **kw):
     pl = mc.plan(case)
     o = mc.run_oracle(case, pl["moves"])
     g = mc.run_device(case, pl, **kw)
-    mc.equal_oracle(g, o)
-    mc.equal_final(g[4], pl["final"])
-    g[7][1].close()
+    mc.equal_oracle(g["four"], o)
+    mc.equal_final(g["final"], pl["final"])
+    g["lp"].close()
     return pl, o, g
 
 
@@ -50,12 +50,12 @@ def test_block_edge_300_phys():
 def test_course_changes_and_a_mid_run_read():
     case = mc.course_case(SEEDS["course"])
     pl, _o, g = check(case)
-    reads = g[5]
+    reads = g["reads"]
     assert len(reads) == 1
     (ev, (pos, vel, paused)), = reads
     want = [t for e, t in pl["records"] if e == ev][0][12]
-    assert pos == want and not paused and vel == case["specs"][12]["vel"]
-    assert g[4][9][1] == (0.0, 0.0, 0.0) and g[4][3][1] == (0.0, 120.0, 0.0)
+    assert pos == want and not paused and vel == case["specs"][12][1]
+    assert g["final"][9][1] == (0.0, 0.0, 0.0) and g["final"][3][1] == (0.0, 120.0, 0.0)
 
 
 def test_more_than_nsend_sends_in_one_closure():
@@ -67,9 +67,9 @@ def test_more_than_nsend_sends_in_one_closure():
 def test_with_hand_back_and_notes():
     case = mc.grid_case(SEEDS["grid"])
     _pl, o, g = check(case, listen=(1, 14), notify=(4, 9))
-    ends, phys, notes = o[1], o[2], g[6]
+    ends, phys, notes = o[1], o[2], g["notes"]
     live = ends[((ends["flags"] & wifi.END_CANCELLED) == 0) & np.isin(ends["phy"], (1, 14))]
-    assert g[3]["handbacks"] == [(int(e["ts"]), int(e["uid"])) for e in live] and len(live) > 5
+    assert g["four"][3]["handbacks"] == [(int(e["ts"]), int(e["uid"])) for e in live] and len(live) > 5
     assert set(np.unique(notes["phy"])) == {4, 9}
     for p in (4, 9):
         mine = notes[notes["phy"] == p]
@@ -116,22 +116,22 @@ def test_static_control_install_then_remove():
     pl = mc.plan(case)
     o = mc.run_oracle(case, mc.static_moves(case, pl["moves"]))
     none = dict(case, specs=[None] * 16)
-    pl_none = dict(pl, final={})
 
     def install_remove(_sim, lp):
         for j, s in enumerate(case["specs"]):
             if s is not None:
-                lp.set_mobility(j, (case["phys"].x[j], case["phys"].y[j], case["phys"].z[j]), s["vel"])
+                lp.set_mobility(j, (case["phys"].x[j], case["phys"].y[j], case["phys"].z[j]), s[1])
         for j in range(16):
             lp.set_mobility(j, None, None)
 
-    a = mc.run_device(none, pl_none)
-    b = mc.run_device(none, pl_none, prepare=install_remove)
+    ga = mc.run_device(none, pl)
+    gb = mc.run_device(none, pl, prepare=install_remove)
+    a, b = ga["four"], gb["four"]
     mc.equal_oracle(a, o)
     mc.equal_oracle(b, o)
     for p, q in zip(a[0], b[0]):
         assert np.array_equal(p, q)
     assert a[3]["digest"] == b[3]["digest"]
     assert np.array_equal(a[1], b[1])
-    a[7][1].close()
-    b[7][1].close()
+    ga["lp"].close()
+    gb["lp"].close()

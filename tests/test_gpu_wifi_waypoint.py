@@ -1,5 +1,5 @@
 """Waypoint and ConstantAcceleration mobility of the closed-loop Wi-Fi PHY on the device (nsgpu_wifil_set_waypoints /
-nsgpu_wifil_set_acceleration and their neighbours; k_wl_move<true> ahead of every send's k_wl_rx).  Each scenario of
+nsgpu_wifil_set_acceleration and their neighbours; k_wl_move ahead of every send's k_wl_rx).  Each scenario of
 tests/waypoint_cases.py runs on the device with the models installed and on the unchanged oracle with the restated
 positions (tests/waypoint_ref.py) written by SetPosition closures: full pop log, dispatch count, digest, next uid,
 per-phy counters and the end records' integer fields are equal, snr / per / rx_w within the closed-loop tests' 1e-9
@@ -37,6 +37,7 @@ def check(name, **kw):
     want_reads = [(ev, r) for ev, _t, r in pl["records"] if r is not None]
     assert len(g["reads"]) == len(want_reads)
     for (ev, got), (wev, want) in zip(g["reads"], want_reads):
+        got = got[:2] if ev[0] == "get" else got  # (get_mobility's paused flag: not part of the restatement's read)
         assert ev == wev and got == want, (ev, got, want)
     g["lp"].close()
     return case, pl, o, g
@@ -196,3 +197,51 @@ def test_refusals():
     assert L.nsgpu_sim_wifi_set_waypoints(sim.h, 0, wp3, 3) == ESTATE  # no PHY attached
     assert L.nsgpu_sim_wifi_get_acceleration(sim.h, 0, C.byref(acc)) == ESTATE
     sim.close()
+
+
+def test_remove_calls_across_kinds_and_a_reinstall():
+    """Each remove call on a phy that holds another kind's model — set_mobility (NULL) removes a constant-velocity model
+    only; set_waypoints (n = 0) and set_acceleration (NULL) remove a waypoint or an acceleration model, whichever the
+    phy has, and no constant-velocity one — with what is installed afterwards read back; and a phy that goes waypoint ->
+    constant velocity -> waypoint with a longer list than its segment held: the segment is reused and grown."""
+    ph = wc.grid_case(wc.SEEDS["grid"])["phys"]
+    L = nsgpu.lib()
+    lp = wifi.LoopPhy(ph)
+    st, acc, mob = wifi.WaypointState(), wifi.Accel(), wifi.Mobility()
+    S = 1_000_000_000
+    way = [(0, (1.0, 2.0, 3.0)), (2 * S, (5.0, 2.0, 3.0)), (4 * S, (5.0, 6.0, 3.0))]
+    # a waypoint phy survives set_mobility (NULL); set_acceleration (NULL) removes its model
+    lp.set_waypoints(3, way)
+    assert L.nsgpu_wifil_set_mobility(lp.h, 3, None) == 0
+    assert lp.get_waypoints(3 * S, 3) == WaypointModel(way).get(3 * S)
+    assert L.nsgpu_wifil_set_position(lp.h, 3, 0.0, 0.0, 0.0) == ESTATE
+    assert L.nsgpu_wifil_set_acceleration(lp.h, 3, None) == 0
+    assert L.nsgpu_wifil_get_waypoints(lp.h, 0, 3, C.byref(st)) == ESTATE
+    assert L.nsgpu_wifil_set_position(lp.h, 3, 0.0, 0.0, 0.0) == 0
+    # a constant-velocity phy survives set_waypoints (n = 0) and set_acceleration (NULL)
+    lp.set_mobility(5, (1.0, 1.0, 1.0), (1.0, 0.0, 0.0))
+    assert L.nsgpu_wifil_set_waypoints(lp.h, 5, None, 0) == 0
+    assert L.nsgpu_wifil_set_acceleration(lp.h, 5, None) == 0
+    assert lp.get_mobility(S, 5) == ((2.0, 1.0, 1.0), (1.0, 0.0, 0.0), False)
+    assert L.nsgpu_wifil_set_position(lp.h, 5, 0.0, 0.0, 0.0) == ESTATE
+    # an acceleration phy survives set_mobility (NULL); set_waypoints (n = 0) removes its model
+    lp.set_acceleration(6, (0.0, 0.0, 0.0), (1.0, 0.0, 0.0), (2.0, 0.0, 0.0))
+    assert L.nsgpu_wifil_set_mobility(lp.h, 6, None) == 0
+    a = lp.get_acceleration(2 * S, 6)
+    assert a["now_pos"] == (6.0, 0.0, 0.0) and a["now_vel"] == (5.0, 0.0, 0.0) and a["base_time"] == 0
+    assert L.nsgpu_wifil_set_waypoints(lp.h, 6, None, 0) == 0
+    assert L.nsgpu_wifil_get_acceleration(lp.h, 0, 6, C.byref(acc)) == ESTATE
+    assert L.nsgpu_wifil_set_position(lp.h, 6, 0.0, 0.0, 0.0) == 0
+    # waypoint -> constant velocity -> waypoint, the second list longer than the first one's segment (four slots)
+    rng = np.random.default_rng(wc.SEEDS["calls"])
+    lp.set_waypoints(9, way[:2])
+    lp.set_mobility(9, (7.0, 7.0, 7.0), (1.0, 2.0, 3.0))
+    assert L.nsgpu_wifil_get_waypoints(lp.h, 0, 9, C.byref(st)) == ESTATE
+    longer = wc.path(rng, (3.0, 4.0, 5.0), [q * S + q * q for q in range(1, 10)])
+    lp.set_waypoints(9, longer)
+    assert L.nsgpu_wifil_get_mobility(lp.h, 0, 9, C.byref(mob)) == ESTATE
+    want = WaypointModel(longer)
+    for t in (longer[0][0], 3 * S + S // 3, 7 * S + S // 7, 8 * S + 5):  # (each read is an Update: in time order)
+        assert lp.get_waypoints(t, 9) == want.get(t), t
+    assert want.get(8 * S + 5)["left"] == 1
+    lp.close()

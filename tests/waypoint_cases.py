@@ -4,16 +4,14 @@ restated positions (tests/waypoint_ref.py) carried in as SetPosition closures â€
 updates at it, one at the time of every course event â€” and the device runs the same sends with the models installed,
 a no-op closure at the place of every send's move and the real call at the place of every course event.
 
-A case: dict (phys, specs, sends, course, stop_ns[, burst]).  specs[j]: None (constant position) | ("cv", vel) |
-("wp", [(t ns, pos)]) | ("acc", vel, acc) (m_basePosition: the phy's setup position, m_baseTime 0).  course: the events
-of waypoint_ref.walk other than sends."""
+The case's form, the plan and the device driver (install, run_device) are mobility_cases'."""
 import numpy as np
 
 import mobility_cases as mc
-import nsgpu
 import wifi
+from mobility_cases import install, run_device  # noqa: F401
 from mobility_ref import CvModel, send_updates
-from waypoint_ref import AccelModel, WaypointModel, walk
+from waypoint_ref import WaypointModel
 
 SEEDS = dict(grid=4101, channels=4102, blocks=4103, calls=4104, burst=4105)
 
@@ -41,7 +39,7 @@ def grid_case(seed, channel=None, course=(), n_sends=36):
     pos = lambda j: (float(x[j]), float(y[j]), float(z[j]))
     specs = [None] * 16
     for j, v in zip((1, 5, 9, 13), mc.velocities(rng, 4, 60.0)):
-        specs[j] = ("cv", v)
+        specs[j] = mc.cv(v)
     for j in (2, 6, 10):
         specs[j] = ("acc", mc.velocities(rng, 1, 30.0)[0], mc.velocities(rng, 1, 40.0)[0])
     specs[0] = ("wp", path(rng, pos(0), [0]))
@@ -65,7 +63,7 @@ def channels_case(seed):
 
 
 def blocks_case(seed):
-    """300 phys (20 x 15, 60 m pitch), all on four-entry waypoint lists, 12 sends: k_wl_move<true> runs two blocks, the
+    """300 phys (20 x 15, 60 m pitch), all on four-entry waypoint lists, 12 sends: k_wl_move runs two blocks, the
     second partial."""
     rng = np.random.default_rng(seed)
     i = np.arange(300)
@@ -137,41 +135,10 @@ def burst_case(seed):
 CASES = dict(grid=grid_case, channels=channels_case, blocks=blocks_case, calls=calls_case, burst=burst_case)
 
 
-def models_of(case):
-    ph = case["phys"]
-    out = []
-    for j, s in enumerate(case["specs"]):
-        p = (float(ph.x[j]), float(ph.y[j]), float(ph.z[j]))
-        out.append(None if s is None else CvModel(p, s[1], paused=False, last_update=0) if s[0] == "cv"
-                   else WaypointModel(s[1]) if s[0] == "wp" else AccelModel(p, s[1], s[2], base_time=0))
-    return out
-
-
-def final_of(m, stop):
-    """What the device's read of the model's kind returns at `stop`."""
-    return m.get(stop)
-
-
 def plan(case, update_rule=send_updates):
-    """mobility_cases.plan over mixed models: events, records (waypoint_ref.walk's), moves (the expected run's), slots
-    (the device run's closure per move: None, or (course event, the phy's position after it)), final ({phy: the
-    model's read at stop_ns}), models (as the walk left them)."""
-    ph = case["phys"]
-    models = models_of(case)
-    events = mc.events_of(case)
-    start = [(float(ph.x[j]), float(ph.y[j]), float(ph.z[j])) for j in range(ph.n_phy)]
-    records = walk(models, ph.channel, events, update_rule, positions=start)
-    moves, slots = [], []
-    for ev, touched, _read in records:
-        if ev[0] == "send":
-            for j in sorted(touched):
-                moves.append((ev[1] - 1, j, touched[j]))
-                slots.append(None)
-        else:
-            moves.append((ev[1], ev[2], touched[ev[2]]))
-            slots.append((ev, touched[ev[2]]))
-    final = {j: final_of(m, case["stop_ns"]) for j, m in enumerate(models) if m is not None}
-    return dict(events=events, records=records, moves=moves, slots=slots, final=final, models=models)
+    """mobility_cases.plan, each record with its read: (event, {phy: position after it}, read)."""
+    pl = mc.plan(case, update_rule)
+    return dict(pl, records=[(ev, touched, read) for (ev, touched), read in zip(pl["records"], pl["reads"])])
 
 
 def margins(case, pl):
@@ -180,110 +147,3 @@ def margins(case, pl):
 
 def kind_of(m):
     return None if m is None else "cv" if isinstance(m, CvModel) else "wp" if isinstance(m, WaypointModel) else "acc"
-
-
-# ---------------------------------------------------------------- the device run
-def install(lp, j, spec, pos):
-    if spec[0] == "cv":
-        lp.set_mobility(j, pos, spec[1], paused=False, last_update=0)
-    elif spec[0] == "wp":
-        lp.set_waypoints(j, spec[1])
-    else:
-        lp.set_acceleration(j, pos, spec[1], spec[2], base_time=0)
-
-
-def read_final(lp, now, j, kind):
-    if kind == "cv":
-        return lp.get_mobility(now, j)[:2]
-    return lp.get_waypoints(now, j) if kind == "wp" else lp.get_acceleration(now, j)
-
-
-def run_device(case, pl, log_cap=1 << 16, prepare=None):
-    """The scenario on the device PHY with the models installed.  Returns dict: log, ends, phys, tot (mobility_cases'
-    four, for mc.equal_oracle), final ({phy: the read of its model's kind at stop_ns}), reads ([(event, result)] of the
-    mid-run reads), sim, lp."""
-    ph = case["phys"]
-    sim = nsgpu.Sim()
-    lp = wifi.LoopPhy(ph)
-    sim.attach_wifi(lp)
-    sim.set_log(log_cap)
-    if prepare:
-        prepare(sim, lp)
-    kind = {}
-    for j, s in enumerate(case["specs"]):
-        if s is not None:
-            install(lp, j, s, (ph.x[j], ph.y[j], ph.z[j]))
-            kind[j] = s[0]
-    reads, failures = [], []
-
-    def course(slot):
-        ev, after = slot
-        k, _t, phy = ev[0], ev[1], ev[2]
-        assert sim.now() == ev[1]
-        if k == "pos":
-            sim.wifi_set_position(phy, *ev[3])
-        elif k == "vel":
-            sim.wifi_set_velocity(phy, ev[3])
-        elif k == "pause":
-            sim.wifi_pause(phy, ev[3])
-        elif k == "get":
-            reads.append((ev, sim.wifi_get_mobility(phy)[:2]))
-        elif k == "wp_add":
-            sim.wifi_add_waypoint(phy, *ev[3])
-        elif k == "wp_end":
-            sim.wifi_end_waypoints(phy)
-        elif k == "wp_get":
-            reads.append((ev, sim.wifi_get_waypoints(phy)))
-        elif k == "acc_set":
-            sim.wifi_set_velocity_and_acceleration(phy, ev[3], ev[4])
-        elif k == "acc_get":
-            reads.append((ev, sim.wifi_get_acceleration(phy)))
-        elif k == "install_wp":
-            sim.wifi_set_waypoints(phy, ev[3])
-            kind[phy] = "wp"
-        elif k == "install_acc":
-            sim.wifi_set_acceleration(phy, ev[3], ev[4], ev[5])
-            kind[phy] = "acc"
-        elif k == "install_cv":  # (ConstantVelocityHelper takes its position with the install: where the phy is)
-            lp.set_mobility(phy, after, ev[3], paused=False, last_update=sim.now())
-            kind[phy] = "cv"
-        elif k == "remove":
-            if kind[phy] == "wp":
-                sim.wifi_set_waypoints(phy, [])
-            elif kind[phy] == "acc":
-                sim.wifi_set_acceleration(phy, None)
-            else:
-                lp.set_mobility(phy, None, None)
-            del kind[phy]
-        else:
-            raise ValueError(k)
-
-    def guarded(fn):
-        def run():
-            try:
-                fn()
-            except BaseException as e:  # (an exception does not cross the C callback: keep it for the test)
-                failures.append(e)
-        return run
-
-    send = lambda p: sim.wifi_send(p, mc.SIZE, mc.DBM, mc.MODE, mc.PREAMBLE)
-    nb = case.get("burst", 0)
-    inline = [s for s in pl["slots"] if s is not None and nb and s[0][1] == case["sends"][0][0]]
-    for k, (t, p) in enumerate(case["sends"]):
-        if k == 0 and nb:  # one closure makes the first nb sends, then the course calls of their time
-            sim.schedule(t, guarded(lambda: [send(q) for _t, q in case["sends"][:nb]] + [course(s) for s in inline]))
-        elif k < nb:
-            sim.schedule(t, lambda: None)
-        else:
-            sim.schedule(t, guarded((lambda p=p: lambda: send(p))()))
-    for (t, _j, _p), slot in zip(pl["moves"], pl["slots"]):
-        sim.schedule(t, (lambda: None) if slot is None or slot in inline else guarded((lambda s=slot: lambda: course(s))()))
-    sim.stop(case["stop_ns"])
-    sim.run()
-    assert not failures, failures
-    digest = sim.host_stats()[2]
-    k = min(sim.dispatched(), log_cap)
-    log = (sim.log[0][:k].copy(), sim.log[1][:k].copy(), sim.log[2][:k].copy())
-    tot = dict(dispatched=sim.dispatched(), digest=digest, next_uid=sim.next_uid(), handbacks=[])
-    final = {j: read_final(lp, case["stop_ns"], j, kd) for j, kd in kind.items()}
-    return dict(four=(log, lp.read_ends(), lp.read_phys(), tot), final=final, reads=reads, sim=sim, lp=lp)
