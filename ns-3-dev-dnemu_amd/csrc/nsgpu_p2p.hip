@@ -182,7 +182,8 @@ struct Ctl {
   uint64_t rnext;
   uint32_t rtrim, pad5;
   // ---- deferred dispatch accounting (single wide engine, nsgpu_p2p_win.h "deferred windows") ----
-  uint64_t acc_tc, acc_tinl;  // this window's children / inline children (k2_handle accumulates)
+  uint64_t acc_tc, acc_tinl;  // this window's children / inline children (k2_handle accumulates; the deferred
+                              // pipeline's k2_handle keeps them in its blocks' partial records instead: Part)
   uint32_t pdf;               // the window the next k2_pa appends is staged (1) or appended from sinfo (0)
   uint32_t sflag;             // k2_pa staged a window for df_sdef: 1 | (its window index & 3) << 1 (k2_pa writes
                               // it every window; df_sdef's blocks only read it)
@@ -206,9 +207,28 @@ struct Ctl {
   // ---- hub windows of the narrow engines: the hub events' stateless node parts by their slots' threads ----
   uint32_t hub_rdy;    // holder blocks done with them (k2_pa zeroes it; the hub blocks wait for NHB)
   uint32_t hub_ser;    // some hub event's node part touches node state (its hub block runs those serially)
+  // ---- the deferred pipeline's allocation word: the forming window's slots | its fresh-buffer entries << 32 (one
+  // returned atomic a block where W and nF take one each; W and nF stay 0 while that pipeline runs) ----
+  uint64_t wnf;
 };
 
 static_assert(offsetof(Ctl, prep) == offsetof(Ctl, W) + 12 && offsetof(Ctl, W) % 16 == 0, "the X0 payload");
+
+// Per-block partials of the deferred pipeline's reductions (single wide engine): a block of k2_pa / a holder or
+// hub block of k2_handle stores its minima and child totals here with plain stores, and k2_rank's bookkeeping
+// block folds them into red[rt] and the window's totals (df_fold) — the blocks' same-line atomics all landed at
+// the kernel's end and the kernel could not retire before they drained.  One record per 128-B line; empty
+// ({~0, ~0, ~0, 0}: nothing published) between windows.  The two arrays (pa_part by k2_pa's block, hd_part by
+// k2_handle's) lie behind the run control in its allocation: P2PDev takes no further pointer (see hub_slot).
+struct Part {
+  uint64_t tmin, wend, wendw;
+  uint64_t tot;  // the block's children | inline children << 32 (k2_handle)
+};
+constexpr size_t PART_LINE = 128;
+constexpr size_t CTL_PARTS_OFF = (sizeof(Ctl) + PART_LINE - 1) / PART_LINE * PART_LINE;
+__host__ __device__ __forceinline__ Part *part_rec(Ctl *C, uint32_t i) {
+  return reinterpret_cast<Part *>(reinterpret_cast<char *>(C) + CTL_PARTS_OFF + (size_t)i * PART_LINE);
+}
 
 // Device-resident model + engine state (all pointers are HBM).  Passed to the kernels by value.
 // A window record's place in the dispatch order, for the wide windows' ranking (k2_rank): the chain of
@@ -1166,6 +1186,48 @@ __device__ __forceinline__ void publish_min(Red &R, uint64_t tmn, uint64_t wnd, 
   if (wnd != ~0ull) atomicMin((unsigned long long *)&R.wend, (unsigned long long)wnd);
   if (WIDE && wndw != ~0ull) atomicMin((unsigned long long *)&R.wendw, (unsigned long long)wndw);
 }
+// The deferred pipeline's publish_min: the same reduction (and the sum of the threads' packed child totals
+// `tot`), then one lane stores the block's record *p with two 16-B stores, no atomics; a block with nothing to
+// publish stores nothing.  merge: the block published before in this kernel (a hub block's next hub): folded into
+// what it stored.  (tot: one-wave blocks only.)  All threads must call it.
+template <int NTH>
+__device__ __forceinline__ void publish_part(Part *p, uint64_t tmn, uint64_t wnd, uint64_t wndw, uint64_t tot = 0,
+                                             bool merge = false) {
+  tmn = wave_min64(tmn);
+  wnd = wave_min64(wnd);
+  wndw = wave_min64(wndw);
+  if constexpr (NTH > 64) {
+    __shared__ uint64_t s0[NTH / 64], s1[NTH / 64], s2[NTH / 64];
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    __syncthreads();
+    if (lane == 0) {
+      s0[wid] = tmn;
+      s1[wid] = wnd;
+      s2[wid] = wndw;
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    for (int w = 1; w < NTH / 64; w++) {
+      tmn = s0[w] < tmn ? s0[w] : tmn;
+      wnd = s1[w] < wnd ? s1[w] : wnd;
+      wndw = s2[w] < wndw ? s2[w] : wndw;
+    }
+  } else {
+    tot = wave_sum64(tot);
+    if ((threadIdx.x & 63) != 0) return;
+  }
+  if ((tmn & wnd & wndw) == ~0ull && tot == 0) return;
+  ulonglong2 *q = reinterpret_cast<ulonglong2 *>(p);
+  if (merge) {
+    const ulonglong2 a = q[0], b = q[1];
+    tmn = a.x < tmn ? a.x : tmn;
+    wnd = a.y < wnd ? a.y : wnd;
+    wndw = b.x < wndw ? b.x : wndw;
+    tot += b.y;
+  }
+  q[0] = make_ulonglong2(tmn, wnd);
+  q[1] = make_ulonglong2(wndw, tot);
+}
 
 // A pending event in registers.
 struct Ev {
@@ -1252,12 +1314,13 @@ constexpr int PFC = 4;  // children per slot k2_pa loads ahead
 // of column tile tj: each row's count of smaller keys is added to its rank (keys are distinct: uids).
 // Wide rows: each column tile's keys are loaded by NRT blocks, not WCAP / HB.
 // (wr: the rank accumulators of the window's parity, wrank_of)
+template <bool DF = false>
 __device__ __forceinline__ void rank_tile(const P2PDev &M, const Ctl &C, uint32_t t, uint32_t *wr) {
   const uint32_t ti = t / NJT, tj = t % NJT;
   __shared__ uint64_t tk[RJ];
   // the window size first: a config-4 window fills ~1/4 of the WCAP x WCAP tiles, and the tiles past
   // it load nothing (these blocks are off the launch's critical path, the holders are on it)
-  const uint32_t W = C.W;
+  const uint32_t W = DF ? (uint32_t)C.wnf : C.W;  // (DF: the deferred pipeline's allocation word)
   const uint32_t r0 = ti * HB * RTR;
   if (r0 >= W || tj * RJ >= W) return;  // uniform over the block
 #pragma unroll
@@ -1287,6 +1350,12 @@ __device__ __forceinline__ void rank_tile(const P2PDev &M, const Ctl &C, uint32_
 }
 
 #include "nsgpu_p2p_win.h"
+
+// Empties the deferred pipeline's partial records (create, reset).
+__global__ void k_part_clear(Ctl *C) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < (uint32_t)NPARTS) *part_rec(C, i) = Part{~0ull, ~0ull, ~0ull, 0};
+}
 
 // ================================ partitioned run (multi-GPU) ================================
 // DistributedSimulatorImpl (src/mpi/model/distributed-simulator-impl.cc:146-326) gives every rank
@@ -2608,7 +2677,7 @@ static int create_engine(const nsgpu_p2p_scenario *sc, const uint32_t *owner, in
   // window records: a whole sorted run (single engine), a whole window before its cut (partitioned)
   M.fcap = (size_t)NMAX * M.maxc;  // children parked in one window: at most every record's
   M.runcap = M.pool_cap + M.fcap;
-  if (M.runcap >= 0xffffffffull) {
+  if (M.runcap >= 0xffffffffull) {  // (so a window's slots and fcap each fit a half of the allocation word, Ctl::wnf)
     nsgpu_p2p_destroy(h);
     return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: pool_cap too large for 32-bit slots");
   }
@@ -2695,7 +2764,14 @@ static int create_engine(const nsgpu_p2p_scenario *sc, const uint32_t *owner, in
     h->x1h0.red.tmin = h->x1h0.red.wend = h->x1h0.red.stopts = h->x1h0.red.wendw = ~0ull;
     h->x1h0.rkey = ~0ull;
   }
-  TRY(dalloc(h, &M.C, 1));
+  {  // the run control, and behind it the deferred pipeline's partial records (Part), empty
+    uint8_t *cb;
+    TRY(dalloc(h, &cb, CTL_PARTS_OFF + (size_t)NPARTS * PART_LINE));
+    M.C = reinterpret_cast<Ctl *>(cb);
+    hipLaunchKernelGGL(k_part_clear, dim3((NPARTS + 255) / 256), dim3(256), 0, nullptr, M.C);
+    NSGPU_HIP(hipGetLastError());
+    NSGPU_HIP(hipDeviceSynchronize());
+  }
   if (owner) M.x0_send = reinterpret_cast<uint64_t *>(&M.C->W);  // X0 sends (W, nxtP, overflow, prep)
   if (owner && nranks == 1) {  // one rank: its exchanges are its own payloads in place (no copies in the window)
     M.x0_recv = M.x0_send;
@@ -2856,6 +2932,8 @@ extern "C" int nsgpu_p2p_reset(nsgpu_p2p *h, void *stream) {
     NSGPU_HIP(hipMemsetAsync(M.log_ctx, 0, M.log_cap * 4, s));
   }
   NSGPU_HIP(hipMemcpyAsync(M.C, &h->C0, sizeof(Ctl), hipMemcpyHostToDevice, s));
+  hipLaunchKernelGGL(k_part_clear, dim3((NPARTS + 255) / 256), dim3(256), 0, s, M.C);  // (a run that failed may leave some)
+  NSGPU_HIP(hipGetLastError());
   h->uid_hint = h->C0.uid;
   return NSGPU_OK;
 }
@@ -2879,7 +2957,8 @@ bool launch_kernel(nsgpu_p2p *h, int k, hipStream_t s, bool df, hipEvent_t ev0 =
       else NSGPU_KLAUNCH((k2_pa<false, false>), dim3(pa_grid_rt<false>(h->M)), dim3(TB), s, ev0, ev1, h->M);
       return true;
     case 1:
-      if (wide) NSGPU_KLAUNCH(k2_handle<true>, dim3(K2_GRID), dim3(HB), s, ev0, ev1, h->M);
+      if (df) NSGPU_KLAUNCH((k2_handle<true, false, true>), dim3(K2_GRID), dim3(HB), s, ev0, ev1, h->M);
+      else if (wide) NSGPU_KLAUNCH(k2_handle<true>, dim3(K2_GRID), dim3(HB), s, ev0, ev1, h->M);
       else NSGPU_KLAUNCH(k2_handle<false>, dim3(K2_GRID), dim3(HB), s, ev0, ev1, h->M);
       return true;
     case 2:
@@ -2905,7 +2984,9 @@ bool launch_kernel(nsgpu_p2p *h, int k, hipStream_t s, bool df, hipEvent_t ev0 =
 // reported by the kernel that made it instead of faulting a later one.
 // In graph mode (NSGPU_P2P_DEBUG=2) k_dbg runs after every kernel of the replay (`at`: window << 8 | kernel)
 // and a broken invariant also ends the run (done = 2, error 1024) so that the next kernels do nothing.
-__global__ __launch_bounds__(256) void k_dbg(const P2PDev M, unsigned long long *out, unsigned long long at = 0) {
+// k: the pipeline kernel that ran last (KERNEL_NAMES).
+__global__ __launch_bounds__(256) void k_dbg(const P2PDev M, unsigned long long *out, unsigned long long at = 0,
+                                             int k = -1) {
   Ctl &C = *M.C;
   const uint64_t i0 = (uint64_t)blockIdx.x * 256 + threadIdx.x, st = (uint64_t)gridDim.x * 256;
   if (at && out[0]) return;  // (graph mode: the first violation is kept)
@@ -2920,13 +3001,19 @@ __global__ __launch_bounds__(256) void k_dbg(const P2PDev M, unsigned long long 
       }
     }
   };
-  const uint64_t Pe = C.P_end, nfree = C.nfree, nF = C.nF, W = C.W;
+  // (the deferred pipeline counts the forming window in wnf, the other one in W / nF: the idle pair is 0)
+  const uint64_t Pe = C.P_end, nfree = C.nfree, nF = C.nF + (C.wnf >> 32), W = C.W + (uint32_t)C.wnf;
   if (i0 == 0) {
     if (Pe > M.pool_cap) bad(1, Pe, M.pool_cap);
     if (nfree + C.npush > M.pool_cap) bad(2, nfree, C.npush);
     if (C.live > Pe + nF) bad(3, C.live, Pe);
     if (nF > M.fcap) bad(4, nF, M.fcap);
     if (W > M.runcap) bad(5, W, M.runcap);
+  }
+  // the deferred pipeline's partial records are empty once k2_rank has run (the other pipeline stores none)
+  if (k == 2 && i0 < (uint64_t)NPARTS) {
+    const Part q = *part_rec(&C, (uint32_t)i0);
+    if ((q.tmin & q.wend & q.wendw) != ~0ull || q.tot) bad(50, i0, q.tmin);
   }
   const uint64_t P = Pe < M.pool_cap ? Pe : M.pool_cap;
   for (uint64_t p = i0; p < P; p += st)
@@ -2960,7 +3047,7 @@ int launch_windows_dbg(nsgpu_p2p *h, hipStream_t s, bool df) {
   if (!h->eager) {  // graph capture: checks as graph nodes
     for (int w = 0; w < NWIN; w++)
       for (int k = 0; k < NKERN; k++)
-        if (launch_kernel(h, k, s, df)) hipLaunchKernelGGL(k_dbg, dim3(256), dim3(256), 0, s, h->M, dout, (unsigned long long)(w << 8 | k | 0x80000000u));
+        if (launch_kernel(h, k, s, df)) hipLaunchKernelGGL(k_dbg, dim3(256), dim3(256), 0, s, h->M, dout, (unsigned long long)(w << 8 | k | 0x80000000u), k);
     return NSGPU_OK;
   }
   static int lines = 0;
@@ -2984,7 +3071,7 @@ int launch_windows_dbg(nsgpu_p2p *h, hipStream_t s, bool df) {
         return set_error(NSGPU_EHIP, "nsgpu_p2p debug: %s faulted in window %llu (df %d, mode %u): %s", KERNEL_NAMES[k],
                          (unsigned long long)c.windows, (int)df, c.mode, hipGetErrorString(e));
       NSGPU_HIP(hipMemsetAsync(dout, 0, 4 * sizeof(unsigned long long), s));
-      hipLaunchKernelGGL(k_dbg, dim3(256), dim3(256), 0, s, h->M, dout);
+      hipLaunchKernelGGL(k_dbg, dim3(256), dim3(256), 0, s, h->M, dout, 0ull, k);
       unsigned long long o[4] = {};
       NSGPU_HIP(hipMemcpyAsync(o, dout, sizeof(o), hipMemcpyDeviceToHost, s));
       NSGPU_HIP(hipStreamSynchronize(s));

@@ -307,7 +307,9 @@ __device__ __forceinline__ NtClaim k2_write(const P2PDev &M, Ctl &C, const WinBo
 // each thread's first index out, ONE atomic per counter per block (a device-scope atomic on a shared
 // word costs ~10 ns and they serialise: per-wave allocation cost k2_pa ~3 us a window).  Every thread
 // of the block calls it.
-template <int NT>
+// DF: the deferred pipeline allocates both from one packed word (C.wnf: slots | fresh entries << 32) — one
+// returned atomic in the slot blocks' chain, not two.
+template <int NT, bool DF = false>
 __device__ __forceinline__ void block_alloc2(Ctl &C, uint32_t nw, uint32_t nf, uint32_t &w0, uint64_t &f0) {
   __shared__ uint64_t s_w[NT / 64];
   __shared__ uint64_t s_base[2];
@@ -323,9 +325,15 @@ __device__ __forceinline__ void block_alloc2(Ctl &C, uint32_t nw, uint32_t nf, u
       s_w[w] = tot;
       tot += x;
     }
-    const uint32_t tw = (uint32_t)tot, tf = (uint32_t)(tot >> 32);
-    s_base[0] = tw ? atomicAdd(&C.W, tw) : 0u;
-    s_base[1] = tf ? (uint64_t)atomicAdd((unsigned long long *)&C.nF, (unsigned long long)tf) : 0ull;
+    if constexpr (DF) {
+      const uint64_t o = tot ? (uint64_t)atomicAdd((unsigned long long *)&C.wnf, (unsigned long long)tot) : 0ull;
+      s_base[0] = (uint32_t)o;
+      s_base[1] = o >> 32;
+    } else {
+      const uint32_t tw = (uint32_t)tot, tf = (uint32_t)(tot >> 32);
+      s_base[0] = tw ? atomicAdd(&C.W, tw) : 0u;
+      s_base[1] = tf ? (uint64_t)atomicAdd((unsigned long long *)&C.nF, (unsigned long long)tf) : 0ull;
+    }
   }
   __syncthreads();
   const uint64_t ex = s_w[wid] + inc - v;
@@ -455,6 +463,11 @@ template <bool WIDE>
 inline int pa_grid_rt(const P2PDev &M) {
   return pa_grid<WIDE>() + (M.pool_cap > (1ull << 20) ? GRID_POOL_BIG - GRID_POOL : 0);
 }
+// The deferred pipeline's partial records (Part): one per block of k2_pa's largest grid, then one per holder / hub
+// block of k2_handle
+constexpr int PA_PARTS = pa_grid<true>() + GRID_POOL_BIG - GRID_POOL, HD_PARTS = NLR, NPARTS = PA_PARTS + HD_PARTS;
+__device__ __forceinline__ Part *pa_part(Ctl &C, uint32_t b) { return part_rec(&C, b); }
+__device__ __forceinline__ Part *hd_part(Ctl &C, uint32_t b) { return part_rec(&C, (uint32_t)PA_PARTS + b); }
 // DF: the deferred pipeline's variant (single wide engine): when the last window is staged (C.pdf) its records
 // are written in rank order to the stage for df_sdef and its children get provisional uids (no dispatch log
 // here); the pool's provisional uids of the window before it are resolved as the pool is read.
@@ -725,7 +738,7 @@ __global__ __launch_bounds__(TB) void k2_pa(const P2PDev M) {
       BLK_MARK(36, c_win);  // digest/log, classify (slot data arrived)
       uint32_t w0;
       uint64_t f0;
-      block_alloc2<TB>(C, cw, cf, w0, f0);
+      block_alloc2<TB, DF>(C, cw, cf, w0, f0);
       BLK_MARK(38, c_win);  // block allocation (atomics)
 #pragma unroll
       for (int q = 0; q < PFC; q++) {
@@ -840,7 +853,7 @@ __global__ __launch_bounds__(TB) void k2_pa(const P2PDev M) {
       }
       uint32_t w0 = 0;
       uint64_t f0 = 0;
-      if (__syncthreads_or(cw != 0)) block_alloc2<TB>(C, cw, 0u, w0, f0);  // (most chunks of a large pool: none)
+      if (__syncthreads_or(cw != 0)) block_alloc2<TB, DF>(C, cw, 0u, w0, f0);  // (most chunks of a large pool: none)
 #ifdef NSGPU_PHASE_PROF
       if (c_win == g_blk_win) {  // (diagnostic: pool entries taken, pool chunks swept)
         if (cw) atomicAdd((unsigned long long *)&g_phase[49], (unsigned long long)cw);
@@ -890,7 +903,8 @@ __global__ __launch_bounds__(TB) void k2_pa(const P2PDev M) {
       R.stopuid = C.drn_stopuid;
     }
   }
-  publish_min<TB, WIDE>(R, tmn, wnd, wndw);
+  if constexpr (DF) publish_part<TB>(pa_part(C, blockIdx.x), tmn, wnd, wndw);  // (df_fold folds the blocks' records)
+  else publish_min<TB, WIDE>(R, tmn, wnd, wndw);
   digest = wave_sum64(digest);
   {  // one digest atomic per block
     __shared__ uint64_t s_dg[TB / 64];
@@ -1120,7 +1134,7 @@ __device__ __forceinline__ void device_act_cached(const P2PDev &M, Emit &E, cons
   }
 }
 
-template <bool WIDE>
+template <bool WIDE, bool DF = false>
 __device__ __forceinline__ void handle_node2(const P2PDev &M, Ctl &C, uint32_t i0, uint32_t W, uint32_t base, Red &R,
                                              uint32_t *lds, const HCtl &hc, SlotPre sp, uint32_t *lcnt_sh) {
   uint32_t *chs = lds;
@@ -1292,8 +1306,12 @@ __device__ __forceinline__ void handle_node2(const P2PDev &M, Ctl &C, uint32_t i
       wndw = E.wndw;
     }
   }
-  publish_min<HB, WIDE>(R, tmn, wnd, wndw);
-  x1_totals(M, xa);
+  if constexpr (DF) {  // (the deferred pipeline: the block's record, minima and child totals; df_fold folds them)
+    publish_part<HB>(hd_part(C, blockIdx.x), tmn, wnd, wndw, (uint64_t)xa.tc | ((uint64_t)xa.ti << 32));
+  } else {
+    publish_min<HB, WIDE>(R, tmn, wnd, wndw);
+    x1_totals(M, xa);
+  }
   if (hs.stop) C.stop_seen = 1;
   // the counters summed over the wave first: one atomic per thread on one word serialised over the window (4,096
   // cancelled OnOff events at a dumbbell's 5 s: 37-54 us a window)
@@ -1670,9 +1688,9 @@ __device__ __forceinline__ void hub_help(const P2PDev &M, Ctl &C, uint32_t i0, u
 // other node parts serially in key order; (3) the device steps and trailing children serially in key
 // order, the device state in registers.  Node parts never read device state and device steps never
 // read node state (node_part), so this is the sequential order's result.
-template <bool WIDE>
+template <bool WIDE, bool DF = false>
 __device__ __forceinline__ void hub_node(const P2PDev &M, Ctl &C, uint32_t c, uint32_t W, uint32_t base, bool sorted, Red &R,
-                         uint32_t hb, uint32_t *lds, const HCtl &hc, uint32_t *lcnt_sh, bool helped) {
+                         uint32_t hb, uint32_t *lds, const HCtl &hc, uint32_t *lcnt_sh, bool helped, bool first = true) {
   const int lane = threadIdx.x;
   const uint64_t below = (1ull << lane) - 1ull;
   uint64_t *gk = M.hub_key + (uint64_t)hb * WCAP;
@@ -2120,8 +2138,12 @@ __device__ __forceinline__ void hub_node(const P2PDev &M, Ctl &C, uint32_t c, ui
     if (lane == 0) D.flush(M);
   }
   HUB_MARK(26);  // (device steps: the parallel scan or the serial pass)
-  publish_min<HB, WIDE>(R, E.tmn, E.wnd, E.wndw);
-  x1_totals(M, xa);
+  if constexpr (DF) {  // (first: this block's first hub of the window — a later one folds into the block's record)
+    publish_part<HB>(hd_part(C, blockIdx.x), E.tmn, E.wnd, E.wndw, (uint64_t)xa.tc | ((uint64_t)xa.ti << 32), !first);
+  } else {
+    publish_min<HB, WIDE>(R, E.tmn, E.wnd, E.wndw);
+    x1_totals(M, xa);
+  }
   const uint64_t nr = wave_sum64(hs.no_route), td = wave_sum64(hs.ttl_drops), cn = wave_sum64(hs.cancelled),
                  ur = wave_sum64(hs.unreach), ic = wave_sum64(hs.icmp);
   const bool stop = __ballot(hs.stop) != 0;
@@ -2242,8 +2264,11 @@ __global__ __launch_bounds__(HB) void k_xlcompact(const P2PDev M) {
 
 // XL: the partitioned wide engine's variant (k_gtile's accumulators zeroed; every region count written, for
 // k_xlcompact): a separate instantiation, so that the single engine's kernel has none of that code.
-template <bool WIDE, bool XL = false>
+// DF: the deferred pipeline's variant (single wide engine): the holder and hub blocks publish per-block partial
+// records (Part) instead of atomics on the run control.
+template <bool WIDE, bool XL = false, bool DF = false>
 __global__ __launch_bounds__(HB) void k2_handle(const P2PDev M) {
+  static_assert(!DF || (WIDE && !XL), "deferred windows are the single wide engine's");
   __shared__ uint64_t lds64[(WIDE ? K2_LDS_WORDS_W : K2_LDS_WORDS) / 2];
   uint32_t *lds = reinterpret_cast<uint32_t *>(lds64);
   PH_BEGIN();
@@ -2253,8 +2278,10 @@ __global__ __launch_bounds__(HB) void k2_handle(const P2PDev M) {
   const uint64_t c_win = C.windows;
 #endif
   // the run control and (holder blocks) the slot's record, all loaded at once
-  const uint32_t c_done = C.done, c_mode = C.mode, W = C.W, c_wbase = C.wbase, c_fr = C.force_run, rt = C.rt,
-                 c_nhub = C.nhub;
+  uint64_t c_wnf = 0;  // (DF: the window's slots and fresh entries come in one word)
+  if constexpr (DF) c_wnf = C.wnf;
+  const uint32_t c_done = C.done, c_mode = C.mode, W = DF ? (uint32_t)c_wnf : C.W, c_wbase = C.wbase,
+                 c_fr = C.force_run, rt = C.rt, c_nhub = C.nhub;
   const uint32_t c_drun = M.dist ? C.drun : 0u;  // a partitioned run's chunk: key order, hubs in slot order
   __shared__ int64_t s_look[2 * K_NKINDS];
   const HCtl hc{C.tmin, C.inline_lim, C.split_lo, C.split_hi, C.lim_rel, s_look};
@@ -2263,7 +2290,7 @@ __global__ __launch_bounds__(HB) void k2_handle(const P2PDev M) {
   const uint64_t c_wn = C.windows;
   __shared__ uint32_t s_lcnt;  // local records this block made (its region's count, wide windows)
   if (threadIdx.x == 0) s_lcnt = 0;
-  const uint64_t c_nfree = C.nfree, c_nF = C.nF, c_Pe = C.P_end;
+  const uint64_t c_nfree = C.nfree, c_nF = DF ? c_wnf >> 32 : C.nF, c_Pe = C.P_end;
   const uint32_t bx = blockIdx.x;
   SlotPre sp{1u, 0, 0, 0, 0};
   if (bx < (uint32_t)NHB) {
@@ -2323,14 +2350,14 @@ __global__ __launch_bounds__(HB) void k2_handle(const P2PDev M) {
   if (bx < (uint32_t)NHB) {
     if (handle) {
       if (helped) hub_help(M, C, bx * HB + threadIdx.x, W, base, hc, sp);
-      handle_node2<WIDE>(M, C, bx * HB + threadIdx.x, W, base, R, lds, hc, sp, &s_lcnt);
+      handle_node2<WIDE, DF>(M, C, bx * HB + threadIdx.x, W, base, R, lds, hc, sp, &s_lcnt);
     }
   } else if (bx < (uint32_t)(NHB + NHUB)) {
     if (handle) {
       const uint32_t hb = bx - NHB;
       const uint32_t nh = c_nhub < (uint32_t)MAXHUB ? c_nhub : (uint32_t)MAXHUB;
       for (uint32_t h = hb; h < nh; h += NHUB)
-        hub_node<WIDE>(M, C, M.hub_list[h], W, base, run || c_drun != 0, R, hb, lds, hc, &s_lcnt, helped);
+        hub_node<WIDE, DF>(M, C, M.hub_list[h], W, base, run || c_drun != 0, R, hb, lds, hc, &s_lcnt, helped, h == hb);
     }
   } else if (bx < (uint32_t)K2_GRID_W) {
     if constexpr (XL) {  // k_gtile's accumulators for this window (k_dfin2 read the last window's: local
@@ -2339,7 +2366,7 @@ __global__ __launch_bounds__(HB) void k2_handle(const P2PDev M) {
     }
     maintain(M, C, bx - (NHB + NHUB), run, handle, W, c_nfree, c_nF, c_Pe);
   } else {
-    if (!run && handle && !M.dist) rank_tile(M, C, bx - K2_GRID_W, wrank_of(M, c_wn));  // (keys known before the handlers run)
+    if (!run && handle && !M.dist) rank_tile<DF>(M, C, bx - K2_GRID_W, wrank_of(M, c_wn));  // (keys known before the handlers run)
   }
   if (WIDE && (hc.lim || XL) && bx < (uint32_t)NLR) {  // this block's local region count (k2_rank / k2_scan /
     __syncthreads();                                       //  k_xlcompact read it; written even when 0: the
@@ -2411,7 +2438,51 @@ constexpr int RKC = 64;  // columns per tile
 #define TILE_MARK(i, win) (void)0
 #endif
 template <int NT>
-__device__ void df_book(const P2PDev &M, Ctl &C, bool ranked, uint32_t W, uint32_t Lt, uint64_t wn);
+__device__ void df_book(const P2PDev &M, Ctl &C, bool ranked, uint32_t W, uint32_t Lt, uint64_t wn, uint64_t tot);
+// The partial records k2_pa's and k2_handle's blocks stored this window (Part), folded by k2_rank<true>'s block 0:
+// thread t < NPARTS holds record t (pr0 / pr1: loaded with the kernel's run control) and thread 0 the accumulating
+// reduction's words (r_tmin, r_wend, r_wendw of red[rt]); the minima are folded into red[rt], the records are
+// emptied again, and the window's child totals (children | inline children << 32) are returned to thread 0.
+// Every thread of the block calls it.
+template <int NT>
+__device__ __forceinline__ uint64_t df_fold(Ctl &C, uint32_t rt, ulonglong2 pr0, ulonglong2 pr1, uint64_t r_tmin,
+                                            uint64_t r_wend, uint64_t r_wendw) {
+  constexpr int NW = (NPARTS + 63) / 64;
+  static_assert(NPARTS <= NT, "one thread per partial record");
+  __shared__ uint64_t s_f[NW][4];
+  const uint32_t tid = threadIdx.x, wid = tid >> 6;
+  if (wid < (uint32_t)NW) {  // (wave-uniform)
+    const uint64_t a = wave_min64(pr0.x), b = wave_min64(pr0.y), c = wave_min64(pr1.x), d = wave_sum64(pr1.y);
+    if ((tid & 63) == 0) {
+      s_f[wid][0] = a;
+      s_f[wid][1] = b;
+      s_f[wid][2] = c;
+      s_f[wid][3] = d;
+    }
+    if (tid < (uint32_t)NPARTS) {
+      ulonglong2 *q = reinterpret_cast<ulonglong2 *>(part_rec(&C, tid));
+      q[0] = make_ulonglong2(~0ull, ~0ull);
+      q[1] = make_ulonglong2(~0ull, 0);
+    }
+  }
+  __syncthreads();
+  uint64_t tot = 0;
+  if (tid == 0) {
+    uint64_t a = r_tmin, b = r_wend, c = r_wendw;
+#pragma unroll
+    for (int w = 0; w < NW; w++) {
+      a = s_f[w][0] < a ? s_f[w][0] : a;
+      b = s_f[w][1] < b ? s_f[w][1] : b;
+      c = s_f[w][2] < c ? s_f[w][2] : c;
+      tot += s_f[w][3];
+    }
+    Red &R = C.red[rt];
+    if (a != r_tmin) R.tmin = a;
+    if (b != r_wend) R.wend = b;
+    if (c != r_wendw) R.wendw = c;
+  }
+  return tot;
+}
 // DF: the deferred pipeline's variant: it reads k2_handle's snapshot (rk_*), always runs for a formed window,
 // copies the window's keys / contexts for the next k2_pa (pwkey / pwctx: k2_scan's job in the other
 // pipeline), and its block 0 does the window's bookkeeping (df_book); the dispatch accounting (log, digest,
@@ -2449,6 +2520,24 @@ __global__ __launch_bounds__(DF ? RKT_DF : RKT) void k2_rank(const P2PDev M) {
     c_done = C.done, c_mode = C.mode, W = C.W, c_fr = C.force_run, lim = C.lim_rel, wn = C.windows;
   }
   const uint32_t lc = threadIdx.x < (uint32_t)NLR ? M.lcnt[threadIdx.x] : 0u;  // (its trip overlaps the control's)
+  uint64_t f_tot = 0;  // (DF, block 0's thread 0: the window's child totals, from the blocks' partial records)
+  if constexpr (DF) {
+    if (blockIdx.x == 0) {  // the partial records, before any return: whatever was published is folded and cleared
+      ulonglong2 pr0 = make_ulonglong2(~0ull, ~0ull), pr1 = make_ulonglong2(~0ull, 0);
+      if (threadIdx.x < (uint32_t)NPARTS) {
+        const ulonglong2 *q = reinterpret_cast<const ulonglong2 *>(part_rec(&C, threadIdx.x));
+        pr0 = q[0], pr1 = q[1];
+      }
+      uint32_t rt = 0;
+      uint64_t ra[2] = {0, 0}, rb[2] = {0, 0}, rc[2] = {0, 0};
+      if (threadIdx.x == 0) {  // (both reductions' words with rt: picked once it is back)
+        rt = C.rt;
+#pragma unroll
+        for (int k = 0; k < 2; k++) ra[k] = C.red[k].tmin, rb[k] = C.red[k].wend, rc[k] = C.red[k].wendw;
+      }
+      f_tot = df_fold<NT>(C, rt, pr0, pr1, rt ? ra[1] : ra[0], rt ? rb[1] : rb[0], rt ? rc[1] : rc[0]);
+    }
+  }
   if (DF) {
     if (!(go & 2u)) return;  // (no window was formed: the run is over or paused)
     if (go & 4u) {  // (a sorted run's chunk: the host drives runs with the other pipeline — never here)
@@ -2473,7 +2562,7 @@ __global__ __launch_bounds__(DF ? RKT_DF : RKT) void k2_rank(const P2PDev M) {
   uint32_t b0 = blockIdx.x, nb = gridDim.x;  // (DF: block 0 keeps the books, 1 .. NSDEF account, the others rank)
   if (DF) {
     if (blockIdx.x == 0) {
-      df_book<NT>(M, C, ranked, W, Lt, wn);
+      df_book<NT>(M, C, ranked, W, Lt, wn, f_tot);
       BLK_REC(2, c_win);
       return;
     }
@@ -2615,21 +2704,23 @@ __global__ __launch_bounds__(DF ? RKT_DF : RKT) void k2_rank(const P2PDev M) {
 }
 
 // The deferred pipeline's window bookkeeping (k2_rank<true>'s block 0; NT threads): k2_scan's run
-// bookkeeping without its scan — the child totals come from k2_handle (acc_tc / acc_tinl), the dispatch
-// bases of the window go to winfo for df_sdef, and the next k2_pa stages the window (pdf = 1).  The
-// free-stack move and the hub resets are the block's; the rest is thread 0's.
+// bookkeeping without its scan — the child totals come from k2_handle's partial records (tot: children | inline
+// children << 32, folded by df_fold, in thread 0), the dispatch bases of the window go to winfo for df_sdef, and
+// the next k2_pa stages the window (pdf = 1).  The free-stack move and the hub resets are the block's; the rest
+// is thread 0's.
 template <int NT>
-__device__ void df_book(const P2PDev &M, Ctl &C, bool ranked, uint32_t W, uint32_t Lt, uint64_t wn) {
+__device__ void df_book(const P2PDev &M, Ctl &C, bool ranked, uint32_t W, uint32_t Lt, uint64_t wn, uint64_t tot) {
   const int tid = threadIdx.x;
   // every run-control field the bookkeeping reads, loaded at once (one memory trip: a load issued after a
   // branch on another loaded value would wait for that value first)
-  const uint64_t nF = C.nF, nfree = C.nfree, npush = C.npush;
+  const uint64_t nF = C.wnf >> 32, nfree = C.nfree, npush = C.npush;  // (the pipeline's allocation word)
   const uint32_t c_nhub = C.nhub;
-  uint64_t tc = 0, tinl = 0, live = 0, P_end = 0, c_bound = 0, c_nbound = 0, K = 0, tmin = 0, ilim = 0, windows = 0,
+  const uint64_t tc = tot & 0xffffffffull, tinl = tot >> 32;
+  uint64_t live = 0, P_end = 0, c_bound = 0, c_nbound = 0, K = 0, tmin = 0, ilim = 0, windows = 0,
            span_t = 0, hts = 0, max_window = 0, max_windows = 0, refits = 0;
   uint32_t uid = 0, rt = 0, stop_seen = 0, hcap = 0;
   if (tid == 0) {
-    tc = C.acc_tc, tinl = C.acc_tinl, live = C.live, P_end = C.P_end, c_bound = C.bound, c_nbound = C.nbound;
+    live = C.live, P_end = C.P_end, c_bound = C.bound, c_nbound = C.nbound;
     K = C.K, tmin = C.tmin, ilim = C.inline_lim, windows = C.windows, span_t = C.span_t, hts = C.hts;
     max_window = C.max_window, max_windows = C.max_windows, refits = C.refits;
     uid = C.uid, rt = C.rt, stop_seen = C.stop_seen, hcap = C.hcap;
@@ -2643,15 +2734,13 @@ __device__ void df_book(const P2PDev &M, Ctl &C, bool ranked, uint32_t W, uint32
     for (uint32_t h = tid; h < nh; h += NT) M.node_tab[(uint64_t)M.hub_list[h] * NTAB] = 0;
   }
   if (tid != 0) return;
-  C.acc_tc = 0;
-  C.acc_tinl = 0;
   C.nfree = nfree - consumed + npush;
   const uint64_t P_end2 = P_end + (nF > nfree ? nF - nfree : 0);
   const uint64_t live2 = live - npush + nF;
   C.P_end = P_end2;
   C.live = live2;
   C.npush = 0;
-  C.nF = 0;
+  C.wnf = 0;  // (W and nF are 0 throughout this pipeline: the other one finds them true wherever it takes over)
   C.nhub = 0;
   C.force_run = 0;
   if (!ranked) {  // the window overflowed: a sorted run (host radix sort), nothing dispatched (k2_scan's branch)
