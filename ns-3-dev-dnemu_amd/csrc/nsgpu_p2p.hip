@@ -20,6 +20,7 @@
 #include <stddef.h>
 #include "nsgpu_device.h"
 #include "nsgpu_internal.h"
+#include "nsgpu_p2p_span.h"
 
 namespace nsgpu {
 
@@ -394,6 +395,13 @@ __device__ __forceinline__ uint64_t wave_max64(uint64_t v) {
   const uint64_t a = rl64(v, 0), b = rl64(v, 16), c = rl64(v, 32), d = rl64(v, 48);
   const uint64_t x = a > b ? a : b, y = c > d ? c : d;
   return x > y ? x : y;
+}
+__device__ __forceinline__ uint32_t wave_max32(uint32_t v) {
+  v = max(v, dpp32<DPP_X1>(v));
+  v = max(v, dpp32<DPP_X2>(v));
+  v = max(v, dpp32<DPP_HMIRROR>(v));
+  v = max(v, dpp32<DPP_MIRROR>(v));
+  return max(max(rl32(v, 0), rl32(v, 16)), max(rl32(v, 32), rl32(v, 48)));
 }
 __device__ __forceinline__ uint32_t wave_sum32(uint32_t v) {
   v += dpp32<DPP_X1>(v);
@@ -2087,7 +2095,8 @@ __global__ __launch_bounds__(HB) void k_dfin2(const P2PDev M) {
   rg.wend = wave_min64(hwend);
   if (WIDE) rg.wendw = wave_min64(hwendw);
   // wide windows: the adaptive span keeps every rank's window inside its capacity (WCAP gen-0, NMAX records;
-  // k2_scan's rule, from the largest rank's counts so that every rank forms the same bound)
+  // marks at 7/8 and 3/4 of both — the single engine's are span_next's, nsgpu_p2p_span.h: its capacities differ,
+  // XLCAP and X1 are sized otherwise — from the largest rank's counts so that every rank forms the same bound)
   const uint64_t mxW = WIDE ? wave_max64(hW) : 0, mxN = WIDE ? wave_max64((uint64_t)hW + l_q) : 0;
   {  // the pending Stop: the smallest stopts, the first rank holding it
     rg.stopts = wave_min64(hsts);

@@ -61,6 +61,14 @@ constexpr int NMAX_PAD = NMAX + NMAX / 64;
 constexpr int LMAX = NMAX - WCAP;        // local records of one window
 static_assert(LMAX == XLCAP, "a partitioned rank's X1Loc list holds its window's local records");
 constexpr int SLOTG = WCAP + LMAX;       // k2_pa's slot-role threads (single engine): gen-0 slots, then local
+constexpr SpanCaps SPAN_CAPS{NMAX, WCAP, LMAX, LR, LRH};  // the span controller's capacities (nsgpu_p2p_span.h)
+static_assert(NHB == 64 && NLR <= 128, "region_fill: the holder regions are wave 0's lanes, the hub regions wave 1's");
+// The fullest holder region and the fullest hub region of a window, from each thread's region count v
+// (M.lcnt[thread], 0 past NLR): {holder, hub} in LDS after the caller's next barrier.  Waves 0 and 1 call it.
+__device__ __forceinline__ void region_fill(uint32_t v, uint32_t *fill) {
+  v = wave_max32(v);
+  if ((threadIdx.x & 63) == 0) fill[threadIdx.x >> 6] = v;
+}
 static_assert(LCAP < (1 << 24) && WTOT < (1 << 24), "wpar packs a record index in 24 bits");
 // Rank accumulators of window `win` (by parity: a deferred window's ranks are read after the next window's
 // ranking has begun).  wrank: 2 x WTOT, lrank: 2 x LMAX.
@@ -2430,7 +2438,13 @@ __device__ __forceinline__ bool lk_before(const LKey &a, const LKey &b) {
 // costs one 16-B LDS load and two compares (64 columns a tile, unrolled: the loads pipeline); the exact
 // chain compare runs after the tile, only for rows whose words tie with a distinct record's (chains of 3+
 // levels with equal ts pairs).
-constexpr int RKC = 64;  // columns per tile
+// The tiles that compare nothing but rel ts (gen-0 rows x local columns, local rows x gen-0 columns) read 4 B a
+// column and take RKCW columns in the deferred pipeline: a window at the full lookahead (config 4: N 5,888, W 3,840,
+// Lt 2,048) is then 15 x 8 + 8 x 32 + 8 x 15 = 496 tiles, one round of the 1,004 sub-tiles, where RKC columns
+// everywhere made it 23 x 32 + 8 x 60 = 1,216 and a second round.
+constexpr int RKC = 64;    // columns per tile: rows with local records (16 B a column)
+constexpr int RKCW = 256;  // columns per tile: the rel-ts-only tiles of k2_rank<true>
+static_assert(RKCW <= RKT && RKCW % 4 == 0, "one thread loads a column; read four at a time");
 // (diagnostic build: the tiles' phase marks only with NSGPU_TILE_MARKS — their atomics distort the per-block times)
 #ifdef NSGPU_TILE_MARKS
 #define TILE_MARK(i, win) BLK_MARK(i, win)
@@ -2438,7 +2452,8 @@ constexpr int RKC = 64;  // columns per tile
 #define TILE_MARK(i, win) (void)0
 #endif
 template <int NT>
-__device__ void df_book(const P2PDev &M, Ctl &C, bool ranked, uint32_t W, uint32_t Lt, uint64_t wn, uint64_t tot);
+__device__ void df_book(const P2PDev &M, Ctl &C, bool ranked, uint32_t W, uint32_t Lt, uint32_t reg, uint32_t hreg,
+                        uint64_t wn, uint64_t tot);
 // The partial records k2_pa's and k2_handle's blocks stored this window (Part), folded by k2_rank<true>'s block 0:
 // thread t < NPARTS holds record t (pr0 / pr1: loaded with the kernel's run control) and thread 0 the accumulating
 // reduction's words (r_tmin, r_wend, r_wendw of red[rt]); the minima are folded into red[rt], the records are
@@ -2497,6 +2512,7 @@ constexpr int RK_GRID_DF = 256;           // one 1024-thread block per CU (~150 
 template <bool DF>
 __global__ __launch_bounds__(DF ? RKT_DF : RKT) void k2_rank(const P2PDev M) {
   constexpr int NT = DF ? RKT_DF : RKT, SUBS = NT / RKT;
+  constexpr int RKW = DF ? RKCW : RKC;  // (the scanning pipeline's k2_rank keeps RKC columns in every tile)
   Ctl &C = *M.C;
   BLK_T0();
 #ifdef NSGPU_PHASE_PROF
@@ -2555,14 +2571,17 @@ __global__ __launch_bounds__(DF ? RKT_DF : RKT) void k2_rank(const P2PDev M) {
   __shared__ ulonglong2 cws[SUBS][RKC];
   // the columns' rel ts alone (the gen-0-row and local-row x gen-0 tiles compare nothing else): 4 B a column, read
   // 4 at a time — the tiles are bound by their per-column LDS reads and 64-bit compares
-  __shared__ __align__(16) uint32_t cwhs[SUBS][RKC];
+  __shared__ __align__(16) uint32_t cwhs[SUBS][RKW];
+  // (DF, block 0: the fullest holder / hub region, for the span controller; local_prefix's barriers order it)
+  __shared__ uint32_t s_fill[2];
+  if (DF && blockIdx.x == 0 && threadIdx.x < 128) region_fill((ranked && lim) ? lc : 0u, s_fill);
   local_prefix<NT>((ranked && lim) ? lc : 0u, pre);
   const uint32_t Lt = pre[NLR], N = W + Lt;
   uint32_t *const wr = wrank_of(M, wn), *const lr = lrank_of(M, wn);
   uint32_t b0 = blockIdx.x, nb = gridDim.x;  // (DF: block 0 keeps the books, 1 .. NSDEF account, the others rank)
   if (DF) {
     if (blockIdx.x == 0) {
-      df_book<NT>(M, C, ranked, W, Lt, wn, f_tot);
+      df_book<NT>(M, C, ranked, W, Lt, s_fill[0], s_fill[1], wn, f_tot);
       BLK_REC(2, c_win);
       return;
     }
@@ -2581,9 +2600,11 @@ __global__ __launch_bounds__(DF ? RKT_DF : RKT) void k2_rank(const P2PDev M) {
   }
 #endif
   TILE_MARK(48, c_win);
-  const uint32_t nr = (N + RKT - 1) / RKT, ncl = (Lt + RKC - 1) / RKC;  // phase A: rows x local columns
-  const uint32_t nl = (Lt + RKT - 1) / RKT, ncg = (W + RKC - 1) / RKC;  // phase B: local rows x gen-0 columns
-  const uint32_t na = nr * ncl, ntile = na + nl * ncg;
+  // phase A: rows x local columns — the row tiles that hold gen-0 records only (the first nrg) at RKW columns a
+  // tile, the others (the tile that straddles W, the local rows) at RKC; phase B: local rows x gen-0 columns, RKW
+  const uint32_t nr = (N + RKT - 1) / RKT, nrg = W / RKT, ncl = (Lt + RKC - 1) / RKC, nclw = (Lt + RKW - 1) / RKW;
+  const uint32_t nl = (Lt + RKT - 1) / RKT, ncg = (W + RKW - 1) / RKW;
+  const uint32_t na0 = nrg * nclw, na = na0 + (nr - nrg) * ncl, ntile = na + nl * ncg;
   // SUBS tiles a block at once: sub-tile `sub` is RKT threads (whole waves) with its own column buffer
   const uint32_t sub = threadIdx.x / RKT, lt = threadIdx.x % RKT;
   ulonglong2 *const cw = cws[sub];
@@ -2598,12 +2619,13 @@ __global__ __launch_bounds__(DF ? RKT_DF : RKT) void k2_rank(const P2PDev M) {
     bool g0rows = false;  // (tA: every row is a gen-0 record)
     uint64_t wx = ~0ull, wx2 = ~0ull, relx = 0;
     if (tA) {  // rows: every record; columns: local records
-      const uint32_t ti = t / ncl;
-      tj = t % ncl;
+      g0rows = t < na0;
+      const uint32_t u = g0rows ? t : t - na0, nc = g0rows ? nclw : ncl, ti = u / nc + (g0rows ? 0u : nrg);
+      const uint32_t cwid = g0rows ? (uint32_t)RKW : (uint32_t)RKC;
+      tj = u % nc;
       ix = ti * RKT + lt;
-      g0rows = ti * RKT + RKT <= W;
-      if (lt < (uint32_t)RKC) {
-        const uint32_t cy = tj * RKC + lt;
+      if (lt < cwid) {
+        const uint32_t cy = tj * cwid + lt;
         ulonglong2 w = make_ulonglong2(~0ull, ~0ull);  // (a padding column: after every row)
         if (cy < Lt) {
           const uint32_t r = dense_rec(W + cy, W, pre);
@@ -2616,8 +2638,8 @@ __global__ __launch_bounds__(DF ? RKT_DF : RKT) void k2_rank(const P2PDev M) {
             M.pwctx[r] = M.wctx[r];
           }
         }
-        cw[lt] = w;
-        cwh[lt] = (uint32_t)(w.x >> 32);  // (padding 0xffffffff: never below a row's rel ts)
+        if (g0rows) cwh[lt] = (uint32_t)(w.x >> 32);  // (padding 0xffffffff: never below a row's rel ts)
+        else cw[lt] = w;
       }
       if (ix < N) {
         rx = dense_rec(ix, W, pre);
@@ -2634,8 +2656,8 @@ __global__ __launch_bounds__(DF ? RKT_DF : RKT) void k2_rank(const P2PDev M) {
       const uint32_t u = t - na, ti = u / ncg;
       tj = u % ncg;
       ix = ti * RKT + lt;
-      if (lt < (uint32_t)RKC) {
-        const uint32_t cy = tj * RKC + lt;
+      if (lt < (uint32_t)RKW) {
+        const uint32_t cy = tj * RKW + lt;
         cwh[lt] = cy < W ? (uint32_t)(M.wkey[cy] >> 32) : 0xffffffffu;  // (padding: counted out below)
       }
       if (ix < Lt) relx = M.wkey[dense_rec(W + ix, W, pre)] >> 32;
@@ -2646,7 +2668,7 @@ __global__ __launch_bounds__(DF ? RKT_DF : RKT) void k2_rank(const P2PDev M) {
     if (tA && g0rows) {  // a local column precedes a gen-0 row iff its rel ts is smaller: one 32-bit compare
       const uint32_t tx = (uint32_t)(wx >> 32);
 #pragma unroll 4
-      for (int y4 = 0; y4 < RKC / 4; y4++) {
+      for (int y4 = 0; y4 < RKW / 4; y4++) {
         const uint4 q = cwh4[y4];
         c += (uint32_t)(q.x < tx) + (uint32_t)(q.y < tx) + (uint32_t)(q.z < tx) + (uint32_t)(q.w < tx);
       }
@@ -2679,12 +2701,12 @@ __global__ __launch_bounds__(DF ? RKT_DF : RKT) void k2_rank(const P2PDev M) {
     } else if (tB) {
       const uint32_t rx32 = (uint32_t)relx;  // (a rel ts: below 2^32)
 #pragma unroll 4
-      for (int y4 = 0; y4 < RKC / 4; y4++) {
+      for (int y4 = 0; y4 < RKW / 4; y4++) {
         const uint4 q = cwh4[y4];
         c += (uint32_t)(q.x <= rx32) + (uint32_t)(q.y <= rx32) + (uint32_t)(q.z <= rx32) + (uint32_t)(q.w <= rx32);
       }
-      const uint32_t nv = W - tj * RKC;  // (the last column tile's padding columns: 0xffffffff <= the row's rel ts
-      if (nv < (uint32_t)RKC && rx32 == 0xffffffffu) c -= (uint32_t)RKC - nv;  //  only at that rel ts)
+      const uint32_t nv = W - tj * RKW;  // (the last column tile's padding columns: 0xffffffff <= the row's rel ts
+      if (nv < (uint32_t)RKW && rx32 == 0xffffffffu) c -= (uint32_t)RKW - nv;  //  only at that rel ts)
       if (ix >= Lt) c = 0;
       slot = ix + LBASE;
     }
@@ -2707,9 +2729,10 @@ __global__ __launch_bounds__(DF ? RKT_DF : RKT) void k2_rank(const P2PDev M) {
 // bookkeeping without its scan — the child totals come from k2_handle's partial records (tot: children | inline
 // children << 32, folded by df_fold, in thread 0), the dispatch bases of the window go to winfo for df_sdef, and
 // the next k2_pa stages the window (pdf = 1).  The free-stack move and the hub resets are the block's; the rest
-// is thread 0's.
+// is thread 0's.  reg / hreg: the fullest holder / hub region of the window (the span controller's inputs).
 template <int NT>
-__device__ void df_book(const P2PDev &M, Ctl &C, bool ranked, uint32_t W, uint32_t Lt, uint64_t wn, uint64_t tot) {
+__device__ void df_book(const P2PDev &M, Ctl &C, bool ranked, uint32_t W, uint32_t Lt, uint32_t reg, uint32_t hreg,
+                        uint64_t wn, uint64_t tot) {
   const int tid = threadIdx.x;
   // every run-control field the bookkeeping reads, loaded at once (one memory trip: a load issued after a
   // branch on another loaded value would wait for that value first)
@@ -2779,10 +2802,8 @@ __device__ void df_book(const P2PDev &M, Ctl &C, bool ranked, uint32_t W, uint32
     atomicOr(M.error, 512u);                           //  unreachable: the pause below hands over first)
     done = true;
   }
-  const uint64_t span = c_bound >> 32;  // wide windows: keep them inside the window capacity
-  if (N > (uint32_t)(7 * NMAX / 8) || W > (uint32_t)(7 * WCAP / 8)) C.span_t = span - span / 4;
-  else if (N < (uint32_t)(3 * NMAX / 4) && W < (uint32_t)(3 * WCAP / 4) && span_t < (1ull << 40))
-    C.span_t = span_t + span_t / 8 + 1;
+  // wide windows: keep them inside the window capacity
+  C.span_t = span_next(SPAN_CAPS, c_bound >> 32, span_t, SpanLoad{N, W, Lt, reg, hreg});
   C.red[rt ^ 1].tmin = C.red[rt ^ 1].wend = C.red[rt ^ 1].stopts = C.red[rt ^ 1].wendw = ~0ull;  // consumed
   C.rt = rt ^ 1;
   C.windows = windows + 1;
@@ -3116,7 +3137,11 @@ __global__ __launch_bounds__(SCAN_THREADS) void k2_scan(const P2PDev M) {
     return;
   }
   // ---- the local records (wide windows): dense positions W .. N-1
-  if constexpr (WIDE) local_prefix<SCAN_THREADS>(c_lim != 0 && !run ? c_lcnt : 0u, pre);
+  __shared__ uint32_t s_fill[2];  // (the fullest holder / hub region, for the span controller)
+  if constexpr (WIDE) {
+    if (tid < 128) region_fill(c_lim != 0 && !run ? c_lcnt : 0u, s_fill);  // (local_prefix's barriers)
+    local_prefix<SCAN_THREADS>(c_lim != 0 && !run ? c_lcnt : 0u, pre);
+  }
   const uint32_t Lt = (WIDE && !run) ? pre[NLR] : 0u;
   const uint32_t N = W + Lt;
   // dense index of slot q, and whether it holds a record of this window
@@ -3321,10 +3346,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void k2_scan(const P2PDev M) {
         C.rtrim = rtrim ? 1u : 0u;
       }
     } else if (WIDE) {  // wide windows: keep them inside the window capacity (WCAP gen-0, NMAX records)
-      const uint64_t span = c_bound >> 32;
-      if (N > (uint32_t)(7 * NMAX / 8) || W > (uint32_t)(7 * WCAP / 8)) C.span_t = span - span / 4;
-      else if (N < (uint32_t)(3 * NMAX / 4) && W < (uint32_t)(3 * WCAP / 4) && bk.span_t < (1ull << 40))
-        C.span_t = bk.span_t + bk.span_t / 8 + 1;
+      C.span_t = span_next(SPAN_CAPS, c_bound >> 32, bk.span_t, SpanLoad{N, W, Lt, s_fill[0], s_fill[1]});
     }
     if (flip) {
       const uint32_t rt = bk.rt;
