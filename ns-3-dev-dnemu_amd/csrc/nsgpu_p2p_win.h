@@ -1,5 +1,5 @@
 // nsgpu_p2p_win.h — the single-GPU window pipeline of the GPU-resident p2p subset (included by
-// nsgpu_p2p.hip inside namespace nsgpu, after the shared model code).
+// nsgpu_p2p.hip inside namespace nsgpu, after the shared model code of nsgpu_p2p_dev.h).
 //
 // Per conservative window three kernels, replayed from a hipGraph:
 //   k2_pa      appends the last window (dispatch log / digest; its children get their uids) and forms
@@ -3767,4 +3767,10 @@ __global__ void k_inject(const P2PDev M, uint32_t a, uint64_t now, uint32_t cur,
   C.uid = uid0 + E.n;
   out[0] = C.uid;
   out[1] = E.trseq;
+}
+
+// Empties the deferred pipeline's partial records (create, reset).
+__global__ void k_part_clear(Ctl *C) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < (uint32_t)NPARTS) *part_rec(C, i) = Part{~0ull, ~0ull, ~0ull, 0};
 }

@@ -119,6 +119,32 @@ def test_rccl_single_rank():
     assert_same(o, g2)
 
 
+def test_rccl_single_rank_window_cut():
+    """The pause path of a one-rank RCCL engine: 48x48 on one rank overflows its window (it holds the events that
+    test_window_cut_agreement splits over two), so the replay loop pauses for a cut, every candidate is sorted
+    into the run arrays, the rank's fitting key is "all-gathered" by the one-rank device copy and the first chunk
+    moves in.  Every counter, the digest, the final time and the next uid equal the oracle's."""
+    sc = p2p.grid(48, 48)
+    o = oracle(sc)
+    comm = p2p.Comm(p2p.Comm.unique_id(), 1, 0)
+    eng = p2p.DistEngine(sc, np.zeros(sc.n_nodes, np.uint32), 0, 1, comm)
+    g = eng.run()
+    assert g[0].refits > 0
+    assert_same(o, g, log=False)
+
+
+def test_rccl_single_rank_eager_launches():
+    """A partitioned engine's windows launched kernel by kernel (set_eager) instead of as graph replays: the same
+    full pop log as the oracle's, either way."""
+    sc = p2p.grid(12, 12)
+    o = oracle(sc, 100000)
+    comm = p2p.Comm(p2p.Comm.unique_id(), 1, 0)
+    eng = p2p.DistEngine(sc, np.zeros(sc.n_nodes, np.uint32), 0, 1, comm, log_cap=100000)
+    assert_same(o, eng.run(log_n=100000))
+    eng.set_eager(True)
+    assert_same(o, eng.run(log_n=100000))
+
+
 @pytest.mark.parametrize("nranks", [2, 3])
 def test_incast_sorted_run_cuts_a_same_ts_group(nranks):
     """A partitioned sorted run (nsgpu_p2p_win.h): 5,000 leaves send to one hub at the same instant, so its

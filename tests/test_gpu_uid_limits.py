@@ -2,7 +2,7 @@
 188-219) that wraps to 0 after 0xffffffff.  Each engine starts its counter just below a limit, against the oracle
 started at the same uid (nsgpu_p2p_scenario.uid_first, nsgpu_sim_set_next_uid, nsref_wifil_mac.uid_first):
 
-  * the deferred p2p pipeline's provisional-uid range (UID_DF_SOFT, nsgpu_p2p.hip): the run hands over to the
+  * the deferred p2p pipeline's provisional-uid range (UID_DF_SOFT, nsgpu_p2p_dev.h): the run hands over to the
     scanning pipeline there and stays bit-exact past UID_DF_LIMIT;
   * the traced engine's old 2^31 limit (local records' trace uids are now flagged, not bit-31 tagged);
   * 2^32: a run whose last uid is 0xfffffffe is bit-exact; one more uid and the reference would hand out
@@ -18,7 +18,7 @@ import trace
 
 pytestmark = pytest.mark.gpu
 
-UID_DF_SOFT = 0x3FE00000 - (1 << 22)  # nsgpu_p2p.hip
+UID_DF_SOFT = 0x3FE00000 - (1 << 22)  # nsgpu_p2p_dev.h
 U32 = 0xFFFFFFFF
 
 
