@@ -6,6 +6,8 @@ CalculateSnrPer fixture (wifi-interference-test-suite.cc only compares PERs of i
 reference-held vector pins SNR / PER; what pins them is tests/wifi_per_ref.py, an independent high-precision
 evaluation of the reference's formulas, to which tests/test_gpu_wifi_per.py holds the device (every mode,
 both models, CalculatePer's interval cases) and tests/test_wifi_per_cpu.py the oracle used here."""
+import functools
+
 import numpy as np
 import pytest
 
@@ -80,15 +82,9 @@ def test_grid_100x100_short_stop_full_pop_log():
     assert tot["sends"] > 200 and tot["dispatched"] > 2_000_000 and len(ends) > 1000
 
 
-@pytest.mark.parametrize("logged", [True, False])
-def test_epoch_order_paths_lds_hbm_host(logged):
-    """One SendPacket at 1 us, two at 1 ms, seven at 2 ms on the 100x100 grid (host closures scheduled in
-    send order): the epochs that end at the next sends hold ~10^4 events (k_wl_tail's keys in LDS), ~2x10^4
-    (more than LDS_EV: keys in HBM) and, in the last epoch, ~7x10^4 receptions plus every EndReceive (more
-    than ERANK_MAX: the host orders it).  Pop log, digest, end records and counters = the oracle's replay.
-    Unlogged (the bench's mode, VERDICT r05 item 9): the host-order epoch with no log, the order of the other
-    epochs behind the PHY on the second stream; count, digest, next uid and end records = the oracle's."""
-    import nsgpu
+@functools.lru_cache(maxsize=None)
+def _epoch_order_case():
+    """The sends of test_epoch_order_paths_lds_hbm_host and the oracle's replay of them (computed once)."""
     import nsref
     x, y, z = wifi.grid(100, 100.0)
     ph = wifi.LoopPhys(x, y, z, tx_cap=64, rxq_cap=1024, ni_cap=1024)
@@ -98,11 +94,28 @@ def test_epoch_order_paths_lds_hbm_host(logged):
     phy = np.array([p for _t, p in sends], np.uint32)
     size = np.full(len(sends), 1000, np.uint32)
     dbm, stop, cap = 16.0206 + 1.0, 30_000_000, 1 << 18
-    olog, oends, ophys, otot = nsref.wifil_replay(ph.c_struct(), ts, phy, size, wifi.DSSS_1M, wifi.PREAMBLE_LONG, dbm,
-                                                  stop, n, wifi.WIFIL_END_DTYPE, wifi.PHY_COUNTERS_DTYPE, log_cap=cap)
+    oracle = nsref.wifil_replay(ph.c_struct(), ts, phy, size, wifi.DSSS_1M, wifi.PREAMBLE_LONG, dbm, stop, n,
+                                wifi.WIFIL_END_DTYPE, wifi.PHY_COUNTERS_DTYPE, log_cap=cap)
+    return ph, sends, dbm, stop, cap, oracle
+
+
+@pytest.mark.parametrize("logged,bounds", [pytest.param(True, None, id="True"), pytest.param(False, None, id="False"),
+                                           pytest.param(True, [0, 3000, 10000], id="True-group"),
+                                           pytest.param(False, [0, 3000, 10000], id="False-group")])
+def test_epoch_order_paths_lds_hbm_host(logged, bounds):
+    """One SendPacket at 1 us, two at 1 ms, seven at 2 ms on the 100x100 grid (host closures scheduled in
+    send order): the epochs that end at the next sends hold ~10^4 events (k_wl_tail's keys in LDS), ~2x10^4
+    (more than LDS_EV: keys in HBM) and, in the last epoch, ~7x10^4 receptions plus every EndReceive (more
+    than ERANK_MAX: the host orders it).  Pop log, digest, end records and counters = the oracle's replay.
+    Unlogged (the bench's mode, VERDICT r05 item 9): the host-order epoch with no log, the order of the other
+    epochs behind the PHY on the second stream; count, digest, next uid and end records = the oracle's.
+    bounds: the same through a partitioned handle of two partitions, whose last epoch goes through the union's
+    order and the host sort."""
+    import nsgpu
+    ph, sends, dbm, stop, cap, (olog, oends, ophys, otot) = _epoch_order_case()
     assert otot["dispatched"] > 100_000
     sim = nsgpu.Sim()
-    lp = wifi.LoopPhy(ph)
+    lp = wifi.LoopPhy(ph, bounds=bounds)
     sim.attach_wifi(lp)
     if logged:
         sim.set_log(cap)

@@ -5,6 +5,9 @@ events are exchanged.  The handle must answer as the single engine does: full (t
 digest, next uid, per-phy counters and end records equal the oracle's (nsref_wifil_run: the single-process
 restatement of yans-wifi-channel.cc:77-115 -> yans-wifi-phy.cc:399-522,770-799), through loopback groups of 1-4
 partitions (empty ones included) on one device and through RCCL with one rank."""
+import ctypes as C
+import functools
+
 import numpy as np
 import pytest
 
@@ -90,6 +93,54 @@ def test_grid_100x100_four_bands_and_one_rccl_rank():
     assert tot["sends"] > 200 and tot["dispatched"] > 2_000_000 and len(ends) > 1000
     comm = p2p.Comm(p2p.Comm.unique_id(), 1, 0)
     check(sc, 1 << 22, oracle=oracle, part=(0, 10000), comm=comm)
+
+
+@functools.lru_cache(maxsize=None)
+def _short_log_oracle(log_cap):
+    return run_oracle(scenario(), log_cap)
+
+
+@pytest.mark.parametrize("bounds", [None, [0, 5, 5, 16]], ids=["single", "group"])
+@pytest.mark.parametrize("log_cap", [64, 50])
+def test_log_shorter_than_the_run(log_cap, bounds):
+    """The 4x4 run (3,462 dispatches) with a log of 64 entries, on the single engine and on a group: count, digest,
+    next uid, end records and counters equal the oracle's, and the log holds the oracle's first 64 entries.  In the
+    oracle's order ranks 57-66 are host closures, so at 64 the log fills between two epochs: the epoch from rank 67
+    on finds *dispatched >= log_cap and logs nothing (the per-epoch switch).  With 50 entries the log fills inside
+    the epoch of ranks 42-56 (the fifteen Receives of one SendPacket), which is logged up to rank 49 and no further
+    (the per-entry rank < log_cap guard)."""
+    oracle = _short_log_oracle(log_cap)
+    assert all(len(a) == log_cap for a in oracle[0]) and oracle[3]["dispatched"] > log_cap
+    if log_cap == 50:  # (ranks 49 and 50: Receives of one SendPacket, consecutive places of its fan-out)
+        ctx = oracle[0][2]
+        assert ctx[41] == 0xFFFFFFFF and (ctx[42:50] != 0xFFFFFFFF).all()
+    check(scenario(), log_cap, oracle=oracle, bounds=bounds)
+
+
+class _Next(C.Structure):  # nsgpu_wifil_next (include/nsgpu.h)
+    _fields_ = [("ts", C.c_uint64), ("uid", C.c_uint32), ("phy", C.c_uint32), ("found", C.c_int32), ("pad_", C.c_int32),
+                ("ts_potential", C.c_uint64)]
+
+
+def test_between_epoch_queries_single_equals_group():
+    """nsgpu_wifil_pending and nsgpu_wifil_next_end after the same run to Stop (6x6 dense grid, every phy listened):
+    a group of four partitions (one empty) answers what the single engine answers — the pending count and earliest
+    ts, and the next EndReceive's record — and the answers are not empty (phys are receiving at Stop)."""
+    import nsgpu
+    sc = scenario(n_side=6, spacing=60.0, seed=3, period=12_000_000, stop_ns=80_000_000, size=600)
+    got = []
+    for bounds in (None, [0, 7, 7, 20, 36]):
+        _log, _ends, _phys, _tot, (sim, lp) = run_gpu(sc, bounds=bounds)
+        for i in range(sc["phys"].n_phy):
+            nsgpu.check(nsgpu.lib().nsgpu_wifil_listen(lp.h, i, 1))
+        nx = _Next()
+        nsgpu.check(nsgpu.lib().nsgpu_wifil_next_end(lp.h, C.byref(nx)))
+        got.append((lp.pending(), (nx.found, nx.ts, nx.uid, nx.phy, nx.ts_potential)))
+        lp.close()
+    (pend_s, next_s), (pend_g, next_g) = got
+    assert pend_s[0] != 0 and next_s[0] == 1
+    assert pend_g == pend_s, (pend_g, pend_s)
+    assert next_g == next_s, (next_g, next_s)
 
 
 def test_partitions_must_tile_the_phys():

@@ -1,4 +1,4 @@
-"""The closed-loop Wi-Fi engine's SNR / PER (csrc/nsgpu_wifil.hip: the error-rate models, CalculateSnr, the chunk
+"""The closed-loop Wi-Fi engine's SNR / PER (csrc/nsgpu_wifil_dev.h: the error-rate models, CalculateSnr, the chunk
 walk and product) against tests/wifi_per_ref.py, an independent 60-digit evaluation of the reference's formulas at the
 reference's own double-precision inputs (tests/wifi_per_cases.py) — not at anything the device reports.
 
