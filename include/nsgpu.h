@@ -582,6 +582,15 @@ int nsgpu_p2p_last_run_ms(nsgpu_p2p *h, double *gpu_ms);
  * it.  Single engines whose nodes have at most 16 devices, unless NSGPU_P2P_NARROW=1 was
  * set when the engine was created (the environment variables are listed after nsgpu_p2p_phase_read). */
 int nsgpu_p2p_get_wide(nsgpu_p2p *h, int *wide);
+/* UDP ports mode (nsgpu_p2p_scenario.app_port): UdpServer::GetReceived / GetLost and the loss counter's
+ * m_lastMaxSeqNum of every application, n_apps records (zeros for every other kind; a partitioned engine returns
+ * its own nodes' servers: the owner's values count). */
+int nsgpu_p2p_udp_servers(nsgpu_p2p *h, nsgpu_udp_server_record *out, void *stream);
+/* PacketLossCounter (packet-loss-counter.cc:32-120) on its own: a fresh counter of `window` bits (a multiple of 8
+ * in [8, 256]) is notified of seq[0 .. n) in order, lost[k] = GetLost () after seq[k].  on_device = 0: on the host;
+ * 1: the same function in a one-thread kernel on `stream` (the function the engine's handlers call). */
+int nsgpu_loss_counter_run(uint32_t window, const uint32_t *seq, uint64_t n, uint32_t *lost, int on_device,
+                           void *stream);
 /* Launch mode of nsgpu_p2p_run: 0 = hipGraph replays (default), 1 = the same kernels launched one by
  * one (also selected by the environment variable NSGPU_P2P_EAGER; used under rocprofv3). */
 int nsgpu_p2p_set_eager(nsgpu_p2p *h, int eager);

@@ -96,12 +96,13 @@ typedef struct nsgpu_loss_trace {
  * next-hop tables, OnOff (UDP, constant on/off times) sources and PacketSink sinks.  All arrays are
  * host pointers; devices and applications are listed in ns-3 creation order (Node::AddDevice /
  * Node::AddApplication), which fixes the setup-time uids (node-list.cc:124-131, node.cc:111-145). */
-enum nsgpu_app_kind { NSGPU_APP_ONOFF = 0, NSGPU_APP_SINK = 1, NSGPU_APP_ECHO_CLIENT = 2, NSGPU_APP_ECHO_SERVER = 3 };
+enum nsgpu_app_kind { NSGPU_APP_ONOFF = 0, NSGPU_APP_SINK = 1, NSGPU_APP_ECHO_CLIENT = 2, NSGPU_APP_ECHO_SERVER = 3,
+                      NSGPU_APP_UDP_CLIENT = 4, NSGPU_APP_UDP_SERVER = 5 };  /* (4, 5: ports mode only, below) */
 /* UdpEchoClient (udp-echo-client.cc): app_dst_node = the server's node, app_pkt_size = PacketSize,
  * app_count = MaxPackets, app_interval_ns = Interval, app_src_slot = the route-table slot of the
  * client's own node (the echo comes back there).  UdpEchoServer (udp-echo-server.cc): the node's bound
- * UDP endpoint, like a PacketSink; HandleRead sends every datagram back to its sender.  A node has
- * at most one bound endpoint (PacketSink or UdpEchoServer). */
+ * UDP endpoint, like a PacketSink; HandleRead sends every datagram back to its sender.  Without UDP ports
+ * (app_port NULL, below) a node has at most one bound endpoint (PacketSink or UdpEchoServer). */
 
 typedef struct nsgpu_p2p_scenario {
   uint32_t n_nodes;
@@ -165,7 +166,39 @@ typedef struct nsgpu_p2p_scenario {
    * whose earlier Schedule calls consumed uids; the engine refuses to pass 0xfffffffe (NSGPU_ERANGE) */
   uint32_t uid_first;
   uint32_t pad_uid_;
+  /* ---- UDP ports (appended: the fields above keep their offsets) ----
+   * app_port == NULL: no port is modelled — one bound endpoint a node, every datagram addressed to the node
+   * reaches it.  app_port given ("ports mode"): UdpL4Protocol::Receive -> Ipv4EndPointDemux::Lookup
+   * (udp-l4-protocol.cc:312-407, ipv4-end-point-demux.cc:195-307) for sockets bound to (Any, port): a datagram of
+   * flow a is delivered to the application of app_dst_node[a] whose app_port equals app_remote_port[a], else
+   * RX_ENDPOINT_UNREACH; a node may host several bound endpoints on distinct ports.  The binding is static, so
+   * nsgpu_p2p_create resolves it per flow; only bound / receiving changes at run time.
+   *   app_port          bound port of a PacketSink / UdpEchoServer / UdpServer (not 0; other kinds: ignored)
+   *   app_remote_port   destination port of an OnOff / UdpEchoClient / UdpClient
+   *   app_loss_window   UdpServer PacketWindowSize: a multiple of 8 in [8, 256]
+   * UdpClient (udp-client.cc:116-187): app_pkt_size = PacketSize (the 12-byte SeqTsHeader included, [12, 1472]),
+   * app_count = MaxPackets (<= 2^24), app_interval_ns = Interval; m_sent advances only when Send succeeded.
+   * UdpServer (udp-server.cc:109-190): StopApplication clears the receive callback only — the socket stays
+   * bound, later datagrams still cost their DoForwardUp event and count nothing. */
+  const uint32_t *app_port;
+  const uint32_t *app_remote_port;
+  const uint32_t *app_loss_window;
 } nsgpu_p2p_scenario;
+
+/* PacketLossCounter (packet-loss-counter.cc:32-120) of one UdpServer, with the server's m_received: the
+ * state nsgpu_loss_counter_notify (csrc/nsgpu_loss_counter.h) advances, on the host and on the device. */
+#define NSGPU_LOSS_WINDOW_MAX 256u
+typedef struct nsgpu_loss_counter {
+  uint32_t lost;          /* m_lost */
+  uint32_t last_max_seq;  /* m_lastMaxSeqNum */
+  uint32_t window;        /* m_bitMapSize * 8 */
+  uint32_t received;      /* UdpServer::m_received */
+  uint8_t map[NSGPU_LOSS_WINDOW_MAX / 8];  /* m_receiveBitMap (window / 8 bytes used, 0xFF at start) */
+} nsgpu_loss_counter;     /* 48 bytes */
+/* What nsgpu_p2p_udp_servers returns per application (zeros for every kind but NSGPU_APP_UDP_SERVER). */
+typedef struct nsgpu_udp_server_record {
+  uint32_t received, lost, last_max_seq, pad_;
+} nsgpu_udp_server_record;
 
 /* Packet descriptor flags (the descriptor {app, ipid, size, ttl} of a datagram): an echo reply
  * travelling back to its client (app) ... */
@@ -174,7 +207,12 @@ typedef struct nsgpu_p2p_scenario {
  * sender: NSGPU_PKT_ICMP_UNREACH = destination unreachable (port), else time exceeded (TTL);
  * NSGPU_PKT_ICMP_OF_REPLY = the offending datagram was an echo reply.  An ICMP descriptor packs the
  * offending datagram's IPv4 header fields: ipid = own | offending << 16 (16 bits each), size = 56 (the
- * ICMP packet's IPv4 length), ttl = own TTL | offending TTL << 8 | offending IPv4 length << 16. */
+ * ICMP packet's IPv4 length), ttl = own TTL | offending TTL << 8 | offending IPv4 length << 16.
+ * A UDP datagram's ttl word holds the IPv4 TTL in its low 8 bits; a UdpClient's datagram carries its
+ * SeqTsHeader sequence number (m_sent, < 2^24) in the other 24: ttl = TTL | seq << 8 (0 for every other
+ * sender, which is what a UdpServer reads from a payload without the header).  Every reader of the TTL takes
+ * the low byte; an ICMP descriptor's "offending TTL" is that byte, and so is the TTL of the Ipv4 Drop record
+ * that follows a time-exceeded error (it is rebuilt from the error's descriptor). */
 #define NSGPU_PKT_ICMP 0x40000000u
 #define NSGPU_PKT_ICMP_UNREACH 0x20000000u
 #define NSGPU_PKT_ICMP_OF_REPLY 0x10000000u

@@ -16,6 +16,13 @@ namespace nsgpu {
 
 using namespace nsgpu;
 
+namespace nsgpu {
+// k2_handle<WIDE, XL, DF, PORTS = true> (nsgpu_p2p_ports.hip: the ports-mode handlers are a translation unit, and
+// so a code object, of their own — this one holds the kernels it held before ports existed, laid out as they were)
+void launch_handle_ports(const P2PDev &M, bool wide, bool xl, bool df, int grid, hipStream_t s, hipEvent_t ev0,
+                         hipEvent_t ev1);
+}  // namespace nsgpu
+
 // (nsgpu_comm, NCCL_TRY: nsgpu_internal.h)
 
 extern "C" int nsgpu_comm_unique_id(uint8_t *id) {
@@ -81,6 +88,7 @@ struct nsgpu_p2p {
   uint64_t *init_ts = nullptr;
   uint32_t *init_uid = nullptr, *init_ctx = nullptr, *init_kind = nullptr, *init_a = nullptr;
   const DevRec *dev_init = nullptr;  // device records after reset (tx state idle)
+  const nsgpu_loss_counter *loss_init = nullptr;  // ports mode: the UdpServers' loss counters after reset
   uint32_t n_apps = 0;
   // partitioned run
   nsgpu_comm *comm = nullptr;  // RCCL transport (null: a loopback group member)
@@ -144,6 +152,8 @@ struct EnginePlan {
   bool has_echo = false;
   std::vector<uint32_t> napps, node_list;
   std::vector<int32_t> sink;
+  bool ports = false;               // ports mode (nsgpu_p2p_scenario.app_port given)
+  std::vector<int32_t> ep_of_flow;  // ports mode: the application a sender's datagrams are delivered to (-1: none)
   int64_t tx_min = 0, lx = 0, send_ivl = 0;
   int64_t lookahead[K_NKINDS], lookw[K_NKINDS];
   // the setup-time events (this rank's, partitioned) and the bound of window 0 (the whole setup: every rank)
@@ -204,14 +214,38 @@ static int plan_engine(const nsgpu_p2p_scenario *sc, const uint32_t *owner, int 
   bool &has_echo = P.has_echo;
   has_echo = false;
   int64_t echo_ivl = (int64_t)1 << 61;
+  const bool ports = sc->app_port != nullptr;
+  P.ports = ports;
+  if (ports && !sc->app_remote_port) return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: app_port without app_remote_port");
   for (uint32_t a = 0; a < A; a++) {
     if (sc->app_node[a] >= N) return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: app %u: bad node", a);
     napps[sc->app_node[a] + 1]++;
     const uint32_t ak = sc->app_kind[a];
-    if (ak == NSGPU_APP_SINK || ak == NSGPU_APP_ECHO_SERVER) {  // the node's bound UDP endpoint
-      if (sink[sc->app_node[a]] >= 0)
-        return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: node %u has two bound endpoints", sc->app_node[a]);
-      sink[sc->app_node[a]] = (int32_t)a;
+    if ((ak == NSGPU_APP_UDP_CLIENT || ak == NSGPU_APP_UDP_SERVER) && !ports)
+      return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: app %u: UdpClient / UdpServer need UDP ports (app_port)", a);
+    if (ak == NSGPU_APP_UDP_SERVER) {  // (bound like a sink: the endpoints are resolved below)
+      if (!sc->app_loss_window || sc->app_loss_window[a] % 8 != 0 || sc->app_loss_window[a] < 8 ||
+          sc->app_loss_window[a] > NSGPU_LOSS_WINDOW_MAX)
+        return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: UdpServer %u: PacketWindowSize must be a multiple of 8 in [8, 256]", a);
+    } else if (ak == NSGPU_APP_UDP_CLIENT) {
+      if (!sc->app_count || !sc->app_interval_ns || sc->app_dst_node[a] >= N || sc->app_dst_slot[a] >= sc->n_dst ||
+          sc->app_ttl[a] == 0 || sc->app_ttl[a] > 255 || sc->app_dst_node[a] == sc->app_node[a] ||
+          sc->app_interval_ns[a] < 0 ||
+          (sc->app_src_slot && sc->app_src_slot[a] != 0xffffffffu && sc->app_src_slot[a] >= sc->n_dst))
+        return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: UdpClient %u: bad destination/ttl/interval/source slot", a);
+      if (sc->app_pkt_size[a] < 12 || sc->app_pkt_size[a] > 1472)
+        return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: UdpClient %u: PacketSize %u outside [12, 1472]", a,
+                         sc->app_pkt_size[a]);
+      if (sc->app_count[a] > (1u << 24))  // (the descriptor carries the sequence number in 24 bits)
+        return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: UdpClient %u: MaxPackets %u above 2^24", a, sc->app_count[a]);
+      min_pkt = std::min(min_pkt, sc->app_pkt_size[a]);
+      echo_ivl = std::min(echo_ivl, sc->app_interval_ns[a]);
+    } else if (ak == NSGPU_APP_SINK || ak == NSGPU_APP_ECHO_SERVER) {  // the node's bound UDP endpoint
+      if (!ports) {
+        if (sink[sc->app_node[a]] >= 0)
+          return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: node %u has two bound endpoints", sc->app_node[a]);
+        sink[sc->app_node[a]] = (int32_t)a;
+      }
       if (ak == NSGPU_APP_ECHO_SERVER) {
         if (sc->app_ttl[a] == 0) return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: UdpEchoServer %u: ttl", a);
         has_echo = true;
@@ -241,6 +275,45 @@ static int plan_engine(const nsgpu_p2p_scenario *sc, const uint32_t *owner, int 
                          sc->app_pkt_size[a]);
     }
     if (A > NSGPU_PKT_APP) return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: more than 2^28 applications");
+  }
+  if (ports) {
+    // Ipv4EndPointDemux for sockets bound to (Any, port): the binding (node, port) -> application is static
+    auto bound = [&](uint32_t k) { return k == NSGPU_APP_SINK || k == NSGPU_APP_ECHO_SERVER || k == NSGPU_APP_UDP_SERVER; };
+    auto sender = [&](uint32_t k) { return k == NSGPU_APP_ONOFF || k == NSGPU_APP_ECHO_CLIENT || k == NSGPU_APP_UDP_CLIENT; };
+    std::vector<std::vector<uint32_t>> eps(N);
+    std::vector<uint8_t> sends(N, 0);
+    for (uint32_t a = 0; a < A; a++)
+      if (sender(sc->app_kind[a])) sends[sc->app_node[a]] = 1;
+    for (uint32_t a = 0; a < A; a++) {
+      if (!bound(sc->app_kind[a])) continue;
+      const uint32_t n = sc->app_node[a], port = sc->app_port[a];
+      if (port == 0 || port > 65535) return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: app %u: bound port %u", a, port);
+      for (uint32_t b : eps[n])  // the second Bind fails (ipv4-end-point-demux.cc:60-76)
+        if (sc->app_port[b] == port)
+          return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: node %u has two applications bound to port %u", n, port);
+      // a sending application's sockets take ephemeral ports from 49152 up (ipv4-end-point-demux.cc:351-372)
+      if (port >= 49152 && sends[n])
+        return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: app %u: port %u is in the ephemeral range of node %u's senders",
+                         a, port, n);
+      eps[n].push_back(a);
+    }
+    P.ep_of_flow.assign(A, -1);
+    std::vector<uint8_t> other(N, 0);  // a flow addressed to the node targets another port than its first endpoint's
+    for (uint32_t a = 0; a < A; a++) {
+      if (!sender(sc->app_kind[a])) continue;
+      const uint32_t n = sc->app_dst_node[a];
+      for (uint32_t b : eps[n])
+        if (sc->app_port[b] == sc->app_remote_port[a]) P.ep_of_flow[a] = (int32_t)b;
+      const int32_t e = P.ep_of_flow[a];
+      if (eps[n].empty() || e != (int32_t)eps[n][0]) other[n] = 1;
+      // a UdpServer reads a SeqTsHeader from every datagram (udp-server.cc:159-160)
+      if (e >= 0 && sc->app_kind[e] == NSGPU_APP_UDP_SERVER && sc->app_pkt_size[a] < 12)
+        return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: app %u: %u-byte payload to UdpServer %d holds no SeqTsHeader", a,
+                         sc->app_pkt_size[a], e);
+    }
+    // sink[n]: the node's single endpoint when every flow addressed to n targets it; EP_BY_FLOW: per flow
+    for (uint32_t n = 0; n < N; n++)
+      sink[n] = eps[n].empty() ? -1 : (eps[n].size() == 1 && !other[n]) ? (int32_t)eps[n][0] : EP_BY_FLOW;
   }
   uint32_t &maxapps = P.maxapps;
   maxapps = 0;
@@ -428,7 +501,13 @@ static int create_engine(const nsgpu_p2p_scenario *sc, const uint32_t *owner, in
   TRY(dupload(h, &M.app_kind, sc->app_kind, A));
   TRY(dupload(h, &M.app_node, sc->app_node, A));
   TRY(dupload(h, &M.app_dst_node, sc->app_dst_node, A));
-  TRY(dupload(h, &M.app_dst_slot, sc->app_dst_slot, A));
+  if (P.ports) {  // (the per-flow endpoint table lies behind the slots: ep_of_flow)
+    std::vector<uint32_t> ds(sc->app_dst_slot, sc->app_dst_slot + A);
+    for (uint32_t a = 0; a < A; a++) ds.push_back((uint32_t)P.ep_of_flow[a]);
+    TRY(dupload(h, &M.app_dst_slot, ds.data(), 2 * (size_t)A));
+  } else {
+    TRY(dupload(h, &M.app_dst_slot, sc->app_dst_slot, A));
+  }
   TRY(dupload(h, &M.app_pkt_size, sc->app_pkt_size, A));
   TRY(dupload(h, &M.app_max_bytes, sc->app_max_bytes, A));
   TRY(dupload(h, &M.app_ttl, sc->app_ttl, A));
@@ -442,7 +521,7 @@ static int create_engine(const nsgpu_p2p_scenario *sc, const uint32_t *owner, in
     std::vector<int64_t> ivl(A, 0);
     for (uint32_t a = 0; a < A; a++) {
       src[a] = sc->app_src_slot ? sc->app_src_slot[a] : 0xffffffffu;
-      if (sc->app_kind[a] == NSGPU_APP_ECHO_CLIENT) {
+      if (sc->app_kind[a] == NSGPU_APP_ECHO_CLIENT || sc->app_kind[a] == NSGPU_APP_UDP_CLIENT) {
         cnt[a] = sc->app_count[a];
         ivl[a] = sc->app_interval_ns[a];
       }
@@ -485,7 +564,16 @@ static int create_engine(const nsgpu_p2p_scenario *sc, const uint32_t *owner, in
   TRY(dalloc(h, &M.app_tot, A));
   TRY(dalloc(h, &M.node_ipid, N));
   TRY(dalloc(h, &M.app_last_start, A));
-  TRY(dalloc(h, &M.appc, A));
+  if (P.ports) {  // (the UdpServers' loss counters lie behind the counters: loss_counters)
+    static_assert(sizeof(nsgpu_loss_counter) == 2 * sizeof(nsgpu_app_counters), "loss_counters");
+    TRY(dalloc(h, &M.appc, 3 * (size_t)A));
+    std::vector<nsgpu_loss_counter> lc(A);
+    for (uint32_t a = 0; a < A; a++)
+      nsgpu_loss_counter_init(&lc[a], sc->app_kind[a] == NSGPU_APP_UDP_SERVER ? sc->app_loss_window[a] : 8u);
+    TRY(dupload(h, &h->loss_init, lc.data(), A));
+  } else {
+    TRY(dalloc(h, &M.appc, A));
+  }
   TRY(dalloc(h, &M.node_tab, (size_t)N * NTAB));
   const std::vector<uint64_t> &its = P.its;
   const std::vector<uint32_t> &iuid = P.iuid, &ictx = P.ictx, &ikind = P.ikind, &ia = P.ia;
@@ -737,6 +825,9 @@ extern "C" int nsgpu_p2p_reset(nsgpu_p2p *h, void *stream) {
   if (M.trace) NSGPU_HIP(hipMemsetAsync(M.trace_n, 0, sizeof(unsigned long long), s));
   NSGPU_HIP(hipMemsetAsync(M.app_last_start, 0, A * sizeof(uint64_t), s));
   NSGPU_HIP(hipMemsetAsync(M.appc, 0, A * sizeof(nsgpu_app_counters), s));
+  if (h->loss_init)
+    NSGPU_HIP(hipMemcpyAsync(loss_counters(M.appc, A), h->loss_init, A * sizeof(nsgpu_loss_counter),
+                             hipMemcpyDeviceToDevice, s));
   NSGPU_HIP(hipMemsetAsync(M.node_tab, 0, (size_t)M.n_nodes * NTAB * sizeof(uint32_t), s));
   NSGPU_HIP(hipMemsetAsync(M.wrank, 0, 2 * WTOT * sizeof(uint32_t), s));
   NSGPU_HIP(hipMemsetAsync(M.lrank, 0, 2 * LMAX * sizeof(uint32_t), s));
@@ -786,7 +877,9 @@ bool launch_kernel(nsgpu_p2p *h, int k, hipStream_t s, bool df, hipEvent_t ev0 =
       else NSGPU_KLAUNCH((k2_pa<false, false>), dim3(pa_grid_rt<false>(h->M)), dim3(TB), s, ev0, ev1, h->M);
       return true;
     case 1:
-      if (df) NSGPU_KLAUNCH((k2_handle<true, false, true>), dim3(K2_GRID), dim3(HB), s, ev0, ev1, h->M);
+      // (a scenario with ports: the handlers with the endpoint lookup, UdpClient, UdpServer — nsgpu_p2p_ports.hip)
+      if (h->loss_init) launch_handle_ports(h->M, wide, false, df, K2_GRID, s, ev0, ev1);
+      else if (df) NSGPU_KLAUNCH((k2_handle<true, false, true>), dim3(K2_GRID), dim3(HB), s, ev0, ev1, h->M);
       else if (wide) NSGPU_KLAUNCH(k2_handle<true>, dim3(K2_GRID), dim3(HB), s, ev0, ev1, h->M);
       else NSGPU_KLAUNCH(k2_handle<false>, dim3(K2_GRID), dim3(HB), s, ev0, ev1, h->M);
       return true;
@@ -1047,11 +1140,13 @@ static void dist_pa(const P2PDev &M, hipStream_t s) {
   if (M.wide) hipLaunchKernelGGL((k2_pa<true, true>), dim3(GRID_POOL_DIST), dim3(TB), 0, s, M);
   else hipLaunchKernelGGL((k2_pa<true, false>), dim3(GRID_POOL_DIST), dim3(TB), 0, s, M);
 }
-static void dist_handle(const P2PDev &M, hipStream_t s) {
+static void dist_handle(const P2PDev &M, hipStream_t s, bool ports) {
   if (M.wide) {
-    hipLaunchKernelGGL((k2_handle<true, true>), dim3(K2_GRID_W), dim3(HB), 0, s, M);
+    if (ports) launch_handle_ports(M, true, true, false, K2_GRID_W, s, nullptr, nullptr);
+    else hipLaunchKernelGGL((k2_handle<true, true>), dim3(K2_GRID_W), dim3(HB), 0, s, M);
     hipLaunchKernelGGL(k_xlcompact, dim3(NLR), dim3(HB), 0, s, M);
   }
+  else if (ports) launch_handle_ports(M, false, false, false, K2_GRID, s, nullptr, nullptr);
   else hipLaunchKernelGGL(k2_handle<false>, dim3(K2_GRID), dim3(HB), 0, s, M);
 }
 // Before the X1 exchange: this rank's records ranked among themselves and, with more ranks, sorted into its X1.
@@ -1080,7 +1175,7 @@ static int launch_windows_dist(nsgpu_p2p *h, hipStream_t s, int nwin = NWIN) {
   for (int w = 0; w < nwin && !rc; w++) {
     dist_pa(M, s);
     rc = x_allgather(h, M.x0_send, M.x0_recv, X0B, s);
-    dist_handle(M, s);
+    dist_handle(M, s, h->loss_init != nullptr);
     dist_rank(M, s);
     if (!rc) rc = x_allgather(h, M.x1_send, M.x1_recv, X1B, s);
     dist_rank_fin(M, s);
@@ -1662,6 +1757,23 @@ extern "C" int nsgpu_p2p_last_run_ms(nsgpu_p2p *h, double *gpu_ms) {
   return NSGPU_OK;
 }
 
+// UdpServer::GetReceived / GetLost of every application (zeros for other kinds, and for a scenario without ports).
+extern "C" int nsgpu_p2p_udp_servers(nsgpu_p2p *h, nsgpu_udp_server_record *out, void *stream) {
+  if (!h || !out) return set_error(NSGPU_EINVAL, "nsgpu_p2p_udp_servers: null");
+  hipStream_t s = (hipStream_t)stream;
+  const uint32_t A = h->M.n_apps;
+  memset(out, 0, A * sizeof(*out));
+  if (!h->loss_init) return NSGPU_OK;
+  std::vector<nsgpu_loss_counter> lc(A);
+  NSGPU_HIP(hipMemcpyAsync(lc.data(), loss_counters(h->M.appc, A), A * sizeof(nsgpu_loss_counter),
+                           hipMemcpyDeviceToHost, s));
+  NSGPU_HIP(hipStreamSynchronize(s));
+  for (uint32_t a = 0; a < A; a++)
+    if (h->app_kind[a] == NSGPU_APP_UDP_SERVER)
+      out[a] = nsgpu_udp_server_record{lc[a].received, lc[a].lost, lc[a].last_max_seq, 0};
+  return NSGPU_OK;
+}
+
 extern "C" int nsgpu_p2p_results(nsgpu_p2p *h, nsgpu_p2p_stats *stats, nsgpu_dev_counters *devc,
                                  nsgpu_app_counters *appc, uint64_t *log_ts, uint32_t *log_uid, uint32_t *log_ctx,
                                  uint64_t log_n, uint32_t *error, void *stream) {
@@ -1720,7 +1832,7 @@ static void launch_windows_group(nsgpu_p2p_group *g, hipStream_t s, int nwin = N
   for (int w = 0; w < nwin; w++) {
     for (auto *h : g->m) dist_pa(h->M, s);
     hipLaunchKernelGGL(k_copies, dim3(n * n), dim3(256), 0, s, (const CopyDesc *)g->d_x[0]);
-    for (auto *h : g->m) dist_handle(h->M, s);
+    for (auto *h : g->m) dist_handle(h->M, s, h->loss_init != nullptr);
     for (auto *h : g->m) dist_rank(h->M, s);
     hipLaunchKernelGGL(k_copies, dim3(n * n), dim3(256), 0, s, (const CopyDesc *)g->d_x[1]);
     for (auto *h : g->m) dist_rank_fin(h->M, s);

@@ -23,6 +23,7 @@
 #include <stddef.h>
 #include "nsgpu_device.h"
 #include "nsgpu_internal.h"
+#include "nsgpu_loss_counter.h"
 #include "nsgpu_p2p_span.h"
 #include "nsgpu_wave.h"
 
@@ -251,6 +252,17 @@ struct LKey {
 };
 static_assert(sizeof(LKey) == 64, "LKey: four 16-B loads");
 
+// Node-part result of one hub event (k2_handle hub blocks, between the two passes).
+struct HubEv {
+  uint32_t op, dev;
+  Pkt p;
+  int64_t pdelay;      // trailing child (OnOffApplication::ScheduleNextTx after SendPacket)
+  uint32_t pkind, pa;  // pkind == 0: none
+  uint32_t n, seq;     // children and trace sink calls the node part made
+  uint32_t cancelled, pad;  // pad: the node part's inline DoForwardUp children
+  uint32_t ctx, xdrop;      // the event's context (its Schedule calls inherit it); NodeOut::xdrop
+};
+
 struct P2PDev {
   // scenario
   uint32_t n_nodes, n_devices, n_apps, n_dst, qcap, maxc;
@@ -265,7 +277,7 @@ struct P2PDev {
   const uint32_t *app_count, *app_src_slot;  // UdpEchoClient MaxPackets, route slot of its own node
   const int64_t *app_interval;               // UdpEchoClient Interval
   const uint32_t *node_app_off, *node_app_list;  // CSR: apps of each node in AddApplication order
-  const int32_t *sink_of_node;                    // PacketSink of each node (-1: none)
+  const int32_t *sink_of_node;                    // PacketSink of each node (-1: none; EP_BY_FLOW: see ep_of_flow)
   uint32_t icmp;                                  // ICMP errors are generated (scenario icmp)
   int64_t lookahead[K_NKINDS];
   int64_t lookw[K_NKINDS];  // wide windows: the smallest delay of a child that does not run in the window
@@ -273,7 +285,8 @@ struct P2PDev {
   // model state
   DevRec *dev;  // per-device tx state + transmit parameters (one record per device)
   Pkt *q_buf;
-  uint32_t *app_flags;    // bit0 started, bit1 sink active, bit2 send live, bit3 start/stop live
+  uint32_t *app_flags;    // bit0 started, bit1 sink active (endpoint bound), bit2 send live, bit3 start/stop live,
+                          // bit4 a UdpServer's endpoint, bit5 its receive callback is cleared (stopped, still bound)
   uint32_t *app_send_gen, *app_ss_gen, *app_residual, *app_tot;
   uint32_t *node_ipid;    // Ipv4L3Protocol::m_identification per node
   uint64_t *app_last_start;
@@ -380,6 +393,46 @@ __device__ __forceinline__ uint32_t block_exscan(uint32_t v, uint32_t *wsum, uin
   __syncthreads();
   *total = tot;
   return off + ex;
+}
+
+// ---------------- UDP ports (ports mode: nsgpu_p2p_scenario.app_port given) ----------------
+// Ipv4EndPointDemux::Lookup for sockets bound to (Any, port) is static, so create resolves it: sink_of_node[n] stays
+// the node's endpoint when every flow addressed to n targets the one endpoint n has (the path of a scenario without
+// ports, no further load), EP_BY_FLOW sends a Receive to the per-flow table — the application of the flow's
+// destination node bound to its remote port, or -1 — and -1 stays "none".  The table and the UdpServers' loss
+// counters lie behind app_dst_slot and appc in their allocations: P2PDev takes no further pointer (see hub_slot).
+constexpr int32_t EP_BY_FLOW = -2;
+constexpr uint32_t AF_BOUND = 2u, AF_UDP_SERVER = 16u, AF_RX_CLEARED = 32u;
+__device__ __forceinline__ int32_t ep_of_flow(const P2PDev &M, uint32_t fa) {
+  return (int32_t)M.app_dst_slot[M.n_apps + fa];
+}
+__host__ __device__ __forceinline__ nsgpu_loss_counter *loss_counters(nsgpu_app_counters *appc, uint32_t n_apps) {
+  return reinterpret_cast<nsgpu_loss_counter *>(appc + n_apps);
+}
+// UdpServer::HandleRead (udp-server.cc:149-187): the SeqTsHeader's sequence number (the descriptor's upper 24 ttl
+// bits; 0 for a payload that carries none), NotifyReceived, m_received++.  Out of line: the handlers of a scenario
+// without a UdpServer never reach it.
+__device__ __noinline__ void udp_server_rx(nsgpu_loss_counter *lc, nsgpu_app_counters *ac, uint32_t size, uint32_t ttl) {
+  nsgpu_loss_counter_notify(lc, ttl >> 8);
+  lc->received++;
+  ac->rx_packets++;
+  ac->rx_bytes += size - 28;
+}
+// Ipv4EndPoint::DoForwardUp -> UdpSocketImpl::ForwardUp -> the endpoint's receive callback, for the endpoints
+// whose HandleRead schedules nothing (PacketSink, UdpServer): sa = the endpoint's application, *pp the datagram.
+// PORTS: the handler kernels are instantiated for engines without and with ports (k2_handle<.., PORTS>): what ports
+// mode adds to an event — the per-flow endpoint, UdpClient, UdpServer — is compiled into the second set only, so an
+// engine without ports runs the code it ran before ports existed.
+template <bool PORTS>
+__device__ __forceinline__ void fwd_up_leaf(const P2PDev &M, uint32_t sa, const Pkt *pp) {
+  const uint32_t f = M.app_flags[sa];
+  if (!(f & AF_BOUND)) return;
+  if (PORTS && (f & AF_UDP_SERVER)) {  // (a stopped UdpServer: the event is dispatched, nothing is counted)
+    if (!(f & AF_RX_CLEARED)) udp_server_rx(loss_counters(M.appc, M.n_apps) + sa, M.appc + sa, pp->size, pp->ttl);
+    return;
+  }
+  M.appc[sa].rx_packets++;
+  M.appc[sa].rx_bytes += pp->size - 28;
 }
 
 // ---------------- model (runs on the thread that owns the event's node) ----------------
@@ -646,6 +699,7 @@ __device__ __forceinline__ void schedule_stop_event(const P2PDev &M, Emit &E, ui
   M.app_flags[a] |= 8u;
   E.child(seconds_to_ts(M.app_on_s[a]), E.ctx, K_STOP_SENDING | (g << 8), a, Pkt{0, 0, 0, 0});
 }
+template <bool PORTS = false>
 __device__ __forceinline__ void stop_application(const P2PDev &M, uint32_t a, uint64_t now) {
   const uint32_t k = M.app_kind[a];
   if (k == NSGPU_APP_SINK || k == NSGPU_APP_ECHO_SERVER) {  // m_socket->Close ()
@@ -654,6 +708,14 @@ __device__ __forceinline__ void stop_application(const P2PDev &M, uint32_t a, ui
   }
   if (k == NSGPU_APP_ECHO_CLIENT) {  // UdpEchoClient::StopApplication: Close; Simulator::Cancel (m_sendEvent)
     M.app_flags[a] &= ~(2u | 4u);
+    return;
+  }
+  if (PORTS && k == NSGPU_APP_UDP_SERVER) {  // UdpServer::StopApplication: SetRecvCallback (null); the socket stays bound
+    M.app_flags[a] |= AF_RX_CLEARED;
+    return;
+  }
+  if (PORTS && k == NSGPU_APP_UDP_CLIENT) {  // UdpClient::StopApplication: Simulator::Cancel (m_sendEvent)
+    M.app_flags[a] &= ~4u;
     return;
   }
   cancel_events(M, a, now);
@@ -769,6 +831,7 @@ struct DstHint {
 };
 // rx_atomic: the device's rx counter is added with an atomic (hub blocks: other lanes add to it too;
 // holders: a no-return atomic, so the event does not wait for the counter's line).
+template <bool PORTS = false>
 __device__ __forceinline__ NodeOut node_part(const P2PDev &M, Emit &E, uint32_t kind_word, uint32_t a,
                                              const Pkt &pkt, int32_t sink, HStat &hs, bool rx_atomic = false,
                                              DstHint hint = DstHint{false, 0, 0}) {
@@ -793,7 +856,10 @@ __device__ __forceinline__ NodeOut node_part(const P2PDev &M, Emit &E, uint32_t 
       // LocalDeliver -> UdpL4Protocol::Receive (udp-l4-protocol.cc:312-407): the bound endpoint is the
       // client's own socket for an echo reply, else the node's PacketSink / UdpEchoServer.  An ICMP error
       // ends in Icmpv4L4Protocol::Receive -> UdpL4Protocol::ReceiveIcmp (no event, no counter).
-      const int32_t k = reply ? (int32_t)fa : sink;
+      int32_t k = reply ? (int32_t)fa : sink;
+      // (per flow: not for an ICMP error, whose word holds flag bits above the flow and finds no endpoint anyway)
+      if (PORTS && !reply && sink == EP_BY_FLOW)
+        k = (p.app & NSGPU_PKT_ICMP) ? -1 : ep_of_flow(M, p.app & NSGPU_PKT_APP);
       if (p.app & NSGPU_PKT_ICMP) {
       } else if (k < 0 || !(M.app_flags[k] & 2u)) {  // no bound endpoint: RX_ENDPOINT_UNREACH
         hs.unreach++;
@@ -852,6 +918,28 @@ __device__ __forceinline__ NodeOut node_part(const P2PDev &M, Emit &E, uint32_t 
         M.app_flags[a] |= 4u;
         post = Post{true, M.app_interval[a], K_SEND | (g << 8), a};
       }
+    } else if (PORTS && M.app_kind[a] == NSGPU_APP_UDP_CLIENT) {  // UdpClient::Send (udp-client.cc:148-187)
+      M.app_flags[a] = f & ~4u;
+      const uint32_t sz = M.app_pkt_size[a];  // Create<Packet> (m_size - 12) + SeqTsHeader
+      uint32_t sent = M.app_tot[a];           // seqTs.SetSeq (m_sent)
+      Pkt p{a, 0, sz + 8 + 20, M.app_ttl[a] | (sent << 8)};
+      const uint32_t an = M.app_node[a];
+      const uint32_t out = route_of(M, an, p);  // m_socket->Send (p): -1 with no route (udp-socket-impl.cc:595-601)
+      if (out == 0xffffffffu) {
+        hs.no_route++;
+      } else {  // ++m_sent only when Send returned >= 0
+        p.ipid = M.node_ipid[an]++;
+        act = Act{ACT_SEND, out, p};
+        M.app_tot[a] = ++sent;
+        M.appc[a].tx_packets++;
+        M.appc[a].tx_bytes += sz;
+      }
+      if (sent < M.app_count[a]) {  // Schedule (m_interval, &UdpClient::Send)
+        const uint32_t g = (M.app_send_gen[a] + 1) & 0xffffffu;
+        M.app_send_gen[a] = g;
+        M.app_flags[a] |= 4u;
+        post = Post{true, M.app_interval[a], K_SEND | (g << 8), a};
+      }
     } else {
       M.app_flags[a] = f & ~4u;
       const uint32_t sz = M.app_pkt_size[a];
@@ -888,13 +976,22 @@ __device__ __forceinline__ NodeOut node_part(const P2PDev &M, Emit &E, uint32_t 
           M.app_send_gen[a] = g;
           M.app_flags[a] |= 2u | 4u;
           E.child(0, E.ctx, K_SEND | (g << 8), a, Pkt{0, 0, 0, 0});
+        } else if (PORTS && M.app_kind[a] == NSGPU_APP_UDP_SERVER) {  // Bind (Any, port); SetRecvCallback (HandleRead)
+          M.app_flags[a] = (M.app_flags[a] | AF_BOUND | AF_UDP_SERVER) & ~AF_RX_CLEARED;
+        } else if (PORTS && M.app_kind[a] == NSGPU_APP_UDP_CLIENT) {
+          // UdpClient::StartApplication: Bind, Connect, SetRecvCallback (null), Schedule (Seconds (0), Send) — its
+          // ephemeral-port socket is no endpoint any flow of this subset addresses (bit 1 stays clear)
+          const uint32_t g = (M.app_send_gen[a] + 1) & 0xffffffu;
+          M.app_send_gen[a] = g;
+          M.app_flags[a] |= 4u;
+          E.child(0, E.ctx, K_SEND | (g << 8), a, Pkt{0, 0, 0, 0});
         } else {
           cancel_events(M, a, E.now);
           schedule_start_event(M, E, a);
         }
         break;
       case K_APP_STOP:
-        stop_application(M, a, E.now);
+        stop_application<PORTS>(M, a, E.now);
         break;
       case K_START_SENDING: {  // onoff-application.cc:196-206
         const uint32_t f = M.app_flags[a];
@@ -923,10 +1020,7 @@ __device__ __forceinline__ NodeOut node_part(const P2PDev &M, Emit &E, uint32_t 
       }
       case K_FWD_UP:  // DoForwardUp -> UdpSocketImpl::ForwardUp -> PacketSink::HandleRead (a = sink app)
       case K_FWD_UP_D:
-        if (M.app_flags[a] & 2u) {
-          M.appc[a].rx_packets++;
-          M.appc[a].rx_bytes += pkt.size - 28;
-        }
+        fwd_up_leaf<PORTS>(M, a, &pkt);
         break;
       case K_FWD_UP_Q:  // DoForwardUp -> UdpSocketImpl::ForwardUp -> UdpEcho{Server,Client}::HandleRead (a = endpoint app)
         if (M.app_flags[a] & 2u) {
@@ -966,7 +1060,11 @@ __device__ __forceinline__ bool run_event(const P2PDev &M, Emit &E, uint32_t kin
 }
 
 // Diagnostic build (-DNSGPU_PHASE_PROF, lib/libnsgpu_prof.so only): thread 0 of block 0 of each
-// pipeline kernel accumulates s_memrealtime (100 MHz) deltas between phase marks into g_phase.
+// pipeline kernel accumulates s_memrealtime (100 MHz) deltas between phase marks into g_phase.  The counters are
+// nsgpu_p2p.hip's: the handlers-only translation unit (nsgpu_p2p_ports.hip) defines none and records no marks.
+#if defined(NSGPU_PHASE_PROF) && defined(NSGPU_P2P_HANDLERS_ONLY)
+#undef NSGPU_PHASE_PROF
+#endif
 #ifdef NSGPU_PHASE_PROF
 __device__ uint64_t g_phase[64];
 #define PH_BEGIN() uint64_t ph_t_ = (threadIdx.x == 0 && blockIdx.x == 0) ? __builtin_amdgcn_s_memrealtime() : 0

@@ -1,0 +1,61 @@
+// nsgpu_p2p_ports.hip — the p2p subset's handler kernels for scenarios with UDP ports (k2_handle<.., PORTS = true>:
+// the per-flow endpoint lookup, UdpClient, UdpServer; nsgpu_p2p_dev.h "UDP ports"), and PacketLossCounter on its own.
+// A translation unit of its own, and so a code object of its own: nsgpu_p2p.hip's holds exactly the kernels it held
+// before ports existed, so the engines of scenarios without ports run the same code at the same layout.  The window
+// header is compiled here for k2_handle alone (NSGPU_P2P_HANDLERS_ONLY): its other kernels stay nsgpu_p2p.hip's.
+#define NSGPU_P2P_HANDLERS_ONLY
+#include "nsgpu_p2p_dev.h"
+namespace nsgpu {
+#include "nsgpu_p2p_win.h"
+
+void launch_handle_ports(const P2PDev &M, bool wide, bool xl, bool df, int grid, hipStream_t s, hipEvent_t ev0,
+                         hipEvent_t ev1) {
+  const dim3 g(grid), b(HB);
+  if (df) hipExtLaunchKernelGGL((k2_handle<true, false, true, true>), g, b, 0, s, ev0, ev1, 0, M);
+  else if (wide && xl) hipExtLaunchKernelGGL((k2_handle<true, true, false, true>), g, b, 0, s, ev0, ev1, 0, M);
+  else if (wide) hipExtLaunchKernelGGL((k2_handle<true, false, false, true>), g, b, 0, s, ev0, ev1, 0, M);
+  else hipExtLaunchKernelGGL((k2_handle<false, false, false, true>), g, b, 0, s, ev0, ev1, 0, M);
+}
+}  // namespace nsgpu
+
+using namespace nsgpu;
+
+// PacketLossCounter::NotifyReceived over seq[0 .. n): lost[k] = GetLost () after seq[k]; on_device = 0 runs
+// nsgpu_loss_counter_notify on the host, 1 in a one-thread kernel (the function the handlers call).
+__global__ void k_loss_counter(nsgpu_loss_counter c, const uint32_t *seq, uint64_t n, uint32_t *lost) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  for (uint64_t k = 0; k < n; k++) {
+    nsgpu_loss_counter_notify(&c, seq[k]);
+    lost[k] = c.lost;
+  }
+}
+extern "C" int nsgpu_loss_counter_run(uint32_t window, const uint32_t *seq, uint64_t n, uint32_t *lost, int on_device,
+                                      void *stream) {
+  if (n && (!seq || !lost)) return set_error(NSGPU_EINVAL, "nsgpu_loss_counter_run: null");
+  if (window % 8 != 0 || window < 8 || window > NSGPU_LOSS_WINDOW_MAX)
+    return set_error(NSGPU_EINVAL, "nsgpu_loss_counter_run: window must be a multiple of 8 in [8, 256]");
+  nsgpu_loss_counter c;
+  nsgpu_loss_counter_init(&c, window);
+  if (!on_device) {
+    for (uint64_t k = 0; k < n; k++) {
+      nsgpu_loss_counter_notify(&c, seq[k]);
+      lost[k] = c.lost;
+    }
+    return NSGPU_OK;
+  }
+  if (!n) return NSGPU_OK;
+  hipStream_t s = (hipStream_t)stream;
+  uint32_t *d = nullptr;
+  NSGPU_HIP(hipMalloc((void **)&d, 2 * n * sizeof(uint32_t)));
+  hipError_t e = hipMemcpyAsync(d, seq, n * sizeof(uint32_t), hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_loss_counter, dim3(1), dim3(64), 0, s, c, d, n, d + n);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(lost, d + n, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  (void)hipFree(d);
+  if (e != hipSuccess) return set_error(NSGPU_EHIP, "nsgpu_loss_counter_run: %s", hipGetErrorString(e));
+  return NSGPU_OK;
+}
+

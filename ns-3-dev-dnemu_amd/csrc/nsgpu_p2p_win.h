@@ -91,16 +91,7 @@ __device__ __forceinline__ uint32_t dense_rec(uint32_t d, uint32_t W, const uint
   return region_base(lo) + (k - pre[lo]);
 }
 
-// Node-part result of one hub event (k2_handle hub blocks, between the two passes).
-struct HubEv {
-  uint32_t op, dev;
-  Pkt p;
-  int64_t pdelay;      // trailing child (OnOffApplication::ScheduleNextTx after SendPacket)
-  uint32_t pkind, pa;  // pkind == 0: none
-  uint32_t n, seq;     // children and trace sink calls the node part made
-  uint32_t cancelled, pad;  // pad: the node part's inline DoForwardUp children
-  uint32_t ctx, xdrop;      // the event's context (its Schedule calls inherit it); NodeOut::xdrop
-};
+// (HubEv, the node-part result of one hub event: nsgpu_p2p_dev.h)
 
 constexpr int HUBL = 1024;  // events of a hub a block sorts in LDS (more: the window is dispatched as a run)
 
@@ -1142,7 +1133,7 @@ __device__ __forceinline__ void device_act_cached(const P2PDev &M, Emit &E, cons
   }
 }
 
-template <bool WIDE, bool DF = false>
+template <bool WIDE, bool DF = false, bool PORTS = false>
 __device__ __forceinline__ void handle_node2(const P2PDev &M, Ctl &C, uint32_t i0, uint32_t W, uint32_t base, Red &R,
                                              uint32_t *lds, const HCtl &hc, SlotPre sp, uint32_t *lcnt_sh) {
   uint32_t *chs = lds;
@@ -1240,11 +1231,7 @@ __device__ __forceinline__ void handle_node2(const P2PDev &M, Ctl &C, uint32_t i
             for (uint32_t j = 0; j < ncr; j++) {
               const uint32_t sl = xr * M.maxc + j;
               if ((E.ch_kind[sl] & 0xffu) != K_FWD_UP) continue;
-              const uint32_t sa = E.ch_a[sl];  // DoForwardUp -> PacketSink::HandleRead
-              if (M.app_flags[sa] & 2u) {
-                M.appc[sa].rx_packets++;
-                M.appc[sa].rx_bytes += E.ch_pkt[sl].size - 28;
-              }
+              fwd_up_leaf<PORTS>(M, E.ch_a[sl], &E.ch_pkt[sl]);  // DoForwardUp -> PacketSink / UdpServer::HandleRead
             }
           }
           pending = 0;
@@ -1292,7 +1279,7 @@ __device__ __forceinline__ void handle_node2(const P2PDev &M, Ctl &C, uint32_t i
         E.trseq = 0;
         E.lj = -1;
         {  // run_event with the device step on the cached state
-          const NodeOut o = node_part(M, E, kw, a, pk, sink, hs, true, hint);
+          const NodeOut o = node_part<PORTS>(M, E, kw, a, pk, sink, hs, true, hint);
           device_act_cached(M, E, o.act, D);
           if (o.xdrop) trace_te_drop(M, E, o.xdrop - 1, o.act.p);
           if (o.post.valid) E.child(o.post.delay, E.ctx, o.post.kind, o.post.a, Pkt{0, 0, 0, 0});
@@ -1613,6 +1600,7 @@ __device__ __forceinline__ bool hub_device_scan(const P2PDev &M, Emit &E, uint32
 // are dispatched first: the holder blocks are running or done when a hub block waits).
 constexpr uint32_t HOP_SER = 0xffu;  // hx[s].op: the node part is the hub block's (serial, node state)
 __device__ __forceinline__ uint32_t *hub_mark(const P2PDev &M) { return M.hub_slot + (uint64_t)NHUB * WCAP; }
+template <bool PORTS>
 __device__ __forceinline__ void hub_help(const P2PDev &M, Ctl &C, uint32_t i0, uint32_t W, uint32_t base,
                                          const HCtl &hc, SlotPre &sp) {
   uint32_t mark = NOSRC;
@@ -1662,9 +1650,10 @@ __device__ __forceinline__ void hub_help(const P2PDev &M, Ctl &C, uint32_t i0, u
               trace_ip_drop(M, E, sp.a, p);
             } else {
               p.ttl -= 1;
-              if (p.ttl == 0) {  // (ICMP off: a stateless event)
+              // (ICMP off: a stateless event; with ports the word's upper bits may hold a sequence number)
+              if (PORTS ? (p.ttl & 0xffu) == 0 : p.ttl == 0) {
                 hs.ttl_drops++;
-                trace_ip_drop(M, E, out, Pkt{p.app, p.ipid, p.size, 1u});
+                trace_ip_drop(M, E, out, Pkt{p.app, p.ipid, p.size, PORTS ? p.ttl + 1u : 1u});
               } else {
                 h.op = ACT_SEND;
                 h.dev = out;
@@ -1696,7 +1685,7 @@ __device__ __forceinline__ void hub_help(const P2PDev &M, Ctl &C, uint32_t i0, u
 // other node parts serially in key order; (3) the device steps and trailing children serially in key
 // order, the device state in registers.  Node parts never read device state and device steps never
 // read node state (node_part), so this is the sequential order's result.
-template <bool WIDE, bool DF = false>
+template <bool WIDE, bool DF = false, bool PORTS = false>
 __device__ __forceinline__ void hub_node(const P2PDev &M, Ctl &C, uint32_t c, uint32_t W, uint32_t base, bool sorted, Red &R,
                          uint32_t hb, uint32_t *lds, const HCtl &hc, uint32_t *lcnt_sh, bool helped, bool first = true) {
   const int lane = threadIdx.x;
@@ -1837,7 +1826,7 @@ __device__ __forceinline__ void hub_node(const P2PDev &M, Ctl &C, uint32_t c, ui
           E.uid = (uint32_t)key, E.tloc = false;
           E.trseq = 0;
           E.demote = rel == slo || rel == shi;
-          const NodeOut o = node_part(M, E, kw, a, pk, sink, hs, true);
+          const NodeOut o = node_part<PORTS>(M, E, kw, a, pk, sink, hs, true);
           uint32_t ni = 0;
           for (uint32_t jj = 0; jj < E.n; jj++) ni += (M.ch_kind[E.slot0 + jj] & 0xffu) == K_FWD_UP;
           M.hx[s] = HubEv{o.act.op, o.act.dev, o.act.p, o.post.delay, o.post.valid ? o.post.kind : 0u, o.post.a, E.n,
@@ -1935,9 +1924,9 @@ __device__ __forceinline__ void hub_node(const P2PDev &M, Ctl &C, uint32_t c, ui
               trace_ip_drop(M, E, a, p);
             } else {
               p.ttl -= 1;
-              if (p.ttl == 0) {  // (ICMP off: stateless_event)
+              if (PORTS ? (p.ttl & 0xffu) == 0 : p.ttl == 0) {  // (ICMP off: stateless_event)
                 hs.ttl_drops++;
-                trace_ip_drop(M, E, out, Pkt{p.app, p.ipid, p.size, 1u});
+                trace_ip_drop(M, E, out, Pkt{p.app, p.ipid, p.size, PORTS ? p.ttl + 1u : 1u});
               } else {
                 h.op = ACT_SEND;
                 h.dev = out;
@@ -1980,7 +1969,7 @@ __device__ __forceinline__ void hub_node(const P2PDev &M, Ctl &C, uint32_t c, ui
             E.uid = (uint32_t)c_key[q], E.tloc = false;
             E.trseq = 0;
             E.demote = rel == slo || rel == shi;
-            const NodeOut o = node_part(M, E, c_kind[q], c_a[q], c_pkt[q], sink, hs, true);
+            const NodeOut o = node_part<PORTS>(M, E, c_kind[q], c_a[q], c_pkt[q], sink, hs, true);
             uint32_t ni = 0;
             for (uint32_t jj = 0; jj < E.n; jj++) ni += (M.ch_kind[E.slot0 + jj] & 0xffu) == K_FWD_UP;
             M.hx[s] = HubEv{o.act.op, o.act.dev, o.act.p, o.post.delay, o.post.valid ? o.post.kind : 0u, o.post.a, E.n,
@@ -2059,11 +2048,7 @@ __device__ __forceinline__ void hub_node(const P2PDev &M, Ctl &C, uint32_t c, ui
         for (uint32_t jj = 0; jj < ncr; jj++) {
           const uint32_t sl = xr * M.maxc + jj;
           if ((M.ch_kind[sl] & 0xffu) != K_FWD_UP) continue;
-          const uint32_t sa = M.ch_a[sl];
-          if (M.app_flags[sa] & 2u) {
-            M.appc[sa].rx_packets++;
-            M.appc[sa].rx_bytes += M.ch_pkt[sl].size - 28;
-          }
+          fwd_up_leaf<PORTS>(M, M.ch_a[sl], &M.ch_pkt[sl]);
         }
       }
       pending = 0;
@@ -2207,6 +2192,9 @@ __device__ __forceinline__ void maintain(const P2PDev &M, Ctl &C, uint32_t mb, b
 }
 
 // WIDE: the single engine's wide windows (local records: k2_rank places them after the handlers).
+// NSGPU_P2P_HANDLERS_ONLY (nsgpu_p2p_ports.hip): that translation unit compiles this header for k2_handle alone — the
+// non-template kernels (this one and everything after k2_handle) stay nsgpu_p2p.hip's, defined once.
+#ifndef NSGPU_P2P_HANDLERS_ONLY
 // Partitioned wide windows, after k2_handle: region bx's local records (its count in lcnt) into this rank's X1Loc
 // list, compacted in region order (each block's offset: the prefix of the region counts, all loaded in one trip —
 // no allocation atomic).  (Inside k2_handle this code made the kernel spill 1.3 KB of scratch a lane.)
@@ -2269,12 +2257,15 @@ __global__ __launch_bounds__(HB) void k_xlcompact(const P2PDev M) {
   lts = wave_max64(lts);
   if (tid == 0 && lts) atomicMax((unsigned long long *)&x1hdr(M.x1_send, 0)->lastkey, (unsigned long long)lts);
 }
+#endif  // NSGPU_P2P_HANDLERS_ONLY
 
 // XL: the partitioned wide engine's variant (k_gtile's accumulators zeroed; every region count written, for
 // k_xlcompact): a separate instantiation, so that the single engine's kernel has none of that code.
 // DF: the deferred pipeline's variant (single wide engine): the holder and hub blocks publish per-block partial
 // records (Part) instead of atomics on the run control.
-template <bool WIDE, bool XL = false, bool DF = false>
+// PORTS: the engine's scenario has UDP ports (nsgpu_p2p_dev.h "UDP ports"): the node parts with the per-flow endpoint
+// lookup, UdpClient and UdpServer; an engine without ports launches the instantiation without them.
+template <bool WIDE, bool XL = false, bool DF = false, bool PORTS = false>
 __global__ __launch_bounds__(HB) void k2_handle(const P2PDev M) {
   static_assert(!DF || (WIDE && !XL), "deferred windows are the single wide engine's");
   __shared__ uint64_t lds64[(WIDE ? K2_LDS_WORDS_W : K2_LDS_WORDS) / 2];
@@ -2357,15 +2348,15 @@ __global__ __launch_bounds__(HB) void k2_handle(const P2PDev M) {
   const bool helped = !WIDE && c_nhub != 0;  // (a window with hubs: the holder blocks help the hub blocks first)
   if (bx < (uint32_t)NHB) {
     if (handle) {
-      if (helped) hub_help(M, C, bx * HB + threadIdx.x, W, base, hc, sp);
-      handle_node2<WIDE, DF>(M, C, bx * HB + threadIdx.x, W, base, R, lds, hc, sp, &s_lcnt);
+      if (helped) hub_help<PORTS>(M, C, bx * HB + threadIdx.x, W, base, hc, sp);
+      handle_node2<WIDE, DF, PORTS>(M, C, bx * HB + threadIdx.x, W, base, R, lds, hc, sp, &s_lcnt);
     }
   } else if (bx < (uint32_t)(NHB + NHUB)) {
     if (handle) {
       const uint32_t hb = bx - NHB;
       const uint32_t nh = c_nhub < (uint32_t)MAXHUB ? c_nhub : (uint32_t)MAXHUB;
       for (uint32_t h = hb; h < nh; h += NHUB)
-        hub_node<WIDE, DF>(M, C, M.hub_list[h], W, base, run || c_drun != 0, R, hb, lds, hc, &s_lcnt, helped, h == hb);
+        hub_node<WIDE, DF, PORTS>(M, C, M.hub_list[h], W, base, run || c_drun != 0, R, hb, lds, hc, &s_lcnt, helped, h == hb);
     }
   } else if (bx < (uint32_t)K2_GRID_W) {
     if constexpr (XL) {  // k_gtile's accumulators for this window (k_dfin2 read the last window's: local
@@ -2386,6 +2377,8 @@ __global__ __launch_bounds__(HB) void k2_handle(const P2PDev M) {
   BLK_REC(1, c_win);
 }
 
+// (everything below is the rest of the window pipeline: not compiled into the handlers-only translation unit)
+#ifndef NSGPU_P2P_HANDLERS_ONLY
 // The local regions' prefix (NLR + 1 entries) into LDS from each thread's region count v (M.lcnt[thread],
 // 0 past NLR); every thread of the block calls it.
 template <int NT>
@@ -3774,3 +3767,4 @@ __global__ void k_part_clear(Ctl *C) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < (uint32_t)NPARTS) *part_rec(C, i) = Part{~0ull, ~0ull, ~0ull, 0};
 }
+#endif  // NSGPU_P2P_HANDLERS_ONLY

@@ -288,6 +288,13 @@ bool record_ok(const nsgpu_trace_codec &c, const nsgpu_trace_record &r) {
   return r.size >= (l3_record(r.kind) ? 0 : PPP) && ip_len >= 28u;
 }
 
+// A record of a UdpClient's flow: its payload starts with a SeqTsHeader (sequence number, send time) whose bytes
+// and Packet::Print wording no test here pins, so the codec refuses it instead of writing zeros.
+bool seqts_record(const nsgpu_trace_codec &c, const nsgpu_trace_record &r) {
+  return c.app_kind[r.app & NSGPU_PKT_APP] == NSGPU_APP_UDP_CLIENT;
+}
+const char *const kSeqTs = "a UdpClient datagram: the codec does not write SeqTsHeader payloads";
+
 // PcapFile::Init (pcap-file.cc:300-346): magic, version 2.4, thiszone 0, sigfigs 0, snaplen, network
 // (native little-endian, no swap)
 void pcap_header(std::vector<uint8_t> &o, uint32_t linktype, uint32_t snaplen) {
@@ -359,7 +366,8 @@ int nsgpu_trace_codec_create(const nsgpu_p2p_scenario *sc, const nsgpu_trace_add
     if (sc->app_src_slot) c->app_src_slot.assign(sc->app_src_slot, sc->app_src_slot + A);
   }
   for (uint32_t a = 0; a < A; a++)
-    if (c->app_node[a] >= N || ((c->app_kind[a] == NSGPU_APP_ONOFF || c->app_kind[a] == NSGPU_APP_ECHO_CLIENT) &&
+    if (c->app_node[a] >= N || ((c->app_kind[a] == NSGPU_APP_ONOFF || c->app_kind[a] == NSGPU_APP_ECHO_CLIENT ||
+                                  c->app_kind[a] == NSGPU_APP_UDP_CLIENT) &&
                                 c->app_dst[a] >= N)) {
       delete c;
       return set_error(NSGPU_EINVAL, "nsgpu_trace_codec_create: application %u names a node out of range", a);
@@ -378,7 +386,9 @@ int nsgpu_trace_codec_create(const nsgpu_p2p_scenario *sc, const nsgpu_trace_add
   c->eport.assign(A, 0);
   std::vector<std::pair<int64_t, uint32_t>> order;
   for (uint32_t a = 0; a < A; a++)
-    if (c->app_kind[a] == NSGPU_APP_ONOFF || c->app_kind[a] == NSGPU_APP_ECHO_CLIENT) order.push_back({sc->app_start_ns[a], a});
+    if (c->app_kind[a] == NSGPU_APP_ONOFF || c->app_kind[a] == NSGPU_APP_ECHO_CLIENT ||
+        c->app_kind[a] == NSGPU_APP_UDP_CLIENT)  // (a UdpClient's socket takes an ephemeral port like the others)
+      order.push_back({sc->app_start_ns[a], a});
   std::sort(order.begin(), order.end());
   std::vector<uint32_t> port(N, 49152);
   for (const auto &o : order) c->eport[o.second] = ++port[c->app_node[o.second]];
@@ -417,6 +427,7 @@ int nsgpu_trace_sort(nsgpu_trace_record *rec, uint64_t n) {
 int nsgpu_trace_line(const nsgpu_trace_codec *c, const nsgpu_trace_record *r, char *out, uint64_t cap, uint64_t *len) {
   if (!c || !r || !len) return set_error(NSGPU_EINVAL, "nsgpu_trace_line: null");
   if (!record_ok(*c, *r)) return set_error(NSGPU_EINVAL, "nsgpu_trace_line: malformed record");
+  if (seqts_record(*c, *r)) return set_error(NSGPU_EINVAL, "nsgpu_trace_line: the record is %s", kSeqTs);
   std::string o;
   line(*c, *r, o);
   return copy_out(o.data(), o.size(), out, cap, len);
@@ -426,6 +437,7 @@ int nsgpu_trace_packet(const nsgpu_trace_codec *c, const nsgpu_trace_record *r, 
                        uint64_t *len) {
   if (!c || !r || !len) return set_error(NSGPU_EINVAL, "nsgpu_trace_packet: null");
   if (!record_ok(*c, *r)) return set_error(NSGPU_EINVAL, "nsgpu_trace_packet: malformed record");
+  if (seqts_record(*c, *r)) return set_error(NSGPU_EINVAL, "nsgpu_trace_packet: the record is %s", kSeqTs);
   std::vector<uint8_t> o;
   packet_bytes(*c, *r, o);
   return copy_out(o.data(), o.size(), out, cap, len);
@@ -438,6 +450,8 @@ int nsgpu_trace_ascii(const nsgpu_trace_codec *c, const nsgpu_trace_record *rec,
   o.reserve(n * 200);
   for (uint64_t i = 0; i < n; i++) {
     if (!record_ok(*c, rec[i])) return set_error(NSGPU_EINVAL, "nsgpu_trace_ascii: record %llu is malformed", (unsigned long long)i);
+    if (seqts_record(*c, rec[i]))
+      return set_error(NSGPU_EINVAL, "nsgpu_trace_ascii: record %llu is %s", (unsigned long long)i, kSeqTs);
     line(*c, rec[i], o);
   }
   return copy_out(o.data(), o.size(), out, cap, len);
@@ -454,6 +468,8 @@ int nsgpu_trace_pcap(const nsgpu_trace_codec *c, const nsgpu_trace_record *rec, 
     const nsgpu_trace_record &r = rec[i];
     if (r.dev != dev || (r.kind != NSGPU_TR_DEQUEUE && r.kind != NSGPU_TR_RX)) continue;  // the sniffer's calls
     if (!record_ok(*c, r)) return set_error(NSGPU_EINVAL, "nsgpu_trace_pcap: record %llu is malformed", (unsigned long long)i);
+    if (seqts_record(*c, r))
+      return set_error(NSGPU_EINVAL, "nsgpu_trace_pcap: record %llu is %s", (unsigned long long)i, kSeqTs);
     pk.clear();
     packet_bytes(*c, r, pk);
     const uint64_t us = r.ts / 1000;  // (Time::GetMicroSeconds, PcapFileWrapper::Write)

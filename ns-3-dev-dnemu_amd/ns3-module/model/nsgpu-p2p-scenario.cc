@@ -18,6 +18,8 @@
 #include "ns3/packet-sink.h"
 #include "ns3/udp-echo-client.h"
 #include "ns3/udp-echo-server.h"
+#include "ns3/udp-client.h"
+#include "ns3/udp-server.h"
 #include "ns3/inet-socket-address.h"
 #include "ns3/address.h"
 #include "ns3/uinteger.h"
@@ -114,10 +116,44 @@ NsgpuP2pScenario::AddApp (const App &a)
 }
 
 uint32_t
-NsgpuP2pScenario::AddPacketSink (uint32_t node, Time start, Time stop)
+NsgpuP2pScenario::AddPacketSink (uint32_t node, Time start, Time stop, uint16_t port)
 {
-  App a = {NSGPU_APP_SINK, node, 0, 0, 0, 0, start.GetTimeStep (), stop.GetTimeStep (), 0, 0.0, 0.0, 0, 0, 0, 0};
+  App a = {NSGPU_APP_SINK, node, 0, 0, 0, 0, start.GetTimeStep (), stop.GetTimeStep (), 0, 0.0, 0.0, 0, 0, 0, 0,
+           port, 0};
   return AddApp (a);
+}
+
+uint32_t
+NsgpuP2pScenario::AddUdpClient (uint32_t node, uint32_t dstNode, Time start, Time stop, uint32_t maxPackets,
+                                Time interval, uint32_t packetSize, uint32_t ttl, uint16_t remotePort)
+{
+  App a = {NSGPU_APP_UDP_CLIENT, node, dstNode, packetSize, 0, ttl, start.GetTimeStep (), stop.GetTimeStep (), 0, 0.0,
+           0.0, maxPackets, interval.GetTimeStep (), 0, remotePort, 0, 0};
+  return AddApp (a);
+}
+
+uint32_t
+NsgpuP2pScenario::AddUdpServer (uint32_t node, Time start, Time stop, uint16_t port, uint16_t packetWindowSize)
+{
+  App a = {NSGPU_APP_UDP_SERVER, node, 0, 0, 0, 0, start.GetTimeStep (), stop.GetTimeStep (), 0, 0.0, 0.0, 0, 0, 0, 0,
+           port, packetWindowSize};
+  return AddApp (a);
+}
+
+void
+NsgpuP2pScenario::GetUdpServer (uint32_t app, uint32_t &received, uint32_t &lost) const
+{
+  if (m_engine == 0 || app >= m_app.size () || m_app[app].kind != NSGPU_APP_UDP_SERVER)
+    {
+      NS_FATAL_ERROR ("NsgpuP2pScenario::GetUdpServer: application " << app << " is not a UdpServer of an engine");
+    }
+  std::vector<nsgpu_udp_server_record> rec (m_app.size ());
+  if (nsgpu_p2p_udp_servers (m_engine, &rec[0], 0) != NSGPU_OK)
+    {
+      NS_FATAL_ERROR ("libnsgpu: " << nsgpu_last_error ());
+    }
+  received = rec[app].received;
+  lost = rec[app].lost;
 }
 
 uint32_t
@@ -433,17 +469,50 @@ NsgpuP2pScenario::FromNodeList (Ptr<HipSimulatorImpl> impl)
       else if (DynamicCast<UdpEchoServer> (o) != 0)
         {
           x.kind = NSGPU_APP_ECHO_SERVER;
+          x.port = UintAttribute (o, "Port");
         }
       else if (DynamicCast<PacketSink> (o) != 0)
         {
           x.kind = NSGPU_APP_SINK;
+          AddressValue local;
+          o->GetAttribute ("Local", local);
+          if (!InetSocketAddress::IsMatchingType (local.Get ()) ||
+              InetSocketAddress::ConvertFrom (local.Get ()).GetIpv4 () != Ipv4Address::GetAny ())
+            {
+              NS_FATAL_ERROR ("NsgpuP2pScenario::FromNodeList: PacketSink on node " << n << ": Local is not "
+                              "(Ipv4Address::GetAny (), port): sockets bound to an address are outside the subset");
+            }
+          x.port = InetSocketAddress::ConvertFrom (local.Get ()).GetPort ();
+        }
+      else if (DynamicCast<UdpClient> (o) != 0)
+        {
+          x.kind = NSGPU_APP_UDP_CLIENT;
+          x.size = UintAttribute (o, "PacketSize");
+          x.count = UintAttribute (o, "MaxPackets");
+          x.interval = TimeAttribute (o, "Interval").GetTimeStep ();
+          AddressValue ra;
+          o->GetAttribute ("RemoteAddress", ra);
+          if (!Ipv4Address::IsMatchingType (ra.Get ()))
+            {
+              NS_FATAL_ERROR ("NsgpuP2pScenario::FromNodeList: UdpClient on node " << n << ": RemoteAddress is not "
+                              "an Ipv4Address");
+            }
+          remote = Ipv4Address::ConvertFrom (ra.Get ()).Get ();
+          x.remotePort = UintAttribute (o, "RemotePort");
+        }
+      else if (DynamicCast<UdpServer> (o) != 0)
+        {
+          x.kind = NSGPU_APP_UDP_SERVER;
+          x.port = UintAttribute (o, "Port");
+          x.window = UintAttribute (o, "PacketWindowSize");
         }
       else
         {
           NS_FATAL_ERROR ("NsgpuP2pScenario::FromNodeList: node " << n << " application " << a
-                          << " is not OnOff / PacketSink / UdpEcho (not in the GPU-resident subset)");
+                          << " is not OnOff / PacketSink / UdpEcho / UdpClient / UdpServer (not in the GPU-resident "
+                          "subset)");
         }
-      if (x.kind == NSGPU_APP_ONOFF || x.kind == NSGPU_APP_ECHO_CLIENT)
+      if (x.kind == NSGPU_APP_ONOFF || x.kind == NSGPU_APP_ECHO_CLIENT || x.kind == NSGPU_APP_UDP_CLIENT)
         {
           if (nodeOfAddr.find (remote) == nodeOfAddr.end ())
             {
@@ -463,7 +532,8 @@ NsgpuP2pScenario::PopulateRoutingTables (void)
   m_nDst = 0;
   for (size_t i = 0; i < m_app.size (); i++)
     {
-      if (m_app[i].kind == NSGPU_APP_ONOFF || m_app[i].kind == NSGPU_APP_ECHO_CLIENT)
+      if (m_app[i].kind == NSGPU_APP_ONOFF || m_app[i].kind == NSGPU_APP_ECHO_CLIENT ||
+          m_app[i].kind == NSGPU_APP_UDP_CLIENT)
         {
           m_dstSlot[m_app[i].dst] = 0;  // mark; numbered below in node order
           if (m_icmp || m_app[i].kind == NSGPU_APP_ECHO_CLIENT)
@@ -516,12 +586,14 @@ NsgpuP2pScenario::Fill (void)
   m_cKind.assign (A1, 0), m_cNode.assign (A1, 0), m_cDst.assign (A1, 0), m_cSlot.assign (A1, 0);
   m_cSrc.assign (A1, 0xffffffffu), m_cSize.assign (A1, 0), m_cMaxb.assign (A1, 0), m_cTtl.assign (A1, 0);
   m_cCount.assign (A1, 0), m_cRaddr.assign (A1, 0), m_cRport.assign (A1, 0);
+  m_cPort.assign (A1, 0), m_cWindow.assign (A1, 0);
   m_cStart.assign (A1, 0), m_cStop.assign (A1, 0), m_cIvl.assign (A1, 0), m_cRate.assign (A1, 0);
   m_cOn.assign (A1, 0.0), m_cOff.assign (A1, 0.0);
   for (size_t i = 0; i < A; i++)
     {
       const App &a = m_app[i];
-      const bool sender = a.kind == NSGPU_APP_ONOFF || a.kind == NSGPU_APP_ECHO_CLIENT;
+      const bool sender = a.kind == NSGPU_APP_ONOFF || a.kind == NSGPU_APP_ECHO_CLIENT || a.kind == NSGPU_APP_UDP_CLIENT;
+      m_cPort[i] = a.port, m_cWindow[i] = a.window;
       m_cKind[i] = a.kind, m_cNode[i] = a.node, m_cDst[i] = a.dst, m_cSize[i] = a.size, m_cMaxb[i] = a.maxBytes;
       m_cTtl[i] = a.ttl, m_cCount[i] = a.count, m_cIvl[i] = a.interval, m_cRaddr[i] = a.remoteAddr;
       m_cRport[i] = a.remotePort;
@@ -547,6 +619,8 @@ NsgpuP2pScenario::Fill (void)
   sc.app_dst_node = &m_cDst[0], sc.app_dst_slot = &m_cSlot[0], sc.app_rate_bps = &m_cRate[0];
   sc.app_pkt_size = &m_cSize[0], sc.app_on_s = &m_cOn[0], sc.app_off_s = &m_cOff[0], sc.app_max_bytes = &m_cMaxb[0];
   sc.app_ttl = &m_cTtl[0], sc.app_count = &m_cCount[0], sc.app_interval_ns = &m_cIvl[0], sc.app_src_slot = &m_cSrc[0];
+  // UDP ports, always: a datagram reaches the application bound to its destination port, as in ns-3
+  sc.app_port = &m_cPort[0], sc.app_remote_port = &m_cRport[0], sc.app_loss_window = &m_cWindow[0];
   sc.stop_ns = m_stop;
   sc.icmp = m_icmp ? 1u : 0u;
   sc.n_setup = m_setup.size ();

@@ -45,7 +45,14 @@ public:
   std::pair<uint32_t, uint32_t> Link (uint32_t a, uint32_t b, uint64_t bps, Time delay, uint32_t queueMaxPackets,
                                       Time interframeGap);
   void InstallStack (void);
-  uint32_t AddPacketSink (uint32_t node, Time start, Time stop);
+  uint32_t AddPacketSink (uint32_t node, Time start, Time stop, uint16_t port = 9);
+  /* UdpClientHelper (address of dstNode, remotePort).Install / UdpServerHelper (port).Install; packetSize counts the
+   * 12-byte SeqTsHeader ([12, 1472]), packetWindowSize is a multiple of 8 in [8, 256] */
+  uint32_t AddUdpClient (uint32_t node, uint32_t dstNode, Time start, Time stop, uint32_t maxPackets, Time interval,
+                         uint32_t packetSize, uint32_t ttl, uint16_t remotePort = 100);
+  uint32_t AddUdpServer (uint32_t node, Time start, Time stop, uint16_t port = 100, uint16_t packetWindowSize = 32);
+  /* UdpServer::GetReceived () / GetLost () of application `app` (a UdpServer) as the engine counts them now */
+  void GetUdpServer (uint32_t app, uint32_t &received, uint32_t &lost) const;
   uint32_t AddOnOff (uint32_t node, uint32_t dstNode, Time start, Time stop, uint64_t rateBps, uint32_t packetSize,
                      double onSeconds, double offSeconds, uint32_t maxBytes, uint32_t ttl);
   void Stop (Time at);
@@ -66,12 +73,14 @@ public:
    * PACKETS mode: MaxPackets), its PointToPointChannel's Delay and peer; the LoopbackNetDevice — its Ipv4
    * interfaces (address, interface index), DefaultTtl, and its applications in Node::AddApplication order
    * (OnOffApplication DataRate / PacketSize / Remote / OnTime / OffTime (ConstantVariable) / MaxBytes,
-   * PacketSink, UdpEchoServer Port, UdpEchoClient RemoteAddress / RemotePort / MaxPackets / Interval /
-   * PacketSize; StartTime / StopTime).  The setup list follows `impl`'s journal: per node, its first
+   * PacketSink Local (Any, port), UdpEchoServer Port, UdpEchoClient RemoteAddress / RemotePort / MaxPackets /
+   * Interval / PacketSize, UdpClient RemoteAddress / RemotePort / MaxPackets / Interval / PacketSize, UdpServer Port /
+   * PacketWindowSize; StartTime / StopTime).  The UDP ports are always given to the engine: a datagram reaches the
+   * application bound to its destination port, a node may host several bound applications on distinct ports.  The setup list follows `impl`'s journal: per node, its first
    * zero-delay call is Node::Start, the next ones its devices' NetDevice::Start then its applications'
    * Application::Start (the helpers add devices before applications); the Stop event; every other call
    * keeps its uid on the host (NSGPU_SETUP_UID).  Anything outside the GPU-resident subset (another device
-   * type, a random OnTime, a sink on a second port of a node, ...) is a fatal error. */
+   * type, a random OnTime, two applications bound to one port of a node, ...) is a fatal error. */
   void FromNodeList (Ptr<HipSimulatorImpl> impl);
   /* The journal entries the engine dispatches from now on (FromNodeList) */
   const std::vector<uint32_t> &GetOwnedSetupCalls (void) const { return m_owned; }
@@ -105,6 +114,8 @@ private:
     int64_t interval;      // UdpEchoClient Interval
     uint32_t remoteAddr;   // the sender's Remote address (0: its destination's first interface)
     uint32_t remotePort;
+    uint32_t port;         // bound port of a PacketSink / UdpEchoServer / UdpServer
+    uint32_t window;       // UdpServer PacketWindowSize
   };
   uint32_t AddApp (const App &a);
   /* the engine's view (kept alive for the trace codec) */
@@ -129,7 +140,7 @@ private:
   // the C view (Fill)
   nsgpu_p2p_scenario m_sc;
   std::vector<uint32_t> m_cDevNode, m_cDevPeer, m_cDevQmax, m_cKind, m_cNode, m_cDst, m_cSlot, m_cSrc, m_cSize,
-    m_cMaxb, m_cTtl, m_cCount, m_cSk, m_cSi, m_cRaddr, m_cRport;
+    m_cMaxb, m_cTtl, m_cCount, m_cSk, m_cSi, m_cRaddr, m_cRport, m_cPort, m_cWindow;
   std::vector<uint64_t> m_cDevBps, m_cRate;
   std::vector<int64_t> m_cDevIfg, m_cDevDelay, m_cStart, m_cStop, m_cIvl;
   std::vector<double> m_cOn, m_cOff;

@@ -26,7 +26,9 @@ TRACE_RECORD_DTYPE = np.dtype([("ts", "<u8"), ("uid", "<u4"), ("seq", "<u2"), ("
                                ("ttl", "<u4"), ("pad2_", "<u4")])
 
 APP_ONOFF, APP_SINK, APP_ECHO_CLIENT, APP_ECHO_SERVER = 0, 1, 2, 3
-SENDERS = (APP_ONOFF, APP_ECHO_CLIENT)  # applications that originate datagrams towards app["dst"]
+APP_UDP_CLIENT, APP_UDP_SERVER = 4, 5  # (Scenario (ports=True) only)
+SENDERS = (APP_ONOFF, APP_ECHO_CLIENT, APP_UDP_CLIENT)  # applications that originate datagrams towards app["dst"]
+BOUND = (APP_SINK, APP_ECHO_SERVER, APP_UDP_SERVER)  # applications whose socket is bound to (Any, app["port"])
 SETUP_NODE, SETUP_DEVICE, SETUP_APP, SETUP_STOP, SETUP_UID, SETUP_NOOP = 0, 1, 2, 3, 4, 5
 NO_ROUTE = 0xFFFFFFFF
 
@@ -45,6 +47,7 @@ class ScenarioStruct(C.Structure):
         ("app_count", C.c_void_p), ("app_interval_ns", C.c_void_p), ("app_src_slot", C.c_void_p),
         ("route_default", C.c_void_p), ("route_exc_off", C.c_void_p), ("route_exc_slot", C.c_void_p),
         ("route_exc_dev", C.c_void_p), ("uid_first", C.c_uint32), ("pad_uid_", C.c_uint32),
+        ("app_port", C.c_void_p), ("app_remote_port", C.c_void_p), ("app_loss_window", C.c_void_p),
     ]
 
 
@@ -60,13 +63,19 @@ DEV_COUNTERS_DTYPE = np.dtype([("enq_packets", "<u4"), ("enq_bytes", "<u4"), ("d
                                ("rx_packets", "<u4"), ("pad_", "<u4")])
 APP_COUNTERS_DTYPE = np.dtype([("tx_packets", "<u4"), ("rx_packets", "<u4"), ("tx_bytes", "<u8"),
                                ("rx_bytes", "<u8")])
+# nsgpu_udp_server_record: UdpServer::GetReceived / GetLost, the loss counter's m_lastMaxSeqNum
+UDP_SERVER_DTYPE = np.dtype([("received", "<u4"), ("lost", "<u4"), ("last_max_seq", "<u4"), ("pad_", "<u4")])
 
 
 class Scenario:
     """Arrays of a nsgpu_p2p_scenario plus the order of setup-time Schedule calls."""
 
-    def __init__(self, n_nodes, icmp=False):
+    def __init__(self, n_nodes, icmp=False, ports=False):
         self.icmp = icmp  # ICMP errors generated and routed back to senders (nsgpu_p2p_scenario.icmp)
+        # UDP ports on the device (nsgpu_p2p_scenario.app_port): a datagram reaches the application of its
+        # destination node bound to its remote port; several bound endpoints a node; UdpClient / UdpServer.
+        # False: the port fields are for the trace codec only and a node has one bound endpoint.
+        self.ports = ports
         self.uid_first = 0  # m_uid before the first setup call (0: 4, DefaultSimulatorImpl's start)
         self.n_nodes = 0
         self.dev = []     # (node, peer, bps, ifg, delay, qmax)
@@ -77,7 +86,7 @@ class Scenario:
         self.route_c = None  # compressed next hops: (default[n], exc_off[n+1], exc_slot, exc_dev)
         self.n_dst = 0
         self.dst_slot = {}
-        # addressing (host side only: the trace codec prints it, the engines never read it)
+        # addressing (host side only: the trace codec prints it; of it the engines read the ports, with ports=True)
         self.dev_addr = {}   # device -> IPv4 address (u32) of its interface
         self.dev_mask = {}   # device -> network mask (u32)
         self.dev_ifindex = {}  # device -> Ipv4 interface index (loopback 0, then Assign order per node)
@@ -113,7 +122,7 @@ class Scenario:
 
     def _app(self, **kw):
         a = dict(dst=0, rate=0, size=0, on=0.0, off=0.0, maxb=0, ttl=64, count=0, interval=0, port=0,
-                 remote_addr=None, remote_port=0)
+                 remote_addr=None, remote_port=0, window=0)
         a.update(kw)
         self.apps.append(a)
         self.setup.append((SETUP_APP, len(self.apps) - 1))  # Node::AddApplication
@@ -135,6 +144,17 @@ class Scenario:
         return self._app(kind=APP_ECHO_CLIENT, node=node, start=start_ns, stop=stop_ns, dst=dst, size=size,
                          count=count, interval=interval_ns, ttl=ttl, remote_addr=remote_addr,
                          remote_port=remote_port)
+
+    # UdpClientHelper (address, port).Install: MaxPackets, Interval, PacketSize (the 12-byte SeqTsHeader included)
+    def add_udp_client(self, node, dst, start_ns, stop_ns, count=100, interval_ns=10**9, size=1024, ttl=64,
+                       remote_addr=None, remote_port=100):
+        return self._app(kind=APP_UDP_CLIENT, node=node, start=start_ns, stop=stop_ns, dst=dst, size=size,
+                         count=count, interval=interval_ns, ttl=ttl, remote_addr=remote_addr,
+                         remote_port=remote_port)
+
+    def add_udp_server(self, node, start_ns, stop_ns, port=100, window=32):  # UdpServerHelper (port).Install
+        return self._app(kind=APP_UDP_SERVER, node=node, start=start_ns, stop=stop_ns, port=port, ttl=0,
+                         window=window)
 
     # Ipv4AddressHelper::Assign on the two devices of a link, then NewNetwork (ipv4-address-helper.cc)
     def assign_link(self, da, db, network, mask=0xFFFFFF00):
@@ -258,6 +278,10 @@ class Scenario:
             setup_kind=np.array([k for k, _ in self.setup], np.uint32),
             setup_index=np.array([i for _, i in self.setup], np.uint32),
         )
+        if self.ports:
+            arrays.update(app_port=np.array([a["port"] for a in A], np.uint32),
+                          app_remote_port=np.array([a["remote_port"] for a in A], np.uint32),
+                          app_loss_window=np.array([a["window"] for a in A], np.uint32))
         if self.route is None:
             dflt, off, es, ed = self.route_c
             arrays.update(route_default=np.ascontiguousarray(dflt, np.uint32),
@@ -268,6 +292,9 @@ class Scenario:
         s.n_nodes, s.n_devices, s.n_apps, s.n_dst = self.n_nodes, len(self.dev), len(A), self.n_dst
         for k, v in arrays.items():
             setattr(s, k, v.ctypes.data if v.size else None)
+        if self.ports and not A:  # (ports mode is the array's presence)
+            arrays["app_port"] = np.zeros(1, np.uint32)
+            s.app_port = s.app_remote_port = arrays["app_port"].ctypes.data
         s.stop_ns = self.stop_ns
         s.n_setup = len(self.setup)
         s.icmp = 1 if self.icmp else 0
@@ -571,6 +598,12 @@ class Engine:
         nsgpu.check(nsgpu.lib().nsgpu_p2p_counters(self.h, devc.ctypes.data, appc.ctypes.data, self.stream))
         return devc, appc
 
+    def udp_servers(self):
+        """UdpServer received / lost / last_max_seq per application (nsgpu_p2p_udp_servers; zeros for other kinds)."""
+        out = np.zeros(self.s.n_apps, UDP_SERVER_DTYPE)
+        nsgpu.check(nsgpu.lib().nsgpu_p2p_udp_servers(self.h, out.ctypes.data, self.stream))
+        return out
+
     def results(self, log_n=0):
         st = P2PStats()
         devc = np.zeros(self.s.n_devices, DEV_COUNTERS_DTYPE)
@@ -775,6 +808,16 @@ class LoopbackGroup:
     def results(self, log_n=0):
         per = [m.results(log_n) for m in self.members]
         return merge_results(per, self.owner, self.members[0].s)
+
+    def udp_servers(self):
+        """Every application's UdpServer record from the rank owning its node (merge_results' rule)."""
+        per = [m.udp_servers() for m in self.members]
+        app_node = self.members[0].s._keep["app_node"]
+        out = per[0].copy()
+        for r, rec in enumerate(per):
+            m = self.owner[app_node] == r
+            out[m] = rec[m]
+        return out
 
     def run(self, log_n=0):
         self.reset()
