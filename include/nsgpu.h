@@ -586,6 +586,13 @@ int nsgpu_p2p_get_wide(nsgpu_p2p *h, int *wide);
  * m_lastMaxSeqNum of every application, n_apps records (zeros for every other kind; a partitioned engine returns
  * its own nodes' servers: the owner's values count). */
 int nsgpu_p2p_udp_servers(nsgpu_p2p *h, nsgpu_udp_server_record *out, void *stream);
+/* IPv4 fragmentation (nsgpu_p2p_scenario.frag): the run's counters — datagrams fragmented, fragments sent,
+ * datagrams reassembled, reassembly timeouts that fired, timers dispatched after they were cancelled, the longest
+ * reassembly list (zeros without frag).  A partitioned engine reports its own nodes: a run's totals are the
+ * ranks' sums, max_list the largest.  A run whose list would pass 128 entries fails (error code 4096).  A frag
+ * engine cannot join a host-closure runtime (nsgpu_p2p_setup_uid, and with it nsgpu_sim_attach_p2p / _adopt_p2p,
+ * return NSGPU_ESTATE). */
+int nsgpu_p2p_frag_stats(nsgpu_p2p *h, nsgpu_frag_stats *out, void *stream);
 /* PacketLossCounter (packet-loss-counter.cc:32-120) on its own: a fresh counter of `window` bits (a multiple of 8
  * in [8, 256]) is notified of seq[0 .. n) in order, lost[k] = GetLost () after seq[k].  on_device = 0: on the host;
  * 1: the same function in a one-thread kernel on `stream` (the function the engine's handlers call). */
@@ -627,7 +634,8 @@ int nsgpu_probe_latency(void *stream, double *boundary_us, double *trip_us);
  * dispatch count in and out; *ended = 1 when the run is over (Simulator::Stop reached, or nothing
  * pending on the device and no host key).  inject_send: while paused, application `app` (an OnOff
  * flow) sends one datagram at `now` on behalf of the host closure with uid cur_uid and context cur_ctx
- * (its Schedule calls inherit the context; its trace calls continue from *trace_seq).  counters: the device / application counters at this point. */
+ * (its Schedule calls inherit the context; its trace calls continue from *trace_seq; one packet: NSGPU_ESTATE on an
+ * engine whose scenario has frag).  counters: the device / application counters at this point. */
 int nsgpu_p2p_setup_uid(nsgpu_p2p *h, uint32_t *uid);
 int nsgpu_p2p_advance(nsgpu_p2p *h, uint64_t hts, uint32_t huid, uint32_t *uid, uint64_t *dispatched, int *ended,
                       void *stream);

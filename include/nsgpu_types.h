@@ -183,7 +183,28 @@ typedef struct nsgpu_p2p_scenario {
   const uint32_t *app_port;
   const uint32_t *app_remote_port;
   const uint32_t *app_loss_window;
+  /* ---- IPv4 fragmentation (appended: the fields above keep their offsets) ----
+   * frag == 0: a payload above 1472 bytes is refused (every device has MTU 1500).  frag == 1: SendRealOut ->
+   * DoFragmentation (ipv4-l3-protocol.cc:722-731, 751-761, 1116-1206) and LocalDeliver -> ProcessFragment ->
+   * Fragments, HandleFragmentsTimeout (:849-859, 1208-1412) are modelled: OnOff and UdpEchoClient payloads up to
+   * 65507 bytes (MAX_IPV4_UDP_DATAGRAM_SIZE, udp-socket-impl.cc:45), UdpClient PacketSize in [12, 1500].  At most
+   * one fragmenting flow may deliver fragments to a node (flows with payload above 1472 addressed to it, plus each
+   * such UdpEchoClient on it: the reply's fragments return there); DESIGN.md §6 says why.
+   *   frag_timeout_ns   Ipv4L3Protocol::FragmentExpirationTimeout; 0: the reference's default, Seconds (30) */
+  uint32_t frag;
+  uint32_t pad_frag_;
+  int64_t frag_timeout_ns;
 } nsgpu_p2p_scenario;
+
+/* What nsgpu_p2p_frag_stats returns (zeros for a scenario without frag). */
+typedef struct nsgpu_frag_stats {
+  uint64_t fragmented;         /* datagrams DoFragmentation split */
+  uint64_t fragments_sent;     /* the fragments it made (each handed to its device: enqueued or dropped) */
+  uint64_t reassembled;        /* datagrams ProcessFragment completed */
+  uint64_t timeouts;           /* HandleFragmentsTimeout calls (timers that fired) */
+  uint64_t cancelled_timers;   /* timers dispatched after their datagram was entire */
+  uint64_t max_list;           /* the longest Fragments::m_fragments seen on any node */
+} nsgpu_frag_stats;
 
 /* PacketLossCounter (packet-loss-counter.cc:32-120) of one UdpServer, with the server's m_received: the
  * state nsgpu_loss_counter_notify (csrc/nsgpu_loss_counter.h) advances, on the host and on the device. */
@@ -217,6 +238,14 @@ typedef struct nsgpu_udp_server_record {
 #define NSGPU_PKT_ICMP_UNREACH 0x20000000u
 #define NSGPU_PKT_ICMP_OF_REPLY 0x10000000u
 #define NSGPU_PKT_APP 0x0fffffffu
+/* A fragment of a UDP datagram (frag scenarios) carries its IPv4 fragment fields in the upper half of ipid, above
+ * the 16-bit identification: ipid = id | offset (13 bits, 8-byte units) << 16 | MF << 29.  size stays the
+ * fragment's plain IPv4 length (the device step computes txTime from it) and the ttl word is the datagram's in
+ * every fragment (a UdpClient's sequence number included).  In a frag scenario every sender writes id & 0xffff, so
+ * a UDP descriptor is a fragment exactly when ipid >> 16 != 0 (an ICMP descriptor packs two ids there, above). */
+#define NSGPU_PKT_FRAG_SHIFT 16
+#define NSGPU_PKT_FRAG_OFF_MASK 0x1fffu
+#define NSGPU_PKT_FRAG_MF 0x20000000u
 
 /* ---------------- trace records (ascii / pcap replay) ----------------
  * One record per call of a default ascii trace sink of PointToPointHelper::EnableAsciiInternal

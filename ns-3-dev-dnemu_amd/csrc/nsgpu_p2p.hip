@@ -90,6 +90,11 @@ struct nsgpu_p2p {
   const DevRec *dev_init = nullptr;  // device records after reset (tx state idle)
   const nsgpu_loss_counter *loss_init = nullptr;  // ports mode: the UdpServers' loss counters after reset
   uint32_t n_apps = 0;
+  // frag mode: the reset image of what lies behind node_ipid up to the FragNodes (device), its words, the whole
+  // allocation's bytes, the FragNodes
+  const uint32_t *frag_init = nullptr;
+  size_t frag_words = 0, frag_bytes = 0;
+  uint32_t frag_nf = 0;
   // partitioned run
   nsgpu_comm *comm = nullptr;  // RCCL transport (null: a loopback group member)
   X1Hdr x1h0{};                // empty X1 summary (reset template)
@@ -156,6 +161,9 @@ struct EnginePlan {
   std::vector<int32_t> ep_of_flow;  // ports mode: the application a sender's datagrams are delivered to (-1: none)
   int64_t tx_min = 0, lx = 0, send_ivl = 0;
   int64_t lookahead[K_NKINDS], lookw[K_NKINDS];
+  bool frag = false;                 // frag mode (nsgpu_p2p_scenario.frag)
+  std::vector<uint32_t> frag_flows;  // frag mode: the fragmenting flows that deliver fragments to each node
+  int64_t frag_timeout = 0;          // FragmentExpirationTimeout
   // the setup-time events (this rank's, partitioned) and the bound of window 0 (the whole setup: every rank)
   std::vector<uint64_t> its;
   std::vector<uint32_t> iuid, ictx, ikind, ia;
@@ -211,6 +219,11 @@ static int plan_engine(const nsgpu_p2p_scenario *sc, const uint32_t *owner, int 
   napps.assign(N + 1, 0);
   sink.assign(N, -1);
   uint32_t min_pkt = 0xffffffffu;
+  uint32_t min_frag_wire = 0xffffffffu;  // frag: the smallest last fragment's frame (PPP included)
+  const bool frag = sc->frag != 0;
+  P.frag = frag;
+  if (frag && sc->frag_timeout_ns < 0) return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: negative frag_timeout_ns");
+  P.frag_flows.assign(N, 0);
   bool &has_echo = P.has_echo;
   has_echo = false;
   int64_t echo_ivl = (int64_t)1 << 61;
@@ -233,9 +246,14 @@ static int plan_engine(const nsgpu_p2p_scenario *sc, const uint32_t *owner, int 
           sc->app_interval_ns[a] < 0 ||
           (sc->app_src_slot && sc->app_src_slot[a] != 0xffffffffu && sc->app_src_slot[a] >= sc->n_dst))
         return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: UdpClient %u: bad destination/ttl/interval/source slot", a);
-      if (sc->app_pkt_size[a] < 12 || sc->app_pkt_size[a] > 1472)
-        return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: UdpClient %u: PacketSize %u outside [12, 1472]", a,
-                         sc->app_pkt_size[a]);
+      if (sc->app_pkt_size[a] < 12 || sc->app_pkt_size[a] > 1472) {
+        if (!frag)
+          return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: UdpClient %u: PacketSize %u outside [12, 1472]", a,
+                           sc->app_pkt_size[a]);
+        if (sc->app_pkt_size[a] < 12 || sc->app_pkt_size[a] > 1500)  // (udp-client.cc:70: the attribute's checker)
+          return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: UdpClient %u: PacketSize %u outside [12, 1500]", a,
+                           sc->app_pkt_size[a]);
+      }
       if (sc->app_count[a] > (1u << 24))  // (the descriptor carries the sequence number in 24 bits)
         return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: UdpClient %u: MaxPackets %u above 2^24", a, sc->app_count[a]);
       min_pkt = std::min(min_pkt, sc->app_pkt_size[a]);
@@ -270,9 +288,24 @@ static int plan_engine(const nsgpu_p2p_scenario *sc, const uint32_t *owner, int 
     // SendRealOut fragments a datagram above the device MTU (ipv4-l3-protocol.cc:722-731; PointToPointNetDevice
     // Mtu 1500): not modelled, so payloads are bounded by 1500 - 20 (IPv4) - 8 (UDP)
     if (ak == NSGPU_APP_ECHO_CLIENT || ak == NSGPU_APP_ONOFF) {
-      if (sc->app_pkt_size[a] > 1472)
+      if (sc->app_pkt_size[a] > 1472 && !frag)
         return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: app %u: %u-byte payload needs IPv4 fragmentation", a,
                          sc->app_pkt_size[a]);
+      // frag: up to MAX_IPV4_UDP_DATAGRAM_SIZE (udp-socket-impl.cc:45); above it DoSendTo fails with EMSGSIZE
+      if (sc->app_pkt_size[a] > 65507)
+        return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: app %u: %u-byte payload is above the largest UDP datagram "
+                         "(65507 bytes: EMSGSIZE)", a, sc->app_pkt_size[a]);
+    }
+    if (frag && (ak == NSGPU_APP_ECHO_CLIENT || ak == NSGPU_APP_ONOFF || ak == NSGPU_APP_UDP_CLIENT)) {
+      const uint32_t sz = sc->app_pkt_size[a];
+      if (sz > 1472) {  // a fragmenting flow: its fragments reach its destination, an echo's reply its client's node
+        P.frag_flows[sc->app_dst_node[a]]++;
+        if (ak == NSGPU_APP_ECHO_CLIENT) P.frag_flows[sc->app_node[a]]++;
+        // the smallest frame on a wire: the last fragment (IPv4 length 20 + what 1480-byte parts leave) + PPP
+        // (down to 21 + 2 bytes; the lookaheads below take it)
+        const uint32_t L = sz + 8, tail = L - (L - 1) / FRAG_PART * FRAG_PART;
+        min_frag_wire = std::min(min_frag_wire, 20 + tail + 2);
+      }
     }
     if (A > NSGPU_PKT_APP) return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: more than 2^28 applications");
   }
@@ -315,6 +348,16 @@ static int plan_engine(const nsgpu_p2p_scenario *sc, const uint32_t *owner, int 
     for (uint32_t n = 0; n < N; n++)
       sink[n] = eps[n].empty() ? -1 : (eps[n].size() == 1 && !other[n]) ? (int32_t)eps[n][0] : EP_BY_FLOW;
   }
+  if (frag) {
+    // ProcessFragment's key is always (0, 0) (nsgpu_p2p_dev.h "IPv4 fragmentation"): a node has one reassembly
+    // buffer for all sources.  With one fragmenting flow a node that shows only when loss mixes the flow's own
+    // datagrams, which is modelled; several flows into one node are refused
+    for (uint32_t n = 0; n < N; n++)
+      if (P.frag_flows[n] > 1)
+        return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: node %u receives fragments of %u fragmenting flows (at most "
+                         "one: the reference's nodes have one reassembly buffer for all sources)", n, P.frag_flows[n]);
+    P.frag_timeout = sc->frag_timeout_ns ? sc->frag_timeout_ns : 30000000000ll;  // Seconds (30) (:61-64)
+  }
   uint32_t &maxapps = P.maxapps;
   maxapps = 0;
   for (uint32_t n = 0; n < N; n++) maxapps = std::max(maxapps, napps[n + 1]);
@@ -325,9 +368,11 @@ static int plan_engine(const nsgpu_p2p_scenario *sc, const uint32_t *owner, int 
   // ---- lookahead per event kind: the smallest delay a child of that kind can get ----
   const int64_t INFL = (int64_t)1 << 61;
   int64_t tx_min = INFL;
+  // the smallest frame a sender puts on a wire: payload + UDP, IPv4, PPP headers, or a frag flow's last fragment
+  const uint32_t min_wire = std::min(min_pkt == 0xffffffffu ? min_pkt : min_pkt + 30, min_frag_wire);
   if (min_pkt != 0xffffffffu)
     for (uint32_t d = 0; d < D; d++) {
-      tx_min = std::min(tx_min, seconds_to_ts(static_cast<double>(min_pkt + 30) * 8 / (double)sc->dev_bps[d]));
+      tx_min = std::min(tx_min, seconds_to_ts(static_cast<double>(min_wire) * 8 / (double)sc->dev_bps[d]));
       // an ICMP error is a 56-byte IPv4 packet (+2 PPP)
       if (sc->icmp) tx_min = std::min(tx_min, seconds_to_ts(static_cast<double>(56 + 2) * 8 / (double)sc->dev_bps[d]));
     }
@@ -352,6 +397,13 @@ static int plan_engine(const nsgpu_p2p_scenario *sc, const uint32_t *owner, int 
   // schedules): the window must then end at the delivering Receive's time, so that the DoForwardUp is
   // the next window's first event at that time.
   if (has_echo) P.lookahead[K_RECEIVE] = 0;
+  // frag: a Receive that opens a reassembly buffer schedules the timeout, and a timeout that fires may send an
+  // ICMP error from its node (the class of K_FWD_UP_Q)
+  constexpr int KFT = K_FRAG_TIMEOUT;
+  if (frag) {
+    P.lookahead[K_RECEIVE] = std::min(P.lookahead[K_RECEIVE], P.frag_timeout);
+    P.lookahead[KFT] = tx_min;
+  }
   // Wide windows (nsgpu_p2p_win.h): an event on another node is at least one transmission
   // plus its channel delay away — Lx = min over devices of (smallest frame's tx time + delay) — and a
   // same-node TransmitComplete before the window's end runs inside the window (a local record), so only
@@ -359,7 +411,7 @@ static int plan_engine(const nsgpu_p2p_scenario *sc, const uint32_t *owner, int 
   int64_t lx = INFL;
   if (min_pkt != 0xffffffffu)
     for (uint32_t d = 0; d < D; d++) {
-      int64_t t = seconds_to_ts(static_cast<double>(min_pkt + 30) * 8 / (double)sc->dev_bps[d]);
+      int64_t t = seconds_to_ts(static_cast<double>(min_wire) * 8 / (double)sc->dev_bps[d]);
       if (sc->icmp) t = std::min(t, seconds_to_ts(static_cast<double>(56 + 2) * 8 / (double)sc->dev_bps[d]));
       lx = std::min(lx, t + sc->dev_delay_ns[d]);
     }
@@ -368,6 +420,10 @@ static int plan_engine(const nsgpu_p2p_scenario *sc, const uint32_t *owner, int 
   P.lookw[K_TX_COMPLETE] = lx;
   P.lookw[K_RECEIVE] = has_echo ? 0 : lx;
   P.lookw[K_FWD_UP_Q] = lx;
+  if (frag) {
+    P.lookw[K_RECEIVE] = std::min(P.lookw[K_RECEIVE], P.frag_timeout);
+    P.lookw[KFT] = lx;
+  }
   {  // a node's pending local records are its busy devices' TransmitCompletes: at most its degree
     std::vector<uint32_t> deg(N, 0);
     uint32_t dmax = 0;
@@ -562,7 +618,23 @@ static int create_engine(const nsgpu_p2p_scenario *sc, const uint32_t *owner, in
   TRY(dalloc(h, &M.app_ss_gen, A));
   TRY(dalloc(h, &M.app_residual, A));
   TRY(dalloc(h, &M.app_tot, A));
-  TRY(dalloc(h, &M.node_ipid, N));
+  if (P.frag) {
+    // behind the identifications: each node's FragNode index, the FragHdr, a FragNode for every node that is the
+    // destination of a fragmenting flow (nsgpu_p2p_dev.h "IPv4 fragmentation"); kept as the reset image too
+    std::vector<uint32_t> img((frag_hdr_off(N) + sizeof(FragHdr)) / 4, 0);
+    uint32_t nf = 0;
+    for (uint32_t n = 0; n < N; n++) img[N + n] = P.frag_flows[n] ? nf++ : NOFRAG;
+    FragHdr fh{P.frag_timeout, nf, 0};
+    memcpy(img.data() + frag_hdr_off(N) / 4, &fh, sizeof(fh));
+    h->frag_words = img.size();
+    h->frag_bytes = img.size() * 4 + (size_t)nf * sizeof(FragNode);
+    h->frag_nf = nf;
+    TRY(dupload(h, &h->frag_init, img.data(), img.size()));
+    TRY(dalloc(h, &M.node_ipid, h->frag_bytes / 4));
+    M.frag = 1;
+  } else {
+    TRY(dalloc(h, &M.node_ipid, N));
+  }
   TRY(dalloc(h, &M.app_last_start, A));
   if (P.ports) {  // (the UdpServers' loss counters lie behind the counters: loss_counters)
     static_assert(sizeof(nsgpu_loss_counter) == 2 * sizeof(nsgpu_app_counters), "loss_counters");
@@ -821,7 +893,12 @@ extern "C" int nsgpu_p2p_reset(nsgpu_p2p *h, void *stream) {
   NSGPU_HIP(hipMemsetAsync(M.app_ss_gen, 0, A * sizeof(uint32_t), s));
   NSGPU_HIP(hipMemsetAsync(M.app_residual, 0, A * sizeof(uint32_t), s));
   NSGPU_HIP(hipMemsetAsync(M.app_tot, 0, A * sizeof(uint32_t), s));
-  NSGPU_HIP(hipMemsetAsync(M.node_ipid, 0, M.n_nodes * sizeof(uint32_t), s));
+  if (M.frag) {  // (the identifications, the FragNode indices and header, empty FragNodes)
+    NSGPU_HIP(hipMemsetAsync(M.node_ipid, 0, h->frag_bytes, s));
+    NSGPU_HIP(hipMemcpyAsync(M.node_ipid, h->frag_init, h->frag_words * 4, hipMemcpyDeviceToDevice, s));
+  } else {
+    NSGPU_HIP(hipMemsetAsync(M.node_ipid, 0, M.n_nodes * sizeof(uint32_t), s));
+  }
   if (M.trace) NSGPU_HIP(hipMemsetAsync(M.trace_n, 0, sizeof(unsigned long long), s));
   NSGPU_HIP(hipMemsetAsync(M.app_last_start, 0, A * sizeof(uint64_t), s));
   NSGPU_HIP(hipMemsetAsync(M.appc, 0, A * sizeof(nsgpu_app_counters), s));
@@ -877,8 +954,9 @@ bool launch_kernel(nsgpu_p2p *h, int k, hipStream_t s, bool df, hipEvent_t ev0 =
       else NSGPU_KLAUNCH((k2_pa<false, false>), dim3(pa_grid_rt<false>(h->M)), dim3(TB), s, ev0, ev1, h->M);
       return true;
     case 1:
-      // (a scenario with ports: the handlers with the endpoint lookup, UdpClient, UdpServer — nsgpu_p2p_ports.hip)
-      if (h->loss_init) launch_handle_ports(h->M, wide, false, df, K2_GRID, s, ev0, ev1);
+      // (a scenario with ports or frag: the extended handlers — the endpoint lookup, UdpClient, UdpServer, IPv4
+      // fragmentation and reassembly — nsgpu_p2p_ports.hip)
+      if (h->loss_init || h->M.frag) launch_handle_ports(h->M, wide, false, df, K2_GRID, s, ev0, ev1);
       else if (df) NSGPU_KLAUNCH((k2_handle<true, false, true>), dim3(K2_GRID), dim3(HB), s, ev0, ev1, h->M);
       else if (wide) NSGPU_KLAUNCH(k2_handle<true>, dim3(K2_GRID), dim3(HB), s, ev0, ev1, h->M);
       else NSGPU_KLAUNCH(k2_handle<false>, dim3(K2_GRID), dim3(HB), s, ev0, ev1, h->M);
@@ -1175,7 +1253,7 @@ static int launch_windows_dist(nsgpu_p2p *h, hipStream_t s, int nwin = NWIN) {
   for (int w = 0; w < nwin && !rc; w++) {
     dist_pa(M, s);
     rc = x_allgather(h, M.x0_send, M.x0_recv, X0B, s);
-    dist_handle(M, s, h->loss_init != nullptr);
+    dist_handle(M, s, h->loss_init != nullptr || M.frag != 0);
     dist_rank(M, s);
     if (!rc) rc = x_allgather(h, M.x1_send, M.x1_recv, X1B, s);
     dist_rank_fin(M, s);
@@ -1264,7 +1342,8 @@ static int engine_error(uint32_t err) {
                                  "records, 64 = window records, 256 = deferred uid resolution (internal), 512 = uids "
                                  "beyond the deferred pipeline's range (internal), 2048 = the uid counter would pass "
                                  "0xfffffffe: DefaultSimulatorImpl's uint32 m_uid wraps there, which the engine does "
-                                 "not replicate)", err);
+                                 "not replicate, 4096 = a node's IPv4 reassembly list would pass 128 fragments, 8192 = a fragment at a node "
+                                 "without reassembly state (internal))", err);
 }
 
 // The replay loop of every driver: replays of a window pipeline on stream s until the run is over (done >= 2 in the
@@ -1428,6 +1507,11 @@ static int read_ctl(nsgpu_p2p *h, uint32_t *err = nullptr) {
 
 extern "C" int nsgpu_p2p_setup_uid(nsgpu_p2p *h, uint32_t *uid) {
   if (!h || !uid) return set_error(NSGPU_EINVAL, "nsgpu_p2p_setup_uid: null");
+  // (nsgpu_sim_attach_p2p / _adopt_p2p start here: a frag engine stays outside mixed host / device runs — a host
+  // closure's send is one packet with the node's whole identification counter, and no test covers the combination)
+  if (h->M.frag)
+    return set_error(NSGPU_ESTATE, "nsgpu_p2p_setup_uid: a scenario with IPv4 fragmentation (frag) cannot be attached "
+                     "to a host-closure runtime");
   *uid = h->C0.uid;
   return NSGPU_OK;
 }
@@ -1489,6 +1573,10 @@ extern "C" int nsgpu_p2p_inject_send(nsgpu_p2p *h, uint32_t app, uint64_t now, u
   if (h->M.dist) return set_error(NSGPU_ESTATE, "nsgpu_p2p_inject_send: single-device engines only");
   if (app >= h->M.n_apps || h->app_kind[app] != NSGPU_APP_ONOFF)
     return set_error(NSGPU_EINVAL, "nsgpu_p2p_inject_send: app %u is not an OnOff flow", app);
+  // (a host closure's send is one packet with the node's whole identification counter: it stays outside frag mode,
+  // whose receivers read the upper half of a descriptor's identification as fragment fields)
+  if (h->M.frag)
+    return set_error(NSGPU_ESTATE, "nsgpu_p2p_inject_send: not available in a scenario with IPv4 fragmentation (frag)");
   hipStream_t s = h->s;
   if (const int rc = join_in(h, (hipStream_t)stream)) return rc;
   if (const int rc = read_ctl(h)) return rc;
@@ -1774,6 +1862,34 @@ extern "C" int nsgpu_p2p_udp_servers(nsgpu_p2p *h, nsgpu_udp_server_record *out,
   return NSGPU_OK;
 }
 
+// The fragmentation counters of a frag scenario (zeros without frag): the senders' from the device records, the
+// receivers' from the nodes' reassembly state.  A partitioned engine reports what its own nodes did (another
+// rank's nodes and devices stay zero here), so a group's totals are the ranks' sums and the largest max_list.
+extern "C" int nsgpu_p2p_frag_stats(nsgpu_p2p *h, nsgpu_frag_stats *out, void *stream) {
+  if (!h || !out) return set_error(NSGPU_EINVAL, "nsgpu_p2p_frag_stats: null");
+  hipStream_t s = (hipStream_t)stream;
+  memset(out, 0, sizeof(*out));
+  const P2PDev &M = h->M;
+  if (!M.frag) return NSGPU_OK;
+  std::vector<uint64_t> dv(2 * (size_t)M.n_devices);
+  std::vector<FragNode> fn(h->frag_nf);
+  if (M.n_devices)
+    NSGPU_HIP(hipMemcpy2DAsync(dv.data(), 16, &M.dev[0].frag_dgrams, sizeof(DevRec), 16, M.n_devices,
+                               hipMemcpyDeviceToHost, s));
+  if (h->frag_nf)
+    NSGPU_HIP(hipMemcpyAsync(fn.data(), frag_nodes(M.node_ipid, M.n_nodes), fn.size() * sizeof(FragNode),
+                             hipMemcpyDeviceToHost, s));
+  NSGPU_HIP(hipStreamSynchronize(s));
+  for (uint32_t d = 0; d < M.n_devices; d++) out->fragmented += dv[2 * d], out->fragments_sent += dv[2 * d + 1];
+  for (const FragNode &f : fn) {
+    out->reassembled += f.reassembled;
+    out->timeouts += f.timeouts;
+    out->cancelled_timers += f.cancelled;
+    out->max_list = std::max<uint64_t>(out->max_list, f.maxlen);
+  }
+  return NSGPU_OK;
+}
+
 extern "C" int nsgpu_p2p_results(nsgpu_p2p *h, nsgpu_p2p_stats *stats, nsgpu_dev_counters *devc,
                                  nsgpu_app_counters *appc, uint64_t *log_ts, uint32_t *log_uid, uint32_t *log_ctx,
                                  uint64_t log_n, uint32_t *error, void *stream) {
@@ -1832,7 +1948,7 @@ static void launch_windows_group(nsgpu_p2p_group *g, hipStream_t s, int nwin = N
   for (int w = 0; w < nwin; w++) {
     for (auto *h : g->m) dist_pa(h->M, s);
     hipLaunchKernelGGL(k_copies, dim3(n * n), dim3(256), 0, s, (const CopyDesc *)g->d_x[0]);
-    for (auto *h : g->m) dist_handle(h->M, s, h->loss_init != nullptr);
+    for (auto *h : g->m) dist_handle(h->M, s, h->loss_init != nullptr || h->M.frag != 0);
     for (auto *h : g->m) dist_rank(h->M, s);
     hipLaunchKernelGGL(k_copies, dim3(n * n), dim3(256), 0, s, (const CopyDesc *)g->d_x[1]);
     for (auto *h : g->m) dist_rank_fin(h->M, s);

@@ -44,7 +44,10 @@ enum EvKind : uint32_t {
   K_FWD_UP = 12,        // Ipv4EndPoint::DoForwardUp -> UdpSocketImpl::ForwardUp -> PacketSink (zero-delay leaf)
   K_FWD_UP_Q = 13,      // DoForwardUp -> UdpEchoServer / UdpEchoClient::HandleRead (queued: it schedules)
   K_FWD_UP_D = 14,      // a PacketSink DoForwardUp queued like any event: its ts group is cut by a run chunk
-  K_NKINDS = 15
+  K_NKINDS = 15,
+  // Ipv4L3Protocol::HandleFragmentsTimeout (gen, never 0); frag scenarios, extended handlers only.  It takes entry 0
+  // of the per-kind tables, which no kind used, so that the tables and with them P2PDev keep their layout
+  K_FRAG_TIMEOUT = 0
 };
 
 constexpr int WCAP = 4096;       // events per window
@@ -99,7 +102,8 @@ struct DevRec {
   int64_t ifg, delay;              // InterframeGap, channel Delay
   uint64_t pad2;
   nsgpu_dev_counters c;            // (copied out strided by nsgpu_p2p_results / _counters)
-  uint64_t pad3[4];
+  uint64_t frag_dgrams, frag_sent;  // frag scenarios: datagrams this device's node fragmented on it, their fragments
+  uint64_t pad3[2];
 };
 static_assert(sizeof(DevRec) == 128 && offsetof(DevRec, c) == 64, "DevRec is one 128-B line");
 
@@ -281,7 +285,7 @@ struct P2PDev {
   uint32_t icmp;                                  // ICMP errors are generated (scenario icmp)
   int64_t lookahead[K_NKINDS];
   int64_t lookw[K_NKINDS];  // wide windows: the smallest delay of a child that does not run in the window
-  uint32_t wide, pad_w;     // wide windows on
+  uint32_t wide, frag;      // wide windows on; IPv4 fragmentation (scenario frag: the extended handlers)
   // model state
   DevRec *dev;  // per-device tx state + transmit parameters (one record per device)
   Pkt *q_buf;
@@ -420,9 +424,9 @@ __device__ __noinline__ void udp_server_rx(nsgpu_loss_counter *lc, nsgpu_app_cou
 }
 // Ipv4EndPoint::DoForwardUp -> UdpSocketImpl::ForwardUp -> the endpoint's receive callback, for the endpoints
 // whose HandleRead schedules nothing (PacketSink, UdpServer): sa = the endpoint's application, *pp the datagram.
-// PORTS: the handler kernels are instantiated for engines without and with ports (k2_handle<.., PORTS>): what ports
-// mode adds to an event — the per-flow endpoint, UdpClient, UdpServer — is compiled into the second set only, so an
-// engine without ports runs the code it ran before ports existed.
+// PORTS: the handler kernels are instantiated twice (k2_handle<.., PORTS>): what ports mode adds to an event — the
+// per-flow endpoint, UdpClient, UdpServer — and what frag mode adds ("IPv4 fragmentation" below) is compiled into the
+// second, extended set only, so an engine with neither runs the code it ran before they existed.
 template <bool PORTS>
 __device__ __forceinline__ void fwd_up_leaf(const P2PDev &M, uint32_t sa, const Pkt *pp) {
   const uint32_t f = M.app_flags[sa];
@@ -433,6 +437,132 @@ __device__ __forceinline__ void fwd_up_leaf(const P2PDev &M, uint32_t sa, const 
   }
   M.appc[sa].rx_packets++;
   M.appc[sa].rx_bytes += pp->size - 28;
+}
+
+// ---------------- IPv4 fragmentation and reassembly (frag scenarios: nsgpu_p2p_scenario.frag) ----------------
+// Every device has MTU 1500 (the subset has no MTU field), so only the originating node fragments: a forwarder
+// never re-fragments, and DoFragmentation's alreadyFragmented branch (ipv4-l3-protocol.cc:1139-1143,1166-1169) is
+// unreachable.  A sender hands the device step the whole datagram (IPv4 length above FRAG_MTU) and the step sends
+// its fragments one by one (send_fragments); a fragment's descriptor carries its offset and MF bit in the upper
+// half of ipid (NSGPU_PKT_FRAG_*, nsgpu_types.h), and in a frag scenario every sender writes the 16-bit
+// identification, so a non-zero upper half of a UDP descriptor's ipid means "fragment".
+// Reassembly restates Ipv4L3Protocol::ProcessFragment and Fragments (:1208-1389).  The map key there is built with
+// `&` where `|` was meant (:1213-1214), so both key words are always 0: a node has ONE buffer and one timer for all
+// sources and identifications, which is what FragNode is.  The state lies behind node_ipid in its allocation
+// (P2PDev takes no further pointer, see hub_slot): [N] the nodes' identifications, [N] each node's FragNode index
+// (NOFRAG: the node is no destination of a fragmenting flow), then the FragHdr and the FragNodes.
+constexpr uint32_t FRAG_MTU = 1500, FRAG_PART = 1480, FRAG_CAP = 128, NOFRAG = 0xffffffffu;
+constexpr uint32_t ERR_FRAG_CAP = 4096u;        // the engine's error bit: a reassembly list would pass FRAG_CAP entries
+constexpr uint32_t ERR_FRAG_STATE = 8192u;      // ... a fragment reached a node create gave no reassembly state (internal)
+constexpr uint32_t XDROP_FRAG = 0x80000000u;    // NodeOut::xdrop: the Drop record is a fragment timeout's
+struct FragEnt {  // one entry of Fragments::m_fragments: (packet, offset); the packet's size, its flow and ttl words
+  uint32_t off, size, app, ttl;
+};
+struct FragNode {
+  uint32_t n, more, gen, live;  // list length, m_moreFragment, the timer's generation, the buffer (and timer) exists
+  Pkt hdr;                      // the first-arrived fragment's header (HandleFragmentsTimeout took it by value)
+  uint32_t iif, pad;            // ... and its input device
+  uint32_t reassembled, timeouts, cancelled, maxlen;  // nsgpu_p2p_frag_stats
+  uint32_t pad2[2];
+  FragEnt e[FRAG_CAP];
+};
+static_assert(sizeof(FragNode) == 64 + 16 * FRAG_CAP, "FragNode");
+struct FragHdr {
+  int64_t timeout;  // Ipv4L3Protocol::FragmentExpirationTimeout
+  uint32_t nf, pad;
+};
+__host__ __device__ __forceinline__ size_t frag_hdr_off(uint32_t n_nodes) {  // bytes behind node_ipid
+  return ((size_t)n_nodes * 8 + 15) / 16 * 16;
+}
+__host__ __device__ __forceinline__ FragHdr *frag_hdr(uint32_t *node_ipid, uint32_t n_nodes) {
+  return reinterpret_cast<FragHdr *>(reinterpret_cast<char *>(node_ipid) + frag_hdr_off(n_nodes));
+}
+__host__ __device__ __forceinline__ FragNode *frag_nodes(uint32_t *node_ipid, uint32_t n_nodes) {
+  return reinterpret_cast<FragNode *>(frag_hdr(node_ipid, n_nodes) + 1);
+}
+struct FragRx {
+  uint32_t flags, gen;  // 1: the buffer is new (Schedule the timer, generation gen); 2: the datagram is entire (p)
+  Pkt p;
+};
+// ProcessFragment for fragment p (PppHeader stripped) that arrived on device iif.  Out of line: the handlers of a
+// scenario without fragments never reach it.
+__device__ __noinline__ FragRx frag_receive(FragNode *F, uint32_t *error, Pkt p, uint32_t iif) {
+  FragRx r{0, 0, p};
+  const uint32_t off = ((p.ipid >> NSGPU_PKT_FRAG_SHIFT) & NSGPU_PKT_FRAG_OFF_MASK) * 8u;
+  const uint32_t more = (p.ipid & NSGPU_PKT_FRAG_MF) ? 1u : 0u, size = p.size - 20u;
+  if (!F->live) {  // m_fragments.find (key) == end: Create<Fragments> (m_moreFragment (0)), Schedule the timeout
+    F->live = 1;
+    F->n = 0;
+    F->more = 0;
+    F->gen = F->gen % 0x3fffffu + 1;  // (1 .. 2^22 - 1: the kind word's top two bits are LOCALBIT / REMOTEBIT)
+    F->hdr = p;
+    F->iif = iif;
+    r.flags = 1;
+    r.gen = F->gen;
+  }
+  // AddFragment (:1268-1289): before the first entry whose offset is greater (equal offsets keep arrival order);
+  // m_moreFragment changes only when the fragment goes to the end
+  uint32_t n = F->n, pos = 0;
+  while (pos < n && !(F->e[pos].off > off)) pos++;
+  if (n >= FRAG_CAP) {  // never truncated silently: the run fails
+    atomicOr(error, ERR_FRAG_CAP);
+    return r;
+  }
+  if (pos == n) F->more = more;
+  for (uint32_t i = n; i > pos; i--) F->e[i] = F->e[i - 1];
+  F->e[pos] = FragEnt{off, size, p.app, p.ttl};
+  F->n = ++n;
+  if (n > F->maxlen) F->maxlen = n;
+  // IsEntire (:1291-1319), its uint16_t arithmetic kept
+  bool ent = !F->more && n > 0;
+  if (ent) {
+    uint16_t last = 0;
+    for (uint32_t i = 0; i < n; i++) {
+      if (last < (uint16_t)F->e[i].off) {
+        ent = false;
+        break;
+      }
+      const uint16_t end = (uint16_t)(F->e[i].size + F->e[i].off);
+      last = last > end ? last : end;
+    }
+  }
+  if (!ent) return r;
+  // GetPacket (:1321-1356): a later entry contributes only what lies beyond lastEndOffset
+  uint32_t total = 0;
+  uint16_t last = 0;
+  for (uint32_t i = 0; i < n; i++) {
+    const uint32_t eo = F->e[i].off & 0xffffu, es = F->e[i].size;
+    if (last > eo) {
+      const uint32_t ns = last - eo;
+      if (es > ns) total += es - ns;
+    } else {
+      total += es;
+    }
+    last = (uint16_t)total;
+  }
+  // m_fragments.erase (key); the timer is cancelled (it is still dispatched, and counted, at its time) and erased.
+  // The datagram goes on with the arrived fragment's IP header and the first entry's UDP header and payload.
+  r.flags |= 2;
+  r.p = Pkt{F->e[0].app, p.ipid & 0xffffu, 20u + total, (p.ttl & 0xffu) | (F->e[0].ttl & ~0xffu)};
+  F->live = 0;
+  F->n = 0;
+  F->reassembled++;
+  return r;
+}
+// Fragments::GetPartialPacket (:1358-1389)'s size: empty unless the first entry is at offset 0, else the contiguous
+// prefix.  (Its CreateFragment (newStart, size - newStart) would assert for an entry that ends before lastEndOffset;
+// fragments of one flow's datagrams, which all have one size, never make one: equal offsets have equal sizes.)
+__device__ __noinline__ uint32_t frag_partial_size(const FragNode *F) {
+  if (F->n == 0 || F->e[0].off > 0) return 0;
+  uint32_t total = 0;
+  uint16_t last = 0;
+  for (uint32_t i = 0; i < F->n; i++) {
+    const uint32_t eo = F->e[i].off & 0xffffu, es = F->e[i].size;
+    if (last > eo) total += es > last - eo ? es - (last - eo) : 0u;
+    else if (last == eo) total += es;
+    last = (uint16_t)total;
+  }
+  return total;
 }
 
 // ---------------- model (runs on the thread that owns the event's node) ----------------
@@ -537,6 +667,34 @@ __device__ __forceinline__ void trace_ip_drop(const P2PDev &M, Emit &E, uint32_t
 __device__ __forceinline__ void trace_te_drop(const P2PDev &M, Emit &E, uint32_t d, const Pkt &e) {
   const uint32_t app = (e.app & NSGPU_PKT_APP) | ((e.app & NSGPU_PKT_ICMP_OF_REPLY) ? NSGPU_PKT_REPLY : 0u);
   trace_call(M, E, NSGPU_TR_IP_DROP, d, Pkt{app, e.ipid >> 16, e.ttl >> 16, 1u});
+}
+
+// The Drop record that follows an ICMP error's device step (NodeOut::xdrop).  XDROP_FRAG (extended handlers): a
+// fragment timeout's, on the captured input device with the captured header's TTL (the error embeds it).
+template <bool EXT>
+__device__ __forceinline__ void xdrop_record(const P2PDev &M, Emit &E, uint32_t xdrop, const Pkt &e) {
+  if (EXT && (xdrop & XDROP_FRAG)) {
+    const uint32_t app = (e.app & NSGPU_PKT_APP) | ((e.app & NSGPU_PKT_ICMP_OF_REPLY) ? NSGPU_PKT_REPLY : 0u);
+    trace_call(M, E, NSGPU_TR_IP_DROP, (xdrop & ~XDROP_FRAG) - 1, Pkt{app, e.ipid >> 16, e.ttl >> 16, (e.ttl >> 8) & 0xffu});
+    return;
+  }
+  trace_te_drop(M, E, xdrop - 1, e);
+}
+// SendRealOut (ipv4-l3-protocol.cc:722-731, 751-761) of a datagram above the MTU, DoFragmentation (:1116-1206): the
+// fragments take FRAG_PART bytes of IP payload each, the last the rest; each has IPv4 length 20 + part, all but the
+// last MF, the offset in 8-byte units, one identification.  For each fragment in order: m_txTrace, then the device's
+// Send (`step`: one single-packet device step) — the first may start transmitting, the rest queue or are dropped.
+// The fragment of datagram d (its IPv4 length in size) at payload offset off; *more: another follows.
+__device__ __forceinline__ Pkt fragment_at(const Pkt &d, uint32_t off, bool *more) {
+  const uint32_t L = d.size - 20u;
+  *more = L > off + FRAG_PART;  // p->GetSize () > offset + fragmentSize
+  const uint32_t part = *more ? FRAG_PART : L - off;
+  return Pkt{d.app, (d.ipid & 0xffffu) | ((off >> 3) << NSGPU_PKT_FRAG_SHIFT) | (*more ? NSGPU_PKT_FRAG_MF : 0u),
+             20u + part, d.ttl};
+}
+// A sender's device step whose datagram is above the MTU (an ICMP error is 56 bytes: never).
+__device__ __forceinline__ bool is_fragmenting_send(uint32_t op, uint32_t size) {
+  return op == ACT_SEND && size > FRAG_MTU;
 }
 
 __device__ __forceinline__ void device_act(const P2PDev &M, Emit &E, const Act &act) {
@@ -841,6 +999,8 @@ __device__ __forceinline__ NodeOut node_part(const P2PDev &M, Emit &E, uint32_t 
   Post post{false, 0, 0, 0};
   bool cancelled = false;
   uint32_t xdrop = 0;
+  // (a frag scenario's senders write the header's 16-bit identification: the upper half is the fragment's)
+  const uint32_t idm = (PORTS && M.frag) ? 0xffffu : 0xffffffffu;
   if (kind == K_RECEIVE) {  // PointToPointNetDevice::Receive -> Ipv4L3Protocol::Receive (ipv4-l3-protocol.cc:434-537)
     if (rx_atomic) atomicAdd(&M.dev[a].c.rx_packets, 1u);
     else M.dev[a].c.rx_packets++;
@@ -860,10 +1020,29 @@ __device__ __forceinline__ NodeOut node_part(const P2PDev &M, Emit &E, uint32_t 
       // (per flow: not for an ICMP error, whose word holds flag bits above the flow and finds no endpoint anyway)
       if (PORTS && !reply && sink == EP_BY_FLOW)
         k = (p.app & NSGPU_PKT_ICMP) ? -1 : ep_of_flow(M, p.app & NSGPU_PKT_APP);
+      // LocalDeliver (:849-859): a fragment (MF set or offset != 0) goes through ProcessFragment first; the datagram
+      // that is entire goes on, and `ip`, the header UdpL4Protocol::Receive and SendDestUnreachPort see, stays the
+      // arrived fragment's
+      const Pkt ip = p;
+      bool held = false;
+      if (PORTS && M.frag && !(p.app & NSGPU_PKT_ICMP) && (p.ipid >> NSGPU_PKT_FRAG_SHIFT) != 0) {
+        const uint32_t fi = M.node_ipid[M.n_nodes + n];
+        if (fi == NOFRAG) {  // (create gives every destination of a fragmenting flow its state)
+          atomicOr(M.error, ERR_FRAG_STATE);
+          held = true;
+        } else {
+          const FragRx r = frag_receive(frag_nodes(M.node_ipid, M.n_nodes) + fi, M.error, p, a);
+          if (r.flags & 1u)  // Simulator::Schedule (m_fragmentExpirationTimeout, HandleFragmentsTimeout)
+            E.child(frag_hdr(M.node_ipid, M.n_nodes)->timeout, E.ctx, K_FRAG_TIMEOUT | (r.gen << 8), n, Pkt{0, 0, 0, 0});
+          held = !(r.flags & 2u);
+          p = r.p;
+        }
+      }
       if (p.app & NSGPU_PKT_ICMP) {
+      } else if (PORTS && held) {
       } else if (k < 0 || !(M.app_flags[k] & 2u)) {  // no bound endpoint: RX_ENDPOINT_UNREACH
         hs.unreach++;
-        if (M.icmp) act = icmp_act(M, n, icmp_error(p, true), hs);  // SendDestUnreachPort (ip, copy)
+        if (M.icmp) act = icmp_act(M, n, icmp_error(ip, true), hs);  // SendDestUnreachPort (ip, copy)
       } else {
         // Ipv4EndPoint::ForwardUp: ScheduleNow (&Ipv4EndPoint::DoForwardUp) (ipv4-end-point.cc:112-120);
         // run inline for a PacketSink, queued for the echo applications (their HandleRead schedules)
@@ -908,7 +1087,7 @@ __device__ __forceinline__ NodeOut node_part(const P2PDev &M, Emit &E, uint32_t 
       if (out == 0xffffffffu) {
         hs.no_route++;
       } else {
-        p.ipid = M.node_ipid[an]++;
+        p.ipid = M.node_ipid[an]++ & idm;
         act = Act{ACT_SEND, out, p};
       }
       const uint32_t sent = ++M.app_tot[a];  // ++m_sent
@@ -928,7 +1107,7 @@ __device__ __forceinline__ NodeOut node_part(const P2PDev &M, Emit &E, uint32_t 
       if (out == 0xffffffffu) {
         hs.no_route++;
       } else {  // ++m_sent only when Send returned >= 0
-        p.ipid = M.node_ipid[an]++;
+        p.ipid = M.node_ipid[an]++ & idm;
         act = Act{ACT_SEND, out, p};
         M.app_tot[a] = ++sent;
         M.appc[a].tx_packets++;
@@ -951,7 +1130,7 @@ __device__ __forceinline__ NodeOut node_part(const P2PDev &M, Emit &E, uint32_t 
       if (out == 0xffffffffu) {
         hs.no_route++;
       } else {
-        p.ipid = M.node_ipid[an]++;  // Ipv4L3Protocol::BuildHeader: SetIdentification (m_identification++)
+        p.ipid = M.node_ipid[an]++ & idm;  // Ipv4L3Protocol::BuildHeader: SetIdentification (m_identification++)
         act = Act{ACT_SEND, out, p};
       }
       M.app_tot[a] += sz;
@@ -1035,7 +1214,7 @@ __device__ __forceinline__ NodeOut node_part(const P2PDev &M, Emit &E, uint32_t 
             if (out == 0xffffffffu) {
               hs.no_route++;
             } else {
-              r.ipid = M.node_ipid[an]++;
+              r.ipid = M.node_ipid[an]++ & idm;
               act = Act{ACT_SEND, out, r};
             }
           }
@@ -1043,6 +1222,28 @@ __device__ __forceinline__ NodeOut node_part(const P2PDev &M, Emit &E, uint32_t 
         break;
       case K_STOP:
         hs.stop = true;
+        break;
+      case K_FRAG_TIMEOUT:  // Ipv4L3Protocol::HandleFragmentsTimeout (:1391-1412), a = the node
+        if (PORTS && M.frag) {
+          FragNode *F = frag_nodes(M.node_ipid, M.n_nodes) + M.node_ipid[M.n_nodes + a];
+          if (!F->live || F->gen != gen) {  // cancelled when its datagram was entire: dispatched, counted
+            cancelled = true;
+            F->cancelled++;
+            break;
+          }
+          const uint32_t part = frag_partial_size(F);
+          const Pkt ip = F->hdr;
+          const uint32_t iif = F->iif;
+          F->timeouts++;
+          F->live = 0;
+          F->n = 0;
+          // more than 8 bytes: SendTimeExceededTtl (ipHeader, packet), to the captured header's source
+          if (part > 8 && M.icmp) act = icmp_act(M, a, icmp_error(ip, false), hs);
+          // m_dropTrace (ipHeader, packet, DROP_FRAGMENT_TIMEOUT, .., iif), after the error's Send: the captured
+          // header's fields — flow, identification, length, TTL (the packet is the partial one: no sequence number)
+          if (act.op == ACT_SEND) xdrop = (iif + 1) | XDROP_FRAG;
+          else trace_ip_drop(M, E, iif, Pkt{ip.app, ip.ipid, ip.size, ip.ttl & 0xffu});
+        }
         break;
       default:  // K_DEV_START: no-op
         break;

@@ -1,5 +1,6 @@
-// nsgpu_p2p_ports.hip — the p2p subset's handler kernels for scenarios with UDP ports (k2_handle<.., PORTS = true>:
-// the per-flow endpoint lookup, UdpClient, UdpServer; nsgpu_p2p_dev.h "UDP ports"), and PacketLossCounter on its own.
+// nsgpu_p2p_ports.hip — the p2p subset's extended handler kernels, for scenarios with UDP ports or IPv4 fragmentation
+// (k2_handle<.., PORTS = true>: the per-flow endpoint lookup, UdpClient, UdpServer; fragments sent by the device
+// step, reassembly and its timeout; nsgpu_p2p_dev.h "UDP ports", "IPv4 fragmentation"), and PacketLossCounter on its own.
 // A translation unit of its own, and so a code object of its own: nsgpu_p2p.hip's holds exactly the kernels it held
 // before ports existed, so the engines of scenarios without ports run the same code at the same layout.  The window
 // header is compiled here for k2_handle alone (NSGPU_P2P_HANDLERS_ONLY): its other kernels stay nsgpu_p2p.hip's.

@@ -1133,6 +1133,33 @@ __device__ __forceinline__ void device_act_cached(const P2PDev &M, Emit &E, cons
   }
 }
 
+// The device step of the extended handlers (EXT): in a frag scenario a Send above the MTU runs device_act_cached
+// once per fragment, in order (SendRealOut's loop over DoFragmentation's list, ipv4-l3-protocol.cc:751-761): the
+// first fragment may start transmitting, which makes the step's two children; the rest queue or are dropped.
+template <bool EXT>
+__device__ __forceinline__ void device_step(const P2PDev &M, Emit &E, const Act &act, DevCache &D) {
+  if constexpr (!EXT) {
+    device_act_cached(M, E, act, D);
+  } else {
+    const bool fr = M.frag && is_fragmenting_send(act.op, act.p.size);
+    Act f = act;
+    uint32_t off = 0, nf = 0;
+    bool more = false;
+    do {
+      if (fr) {
+        f.p = fragment_at(act.p, off, &more);
+        off += FRAG_PART;
+        nf++;
+      }
+      device_act_cached(M, E, f, D);
+    } while (more);
+    if (fr) {
+      M.dev[act.dev].frag_dgrams++;
+      M.dev[act.dev].frag_sent += nf;
+    }
+  }
+}
+
 template <bool WIDE, bool DF = false, bool PORTS = false>
 __device__ __forceinline__ void handle_node2(const P2PDev &M, Ctl &C, uint32_t i0, uint32_t W, uint32_t base, Red &R,
                                              uint32_t *lds, const HCtl &hc, SlotPre sp, uint32_t *lcnt_sh) {
@@ -1280,8 +1307,8 @@ __device__ __forceinline__ void handle_node2(const P2PDev &M, Ctl &C, uint32_t i
         E.lj = -1;
         {  // run_event with the device step on the cached state
           const NodeOut o = node_part<PORTS>(M, E, kw, a, pk, sink, hs, true, hint);
-          device_act_cached(M, E, o.act, D);
-          if (o.xdrop) trace_te_drop(M, E, o.xdrop - 1, o.act.p);
+          device_step<PORTS>(M, E, o.act, D);
+          if (o.xdrop) xdrop_record<PORTS>(M, E, o.xdrop, o.act.p);
           if (o.post.valid) E.child(o.post.delay, E.ctx, o.post.kind, o.post.a, Pkt{0, 0, 0, 0});
           hs.cancelled += o.cancelled;
         }
@@ -2007,6 +2034,11 @@ __device__ __forceinline__ void hub_node(const P2PDev &M, Ctl &C, uint32_t c, ui
         op[u] = hp->op;
         dv[u] = hp->dev;
         pd[u] = hp->pad;
+        // (a multi-fragment send is several queue steps of one event: the device scan declines the window, like one
+        // with inline children, and the serial pass takes it)
+        // (... and so does a fragment timeout's error: the Drop record that follows its Send is XDROP_FRAG's, which
+        // only xdrop_record decodes)
+        if (PORTS && M.frag && (is_fragmenting_send(op[u], hp->p.size) || (hp->xdrop & XDROP_FRAG))) pd[u] |= 0x80000000u;
       }
 #pragma unroll
     for (int u = 0; u < HSO; u++)
@@ -2117,8 +2149,8 @@ __device__ __forceinline__ void hub_node(const P2PDev &M, Ctl &C, uint32_t c, ui
           E.demote = rel == slo || rel == shi;
           E.lj = -1;
           hs.cancelled += h.cancelled;
-          device_act_cached(M, E, Act{h.op, h.dev, h.p}, D);
-          if (h.xdrop) trace_te_drop(M, E, h.xdrop - 1, h.p);
+          device_step<PORTS>(M, E, Act{h.op, h.dev, h.p}, D);
+          if (h.xdrop) xdrop_record<PORTS>(M, E, h.xdrop, h.p);
           if (h.pkind) E.child(h.pdelay, h.ctx, h.pkind, h.pa, Pkt{0, 0, 0, 0});
           const uint32_t ni = rel < inline_lim ? h.pad : 0u;
           slot_done(M, s, key, E.n, ni, xa);

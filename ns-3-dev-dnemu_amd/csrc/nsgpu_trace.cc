@@ -38,11 +38,13 @@ using nsgpu::set_error;
 
 struct nsgpu_trace_codec {
   uint32_t n_nodes = 0, n_devices = 0, n_apps = 0, n_dst = 0;
+  bool frag = false;  // the scenario has IPv4 fragmentation on: a UDP record's upper ipid half is the fragment's
   std::vector<uint32_t> dev_node, dev_peer, dev_addr, dev_ipif, ifindex;
   std::vector<uint32_t> route, route_def, route_exc_slot, route_exc_dev;
   std::vector<uint64_t> route_exc_off;
   std::vector<uint32_t> app_kind, app_node, app_dst, app_dst_slot, app_src_slot, app_ttl, app_raddr, app_rport;
   std::vector<uint32_t> eport, first_addr;
+  std::vector<uint32_t> app_size;  // PacketSize (0 where the scenario gives none)
   std::vector<int32_t> echo_server;  // per node: its UdpEchoServer application (the last one), -1: none
 
   uint32_t next_hop(uint32_t n, uint32_t slot) const {
@@ -294,6 +296,17 @@ bool seqts_record(const nsgpu_trace_codec &c, const nsgpu_trace_record &r) {
   return c.app_kind[r.app & NSGPU_PKT_APP] == NSGPU_APP_UDP_CLIENT;
 }
 const char *const kSeqTs = "a UdpClient datagram: the codec does not write SeqTsHeader payloads";
+// A record of an IPv4 fragment (frag scenarios: offset or MF above the identification, nsgpu_types.h): Packet::Print's
+// wording for fragmented items and the fragments' bytes are pinned by no fixture here, so it is refused as well.
+// An ICMP error about a fragment is refused too: the error's descriptor embeds the offending header's
+// identification, length and TTL, not its MF bit and offset, and every packet of a flow whose payload is above
+// 1472 bytes is a fragment.
+bool fragment_record(const nsgpu_trace_codec &c, const nsgpu_trace_record &r) {
+  if (!c.frag) return false;
+  if (r.app & NSGPU_PKT_ICMP) return c.app_size[r.app & NSGPU_PKT_APP] > 1472u;
+  return (r.ipid >> NSGPU_PKT_FRAG_SHIFT) != 0;
+}
+const char *const kFragment = "an IPv4 fragment or an ICMP error about one: the codec does not write fragments";
 
 // PcapFile::Init (pcap-file.cc:300-346): magic, version 2.4, thiszone 0, sigfigs 0, snaplen, network
 // (native little-endian, no swap)
@@ -336,6 +349,7 @@ int nsgpu_trace_codec_create(const nsgpu_p2p_scenario *sc, const nsgpu_trace_add
   if (!c) return set_error(NSGPU_ENOMEM, "nsgpu_trace_codec_create: out of memory");
   const uint32_t N = sc->n_nodes, D = sc->n_devices, A = sc->n_apps;
   c->n_nodes = N, c->n_devices = D, c->n_apps = A, c->n_dst = sc->n_dst;
+  c->frag = sc->frag != 0;
   c->dev_node.assign(sc->dev_node, sc->dev_node + D);
   c->dev_peer.assign(sc->dev_peer, sc->dev_peer + D);
   c->dev_addr.assign(ad->dev_addr, ad->dev_addr + D);
@@ -356,6 +370,8 @@ int nsgpu_trace_codec_create(const nsgpu_p2p_scenario *sc, const nsgpu_trace_add
     }
   if (A) {
     c->app_kind.assign(sc->app_kind, sc->app_kind + A);
+    c->app_size.assign(A, 0);
+    if (sc->app_pkt_size) c->app_size.assign(sc->app_pkt_size, sc->app_pkt_size + A);
     c->app_node.assign(sc->app_node, sc->app_node + A);
     c->app_dst.assign(sc->app_dst_node, sc->app_dst_node + A);
     c->app_dst_slot.assign(sc->app_dst_slot, sc->app_dst_slot + A);
@@ -428,6 +444,7 @@ int nsgpu_trace_line(const nsgpu_trace_codec *c, const nsgpu_trace_record *r, ch
   if (!c || !r || !len) return set_error(NSGPU_EINVAL, "nsgpu_trace_line: null");
   if (!record_ok(*c, *r)) return set_error(NSGPU_EINVAL, "nsgpu_trace_line: malformed record");
   if (seqts_record(*c, *r)) return set_error(NSGPU_EINVAL, "nsgpu_trace_line: the record is %s", kSeqTs);
+  if (fragment_record(*c, *r)) return set_error(NSGPU_EINVAL, "nsgpu_trace_line: the record is %s", kFragment);
   std::string o;
   line(*c, *r, o);
   return copy_out(o.data(), o.size(), out, cap, len);
@@ -438,6 +455,7 @@ int nsgpu_trace_packet(const nsgpu_trace_codec *c, const nsgpu_trace_record *r, 
   if (!c || !r || !len) return set_error(NSGPU_EINVAL, "nsgpu_trace_packet: null");
   if (!record_ok(*c, *r)) return set_error(NSGPU_EINVAL, "nsgpu_trace_packet: malformed record");
   if (seqts_record(*c, *r)) return set_error(NSGPU_EINVAL, "nsgpu_trace_packet: the record is %s", kSeqTs);
+  if (fragment_record(*c, *r)) return set_error(NSGPU_EINVAL, "nsgpu_trace_packet: the record is %s", kFragment);
   std::vector<uint8_t> o;
   packet_bytes(*c, *r, o);
   return copy_out(o.data(), o.size(), out, cap, len);
@@ -452,6 +470,8 @@ int nsgpu_trace_ascii(const nsgpu_trace_codec *c, const nsgpu_trace_record *rec,
     if (!record_ok(*c, rec[i])) return set_error(NSGPU_EINVAL, "nsgpu_trace_ascii: record %llu is malformed", (unsigned long long)i);
     if (seqts_record(*c, rec[i]))
       return set_error(NSGPU_EINVAL, "nsgpu_trace_ascii: record %llu is %s", (unsigned long long)i, kSeqTs);
+    if (fragment_record(*c, rec[i]))
+      return set_error(NSGPU_EINVAL, "nsgpu_trace_ascii: record %llu is %s", (unsigned long long)i, kFragment);
     line(*c, rec[i], o);
   }
   return copy_out(o.data(), o.size(), out, cap, len);
@@ -470,6 +490,8 @@ int nsgpu_trace_pcap(const nsgpu_trace_codec *c, const nsgpu_trace_record *rec, 
     if (!record_ok(*c, r)) return set_error(NSGPU_EINVAL, "nsgpu_trace_pcap: record %llu is malformed", (unsigned long long)i);
     if (seqts_record(*c, r))
       return set_error(NSGPU_EINVAL, "nsgpu_trace_pcap: record %llu is %s", (unsigned long long)i, kSeqTs);
+    if (fragment_record(*c, r))
+      return set_error(NSGPU_EINVAL, "nsgpu_trace_pcap: record %llu is %s", (unsigned long long)i, kFragment);
     pk.clear();
     packet_bytes(*c, r, pk);
     const uint64_t us = r.ts / 1000;  // (Time::GetMicroSeconds, PcapFileWrapper::Write)

@@ -48,6 +48,8 @@ NsgpuP2pScenario::NsgpuP2pScenario ()
   : m_nodes (0),
     m_nDst (0),
     m_icmp (true),
+    m_frag (false),
+    m_fragTimeout (0),
     m_stop (-1),
     m_firstLink (true),
     m_engine (0),
@@ -188,6 +190,13 @@ void
 NsgpuP2pScenario::SetIcmp (bool on)
 {
   m_icmp = on;
+}
+
+void
+NsgpuP2pScenario::SetFragmentation (bool on, Time timeout)
+{
+  m_frag = on;
+  m_fragTimeout = timeout.GetTimeStep ();
 }
 
 namespace {
@@ -384,7 +393,8 @@ NsgpuP2pScenario::FromNodeList (Ptr<HipSimulatorImpl> impl)
         }
       if (UintAttribute (p, "Mtu") != 1500)
         {
-          // the engine forwards whole datagrams up to 1500 bytes (no Ipv4L3Protocol fragmentation, ipv4-l3-protocol.cc:722)
+          // the engine's devices all have MTU 1500: only a datagram's sender fragments it (ipv4-l3-protocol.cc:722),
+          // a forwarder never does
           NS_FATAL_ERROR ("NsgpuP2pScenario::FromNodeList: device " << d << "'s Mtu is " << UintAttribute (p, "Mtu")
                           << ", not 1500");
         }
@@ -396,6 +406,7 @@ NsgpuP2pScenario::FromNodeList (Ptr<HipSimulatorImpl> impl)
     }
   // ---- Ipv4: interface addresses and indices, DefaultTtl ----
   std::vector<uint32_t> ttl (N, 64);
+  int64_t fragTimeout = -1;  // the nodes' FragmentExpirationTimeout (-1: no Ipv4L3Protocol seen yet)
   std::map<uint32_t, uint32_t> nodeOfAddr;
   for (uint32_t n = 0; n < N; n++)
     {
@@ -421,9 +432,32 @@ NsgpuP2pScenario::FromNodeList (Ptr<HipSimulatorImpl> impl)
       if (l3 != 0)
         {
           ttl[n] = UintAttribute (l3, "DefaultTtl");
+          // one FragmentExpirationTimeout for the whole scenario (ipv4-l3-protocol.cc:61-64)
+          const int64_t ft = TimeAttribute (l3, "FragmentExpirationTimeout").GetTimeStep ();
+          if (ft <= 0)
+            {
+              // (ns-3 would expire a buffer at once; in nsgpu_p2p_scenario 0 means the default 30 s)
+              NS_FATAL_ERROR ("NsgpuP2pScenario::FromNodeList: node " << n << "'s FragmentExpirationTimeout is not positive");
+            }
+          if (fragTimeout >= 0 && ft != fragTimeout)
+            {
+              NS_FATAL_ERROR ("NsgpuP2pScenario::FromNodeList: node " << n << "'s FragmentExpirationTimeout differs "
+                              "from the other nodes'");
+            }
+          fragTimeout = ft;
         }
     }
   // ---- applications ----
+  // (a timeout given to SetFragmentation must be the nodes': the engine has one, and the program's objects decide)
+  if (m_fragTimeout != 0 && fragTimeout > 0 && m_fragTimeout != fragTimeout)
+    {
+      NS_FATAL_ERROR ("NsgpuP2pScenario::FromNodeList: SetFragmentation's timeout differs from the nodes' "
+                      "FragmentExpirationTimeout");
+    }
+  if (fragTimeout > 0)
+    {
+      m_fragTimeout = fragTimeout;
+    }
   for (uint32_t a = 0; a < apps.size (); a++)
     {
       Ptr<Application> o = apps[a];
@@ -520,6 +554,12 @@ NsgpuP2pScenario::FromNodeList (Ptr<HipSimulatorImpl> impl)
             }
           x.dst = nodeOfAddr[remote];
           x.remoteAddr = remote;
+        }
+      // a payload above 1500 - 20 - 8 bytes is fragmented by its sender's Ipv4L3Protocol (a UdpClient's PacketSize
+      // counts its payload whole): the engine models that only when told to (nsgpu_p2p_scenario.frag)
+      if ((x.kind == NSGPU_APP_ONOFF || x.kind == NSGPU_APP_ECHO_CLIENT || x.kind == NSGPU_APP_UDP_CLIENT) && x.size > 1472)
+        {
+          m_frag = true;
         }
       m_app.push_back (x);
     }
@@ -623,6 +663,9 @@ NsgpuP2pScenario::Fill (void)
   sc.app_port = &m_cPort[0], sc.app_remote_port = &m_cRport[0], sc.app_loss_window = &m_cWindow[0];
   sc.stop_ns = m_stop;
   sc.icmp = m_icmp ? 1u : 0u;
+  sc.frag = m_frag ? 1u : 0u;
+  sc.pad_frag_ = 0;
+  sc.frag_timeout_ns = m_fragTimeout;
   sc.n_setup = m_setup.size ();
   sc.setup_kind = m_cSk.empty () ? 0 : &m_cSk[0];
   sc.setup_index = m_cSi.empty () ? 0 : &m_cSi[0];

@@ -47,7 +47,7 @@ public:
   void InstallStack (void);
   uint32_t AddPacketSink (uint32_t node, Time start, Time stop, uint16_t port = 9);
   /* UdpClientHelper (address of dstNode, remotePort).Install / UdpServerHelper (port).Install; packetSize counts the
-   * 12-byte SeqTsHeader ([12, 1472]), packetWindowSize is a multiple of 8 in [8, 256] */
+   * 12-byte SeqTsHeader ([12, 1472]; with SetFragmentation [12, 1500]), packetWindowSize is a multiple of 8 in [8, 256] */
   uint32_t AddUdpClient (uint32_t node, uint32_t dstNode, Time start, Time stop, uint32_t maxPackets, Time interval,
                          uint32_t packetSize, uint32_t ttl, uint16_t remotePort = 100);
   uint32_t AddUdpServer (uint32_t node, Time start, Time stop, uint16_t port = 100, uint16_t packetWindowSize = 32);
@@ -62,6 +62,13 @@ public:
   /* InternetStackHelper installs Icmpv4L4Protocol: TTL expiries and unbound arrivals send ICMP errors back
    * to the sender (icmpv4-l4-protocol.cc:131-165).  On by default, as in the reference. */
   void SetIcmp (bool on);
+  /* Ipv4L3Protocol fragments a datagram above the devices' 1500-byte MTU and reassembles it at its destination
+   * (ipv4-l3-protocol.cc:722-761, 1116-1412).  Off by default: a payload above 1472 bytes is then refused.  On:
+   * OnOff / UdpEchoClient payloads up to 65507 bytes, UdpClient PacketSize up to 1500, at most one fragmenting flow
+   * into a node; timeout = Ipv4L3Protocol::FragmentExpirationTimeout (zero: its default, 30 s).  FromNodeList turns
+   * it on when an application's PacketSize needs it and reads the timeout from the nodes' Ipv4L3Protocol: one positive
+   * value for all nodes (a timeout set here before must equal it; 0 is fatal, it would mean "default" to the engine). */
+  void SetFragmentation (bool on, Time timeout = Time ());
   /* Ipv4GlobalRoutingHelper::PopulateRoutingTables on the GPU (nsgpu_route_global): next hops towards every
    * flow destination and, with ICMP, every sender.  With every device addressed the ties are global
    * routing's (lowest peer address, then interface); an unaddressed topology takes the lowest device. */
@@ -133,6 +140,8 @@ private:
   std::vector<Ptr<NetDevice> > m_devObj;                // FromNodeList: the ns-3 device of each engine device
   uint32_t m_nDst;
   bool m_icmp;
+  bool m_frag;
+  int64_t m_fragTimeout;                                // FragmentExpirationTimeout (ns; 0: the default)
   int64_t m_stop;
   bool m_firstLink;
   nsgpu_p2p *m_engine;

@@ -162,6 +162,7 @@ SIGNATURES = {
     "nsgpu_p2p_pending": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "nsgpu_p2p_get_wide": (C.c_int, [_vp, _vp]),
     "nsgpu_p2p_udp_servers": (C.c_int, [_vp, _vp, _vp]),
+    "nsgpu_p2p_frag_stats": (C.c_int, [_vp, _vp, _vp]),
     "nsgpu_loss_counter_run": (C.c_int, [C.c_uint32, _vp, C.c_uint64, _vp, C.c_int, _vp]),
     "nsgpu_p2p_setup_uid": (C.c_int, [_vp, _vp]),
     "nsgpu_p2p_advance": (C.c_int, [_vp, _u64, _u32, _vp, _vp, _vp, _vp]),

@@ -48,6 +48,7 @@ class ScenarioStruct(C.Structure):
         ("route_default", C.c_void_p), ("route_exc_off", C.c_void_p), ("route_exc_slot", C.c_void_p),
         ("route_exc_dev", C.c_void_p), ("uid_first", C.c_uint32), ("pad_uid_", C.c_uint32),
         ("app_port", C.c_void_p), ("app_remote_port", C.c_void_p), ("app_loss_window", C.c_void_p),
+        ("frag", C.c_uint32), ("pad_frag_", C.c_uint32), ("frag_timeout_ns", C.c_int64),
     ]
 
 
@@ -65,12 +66,19 @@ APP_COUNTERS_DTYPE = np.dtype([("tx_packets", "<u4"), ("rx_packets", "<u4"), ("t
                                ("rx_bytes", "<u8")])
 # nsgpu_udp_server_record: UdpServer::GetReceived / GetLost, the loss counter's m_lastMaxSeqNum
 UDP_SERVER_DTYPE = np.dtype([("received", "<u4"), ("lost", "<u4"), ("last_max_seq", "<u4"), ("pad_", "<u4")])
+# nsgpu_frag_stats: the IPv4 fragmentation counters of a run (Scenario (frag=True))
+FRAG_STATS_FIELDS = ("fragmented", "fragments_sent", "reassembled", "timeouts", "cancelled_timers", "max_list")
+FRAG_CAP = 128  # entries of a node's reassembly list (a run that would pass it fails)
 
 
 class Scenario:
     """Arrays of a nsgpu_p2p_scenario plus the order of setup-time Schedule calls."""
 
-    def __init__(self, n_nodes, icmp=False, ports=False):
+    def __init__(self, n_nodes, icmp=False, ports=False, frag=False, frag_timeout_ns=0):
+        # IPv4 fragmentation and reassembly on the device (nsgpu_p2p_scenario.frag): payloads up to 65507 bytes;
+        # frag_timeout_ns = Ipv4L3Protocol::FragmentExpirationTimeout (0: the reference's 30 s)
+        self.frag = frag
+        self.frag_timeout_ns = frag_timeout_ns
         self.icmp = icmp  # ICMP errors generated and routed back to senders (nsgpu_p2p_scenario.icmp)
         # UDP ports on the device (nsgpu_p2p_scenario.app_port): a datagram reaches the application of its
         # destination node bound to its remote port; several bound endpoints a node; UdpClient / UdpServer.
@@ -299,6 +307,8 @@ class Scenario:
         s.n_setup = len(self.setup)
         s.icmp = 1 if self.icmp else 0
         s.uid_first = self.uid_first
+        s.frag = 1 if self.frag else 0
+        s.frag_timeout_ns = self.frag_timeout_ns
         s._keep = arrays  # keep the arrays alive with the struct
         return s
 
@@ -604,6 +614,12 @@ class Engine:
         nsgpu.check(nsgpu.lib().nsgpu_p2p_udp_servers(self.h, out.ctypes.data, self.stream))
         return out
 
+    def frag_stats(self):
+        """The run's IPv4 fragmentation counters (nsgpu_p2p_frag_stats): a dict of FRAG_STATS_FIELDS."""
+        out = np.zeros(len(FRAG_STATS_FIELDS), np.uint64)
+        nsgpu.check(nsgpu.lib().nsgpu_p2p_frag_stats(self.h, out.ctypes.data, self.stream))
+        return {k: int(v) for k, v in zip(FRAG_STATS_FIELDS, out)}
+
     def results(self, log_n=0):
         st = P2PStats()
         devc = np.zeros(self.s.n_devices, DEV_COUNTERS_DTYPE)
@@ -818,6 +834,12 @@ class LoopbackGroup:
             m = self.owner[app_node] == r
             out[m] = rec[m]
         return out
+
+    def frag_stats(self):
+        """The run's fragmentation counters merged by owner: every rank counts what its own nodes did, so the
+        counters add up and the largest list is the ranks' largest."""
+        per = [m.frag_stats() for m in self.members]
+        return {k: (max if k == "max_list" else sum)(p[k] for p in per) for k in FRAG_STATS_FIELDS}
 
     def run(self, log_n=0):
         self.reset()

@@ -200,6 +200,22 @@ class Codec:
         return own_src, osrc, (osrc, odst, osp, odp, (int(r["ttl"]) >> 8) & 255, int(r["ipid"]) >> 16,
                                int(r["ttl"]) >> 16)
 
+    def _no_fragment(self, r):
+        # a frag scenario's UDP record with offset or MF above its identification (include/nsgpu_types.h):
+        # Packet::Print's wording for fragmented items and the fragments' bytes are pinned by nothing here: refused
+        # (... and an ICMP error about one: its descriptor embeds the offending identification, length and TTL, not MF
+        # and offset, and every packet of a flow with a payload above 1472 bytes is a fragment)
+        if not getattr(self.sc, "frag", False):
+            return
+        if int(r["app"]) & PKT_ICMP:
+            if self.sc.apps[int(r["app"]) & PKT_APP]["size"] > 1472:
+                raise ValueError("trace codec: an ICMP error about an IPv4 fragment (flow %d): fragments are not written"
+                                 % (int(r["app"]) & PKT_APP))
+            return
+        if int(r["ipid"]) >> 16:
+            raise ValueError("trace codec: an IPv4 fragment (flow %d): fragments are not written"
+                             % (int(r["app"]) & ~PKT_REPLY))
+
     def headers(self, app_word):
         """(src, dst, sport, dport) of a datagram of flow app_word."""
         a = app_word & ~PKT_REPLY
@@ -222,6 +238,7 @@ class Codec:
                 "%s > %s" % (ttl & 255, ipid & 0xffff, proto, length, dotted(src), dotted(dst)))
 
     def packet_text(self, r):
+        self._no_fragment(r)
         if int(r["app"]) & PKT_ICMP:
             return self.icmp_text(r)
         src, dst, sp, dp = self.headers(int(r["app"]))
@@ -275,6 +292,7 @@ class Codec:
     # ---------------- pcap ----------------
     def packet_bytes(self, r):
         """Serialized packet with its PPP header (what the sniffer sees)."""
+        self._no_fragment(r)
         if int(r["app"]) & PKT_ICMP:  # IPv4 (protocol 1) + Icmpv4Header + TimeExceeded / DestinationUnreachable
             own_src, own_dst, (osrc, odst, osp, odp, ottl, oid, olen) = self.icmp_fields(r)
             ip_len = int(r["size"]) - (0 if r["kind"] in _L3 else PPP_HDR)
