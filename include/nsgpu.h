@@ -598,6 +598,20 @@ int nsgpu_p2p_frag_stats(nsgpu_p2p *h, nsgpu_frag_stats *out, void *stream);
  * 1: the same function in a one-thread kernel on `stream` (the function the engine's handlers call). */
 int nsgpu_loss_counter_run(uint32_t window, const uint32_t *seq, uint64_t n, uint32_t *lost, int on_device,
                            void *stream);
+/* Receive error models (nsgpu_p2p_scenario.dev_em_kind): per device, the IsCorrupt calls on its enabled model and
+ * the frames it declared corrupt, n_devices records (zeros for a device without an enabled model; a partitioned
+ * engine returns its own nodes' devices: the owner's values count).  An engine with an enabled model cannot join a
+ * host-closure runtime (nsgpu_p2p_setup_uid, nsgpu_sim_attach_p2p / _adopt_p2p) and refuses nsgpu_p2p_inject_send. */
+int nsgpu_p2p_error_models(nsgpu_p2p *h, nsgpu_error_model_record *out, void *stream);
+/* The threshold table nsgpu_p2p_create builds for an EU_BYTE / EU_BIT Rate model (host only): out[n] =
+ * 1 - pow (1.0 - rate, n or 8 n) for frame sizes n = 0 .. NSGPU_EM_TABLE_SIZE - 1, with the host's pow. */
+int nsgpu_error_model_thresholds(uint32_t unit, double rate, double *out);
+/* RngStream on its own: out[0 .. n) = the first n U01 () values of the stream_index-th (0-based) RngStream of a
+ * program with RngSeed `seed` and RngRun `run` (0: the default, 1).  on_device = 0: on the host; 1: the same step
+ * function in a one-thread kernel on `stream` (the function the engine's handlers call).  A seed CheckSeed rejects
+ * is NSGPU_EINVAL. */
+int nsgpu_rng_stream_run(uint32_t seed, uint32_t run, uint32_t stream_index, uint64_t n, double *out, int on_device,
+                         void *stream);
 /* Launch mode of nsgpu_p2p_run: 0 = hipGraph replays (default), 1 = the same kernels launched one by
  * one (also selected by the environment variable NSGPU_P2P_EAGER; used under rocprofv3). */
 int nsgpu_p2p_set_eager(nsgpu_p2p *h, int eager);

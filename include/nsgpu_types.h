@@ -194,7 +194,49 @@ typedef struct nsgpu_p2p_scenario {
   uint32_t frag;
   uint32_t pad_frag_;
   int64_t frag_timeout_ns;
+  /* ---- receive error models (appended: the fields above keep their offsets) ----
+   * dev_em_kind == NULL: no device has a model (the other fields are then ignored).  Given: device d's
+   * PointToPointNetDevice::SetReceiveErrorModel (point-to-point-net-device.cc:304-317: Receive asks IsCorrupt first;
+   * a corrupt frame fires PhyRxDrop and nothing else) — NSGPU_EM_NONE, NSGPU_EM_RECEIVE_LIST
+   * (ReceiveListErrorModel, error-model.cc:343-360: the frames whose 0-based arrival ordinal at the device is in
+   * the list) or NSGPU_EM_RATE (RateErrorModel, :178-223: one UniformVariable (0, 1) draw a frame against the rate
+   * (EU_PKT) or 1 - pow (1 - rate, size or 8 * size) (EU_BYTE, EU_BIT), size = the frame with its PPP header).
+   *   dev_em_enabled   ErrorModel::IsEnabled () at setup (NULL: all enabled); a disabled model counts, draws and
+   *                    drops nothing
+   *   dev_em_unit      NSGPU_EU_* of a Rate model (NULL: EU_BYTE, the attribute's default)
+   *   dev_em_rate      ErrorRate of a Rate model (NaN is refused)
+   *   dev_em_stream    a Rate model's variable is the dev_em_stream[d]-th RngStream the program constructs (0-based);
+   *                    two Rate devices may not name the same stream
+   *   em_list_off / em_list   CSR (n_devices + 1 offsets): the ReceiveList models' lists, any order, duplicates allowed
+   *   rng_seed / rng_run      RngSeed / RngRun (0: the reference's default, 1)
+   * At most NSGPU_EM_MAX_TABLES distinct (unit, rate) pairs of enabled EU_BYTE / EU_BIT models a scenario. */
+  const uint32_t *dev_em_kind;
+  const uint32_t *dev_em_enabled;
+  const uint32_t *dev_em_unit;
+  const double *dev_em_rate;
+  const uint32_t *dev_em_stream;
+  const uint64_t *em_list_off;
+  const uint32_t *em_list;
+  uint32_t rng_seed;
+  uint32_t rng_run;
 } nsgpu_p2p_scenario;
+
+enum { NSGPU_EM_NONE = 0, NSGPU_EM_RECEIVE_LIST = 1, NSGPU_EM_RATE = 2,
+       NSGPU_EM_LIST = 3 /* ListErrorModel (by Packet::GetUid): named so that it can be refused */ };
+enum { NSGPU_EU_PKT = 0, NSGPU_EU_BYTE = 1, NSGPU_EU_BIT = 2 };
+#define NSGPU_EM_MAX_TABLES 16u   /* threshold tables (distinct EU_BYTE / EU_BIT (unit, rate) pairs) a scenario */
+#define NSGPU_EM_TABLE_SIZE 1503u /* frame sizes 0 .. 1502: MTU 1500 + the PPP header */
+
+/* What nsgpu_p2p_error_models returns per device (zeros without an enabled model). */
+typedef struct nsgpu_error_model_record {
+  uint32_t invoked;    /* IsCorrupt calls on the enabled model: the frames that arrived */
+  uint32_t corrupted;  /* ... of which it declared corrupt (m_phyRxDropTrace) */
+} nsgpu_error_model_record;
+
+/* RngStream (rng-stream.cc): MRG32k3a's state Cg, whose six values stay below 2^32 (csrc/nsgpu_rng_stream.h). */
+typedef struct nsgpu_rng_stream {
+  uint32_t s[6];
+} nsgpu_rng_stream;
 
 /* What nsgpu_p2p_frag_stats returns (zeros for a scenario without frag). */
 typedef struct nsgpu_frag_stats {

@@ -12,6 +12,7 @@ namespace nsgpu {
 #include <algorithm>
 #include <string.h>
 #include <stdlib.h>
+#include <math.h>
 #include <rccl/rccl.h>
 
 using namespace nsgpu;
@@ -87,7 +88,9 @@ struct nsgpu_p2p {
   // pristine initial pool (device) for resets
   uint64_t *init_ts = nullptr;
   uint32_t *init_uid = nullptr, *init_ctx = nullptr, *init_kind = nullptr, *init_a = nullptr;
-  const DevRec *dev_init = nullptr;  // device records after reset (tx state idle)
+  const DevRec *dev_init = nullptr;  // device records after reset (tx state idle), and behind them the receive error
+  size_t dev_bytes = 0;              // models' reset image (nsgpu_p2p_dev.h "receive error models"); its bytes
+  uint32_t em_models = 0;            // enabled receive error models
   const nsgpu_loss_counter *loss_init = nullptr;  // ports mode: the UdpServers' loss counters after reset
   uint32_t n_apps = 0;
   // frag mode: the reset image of what lies behind node_ipid up to the FragNodes (device), its words, the whole
@@ -164,6 +167,12 @@ struct EnginePlan {
   bool frag = false;                 // frag mode (nsgpu_p2p_scenario.frag)
   std::vector<uint32_t> frag_flows;  // frag mode: the fragmenting flows that deliver fragments to each node
   int64_t frag_timeout = 0;          // FragmentExpirationTimeout
+  // receive error models: each device's enabled model + 1 (0: none), the models' reset records, the EU_BYTE / EU_BIT
+  // threshold tables and the ReceiveList models' sorted lists
+  std::vector<uint32_t> dev_em;
+  std::vector<EmRec> em_recs;
+  std::vector<double> em_tabs;
+  std::vector<uint32_t> em_list;
   // the setup-time events (this rank's, partitioned) and the bound of window 0 (the whole setup: every rank)
   std::vector<uint64_t> its;
   std::vector<uint32_t> iuid, ictx, ikind, ia;
@@ -173,6 +182,93 @@ struct EnginePlan {
   uint32_t capx = 0;  // partitioned: X2 records per peer per window
   uint64_t x2b = 0;   // partitioned: X2 bytes per peer
 };
+
+// RateErrorModel::DoCorruptByte / DoCorruptBit (error-model.cc:207-223): out[n] = the threshold for a frame of n bytes,
+// n = 0 .. 1502, in the reference's expression and operation order, with the host's pow (the device looks it up).
+static void em_thresholds(uint32_t unit, double rate, double *out) {
+  for (uint32_t n = 0; n < NSGPU_EM_TABLE_SIZE; n++)
+    out[n] = 1 - pow(1.0 - rate, (double)(unit == NSGPU_EU_BIT ? 8 * n : n));
+}
+extern "C" int nsgpu_error_model_thresholds(uint32_t unit, double rate, double *out) {
+  if (!out || (unit != NSGPU_EU_BYTE && unit != NSGPU_EU_BIT))
+    return set_error(NSGPU_EINVAL, "nsgpu_error_model_thresholds: unit must be EU_BYTE or EU_BIT");
+  em_thresholds(unit, rate, out);
+  return NSGPU_OK;
+}
+
+// The receive error models of a scenario (nsgpu_p2p_scenario.dev_em_kind), validated; the models' reset records.
+static int plan_error_models(const nsgpu_p2p_scenario *sc, EnginePlan &P) {
+  const uint32_t D = sc->n_devices;
+  P.dev_em.assign(D, 0);
+  if (!sc->dev_em_kind) return NSGPU_OK;
+  if (!nsgpu_rng_check_seed(sc->rng_seed ? sc->rng_seed : 1u))
+    return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: rng_seed %u is not a seed RngStream::CheckSeed accepts (below "
+                     "4294944443)", sc->rng_seed);
+  std::vector<std::pair<uint32_t, uint64_t>> tabs;  // (unit, the rate's bits) of each table
+  std::vector<std::pair<uint32_t, uint32_t>> streams;  // (stream, device) of the enabled Rate models
+  for (uint32_t d = 0; d < D; d++) {
+    const uint32_t kind = sc->dev_em_kind[d];
+    if (kind == NSGPU_EM_NONE) continue;
+    if (kind == NSGPU_EM_LIST)
+      return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: device %u: ListErrorModel is not modelled (it selects by "
+                       "Packet::GetUid, and the engine carries no packet uids)", d);
+    if (kind != NSGPU_EM_RECEIVE_LIST && kind != NSGPU_EM_RATE)
+      return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: device %u: unknown error model kind %u", d, kind);
+    EmRec r{};
+    r.kind = kind;
+    r.tab = EM_NOTAB;
+    r.dev = d;
+    if (kind == NSGPU_EM_RATE) {
+      if (!sc->dev_em_rate || !sc->dev_em_stream)
+        return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: device %u: a Rate error model without dev_em_rate / dev_em_stream", d);
+      const uint32_t unit = sc->dev_em_unit ? sc->dev_em_unit[d] : (uint32_t)NSGPU_EU_BYTE;
+      if (unit > NSGPU_EU_BIT)
+        return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: device %u: unknown error unit %u", d, unit);
+      r.rate = sc->dev_em_rate[d];
+      if (r.rate != r.rate)
+        return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: device %u: the Rate error model's ErrorRate is NaN", d);
+      if (sc->dev_em_enabled && !sc->dev_em_enabled[d]) continue;  // (disabled: it draws nothing, no stream is used)
+      for (const auto &st : streams)
+        if (st.first == sc->dev_em_stream[d])
+          return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: devices %u and %u name the same RngStream %u (one Rate error "
+                           "model object shared by two devices is not modelled)", st.second, d, st.first);
+      streams.emplace_back(sc->dev_em_stream[d], d);
+      nsgpu_rng_stream_init(&r.g, sc->rng_seed, sc->rng_run, sc->dev_em_stream[d]);
+      if (unit != NSGPU_EU_PKT) {
+        uint64_t bits;
+        memcpy(&bits, &r.rate, 8);
+        uint32_t t = 0;
+        while (t < tabs.size() && !(tabs[t].first == unit && tabs[t].second == bits)) t++;
+        if (t == tabs.size()) {
+          if (t == NSGPU_EM_MAX_TABLES)
+            return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: device %u: more than %u distinct (unit, rate) pairs of "
+                             "EU_BYTE / EU_BIT error models", d, NSGPU_EM_MAX_TABLES);
+          tabs.emplace_back(unit, bits);
+          P.em_tabs.resize((size_t)(t + 1) * NSGPU_EM_TABLE_SIZE);
+          em_thresholds(unit, r.rate, P.em_tabs.data() + (size_t)t * NSGPU_EM_TABLE_SIZE);
+        }
+        r.tab = t;
+      }
+    } else {
+      const uint64_t lo = sc->em_list_off ? sc->em_list_off[d] : 0, hi = sc->em_list_off ? sc->em_list_off[d + 1] : 0;
+      if (hi < lo || (hi > lo && !sc->em_list))
+        return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: device %u: bad ReceiveList error model list", d);
+      if (sc->dev_em_enabled && !sc->dev_em_enabled[d]) continue;
+      // the std::list acts as a set: sorted, duplicates dropped
+      std::vector<uint32_t> l(sc->em_list + lo, sc->em_list + hi);
+      std::sort(l.begin(), l.end());
+      l.erase(std::unique(l.begin(), l.end()), l.end());
+      if (P.em_list.size() + l.size() > 0xffffffffull)
+        return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: the ReceiveList error models' lists hold 2^32 entries or more");
+      r.cur = (uint32_t)P.em_list.size();
+      P.em_list.insert(P.em_list.end(), l.begin(), l.end());
+      r.end = (uint32_t)P.em_list.size();
+    }
+    P.em_recs.push_back(r);
+    P.dev_em[d] = (uint32_t)P.em_recs.size();
+  }
+  return NSGPU_OK;
+}
 
 static int plan_engine(const nsgpu_p2p_scenario *sc, const uint32_t *owner, int rank, int nranks, uint64_t pool_cap,
                        EnginePlan &P) {
@@ -190,6 +286,7 @@ static int plan_engine(const nsgpu_p2p_scenario *sc, const uint32_t *owner, int 
       return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: device %u: negative delay", d);
     qcap = std::max(qcap, sc->dev_qmax[d]);
   }
+  if (int rce = plan_error_models(sc, P)) return rce;
   if (owner) {
     if (nranks < 1 || nranks > MAXR || rank < 0 || rank >= nranks ||
         (uint64_t)nranks * CAPX_MAX + TB + 2 * WCAP >= (uint64_t)GRID_POOL_DIST * TB)  // (k2_pa: slot, remote, chunk blocks)
@@ -605,12 +702,33 @@ static int create_engine(const nsgpu_p2p_scenario *sc, const uint32_t *owner, in
       r.bps = sc->dev_bps[d];
       r.ifg = sc->dev_ifg_ns[d];
       r.delay = sc->dev_delay_ns[d];
+      r.em = P.dev_em[d];
       dr[d] = r;
     }
-    const DevRec *init;
-    TRY(dupload(h, &init, dr.data(), D));
-    h->dev_init = init;
-    TRY(dalloc(h, &M.dev, D));
+    // ... and behind them the receive error models: header, records, threshold tables, lists (em_is_corrupt)
+    const uint32_t nm = (uint32_t)P.em_recs.size(), nt = (uint32_t)(P.em_tabs.size() / NSGPU_EM_TABLE_SIZE);
+    h->dev_bytes = (size_t)D * sizeof(DevRec) + (nm ? em_bytes(nm, nt, P.em_list.size()) : 0);
+    std::vector<uint8_t> img(h->dev_bytes ? h->dev_bytes : 1, 0);
+    if (D) memcpy(img.data(), dr.data(), (size_t)D * sizeof(DevRec));
+    if (nm) {
+      uint8_t *q = img.data() + (size_t)D * sizeof(DevRec);
+      const EmHdr eh{nm, nt, P.em_list.size()};
+      memcpy(q, &eh, sizeof(eh));
+      q += sizeof(eh);
+      memcpy(q, P.em_recs.data(), (size_t)nm * sizeof(EmRec));
+      q += (size_t)nm * sizeof(EmRec);
+      if (nt) memcpy(q, P.em_tabs.data(), P.em_tabs.size() * sizeof(double));
+      q += P.em_tabs.size() * sizeof(double);
+      if (!P.em_list.empty()) memcpy(q, P.em_list.data(), P.em_list.size() * sizeof(uint32_t));
+      M.errm = 1;
+      h->em_models = nm;
+    }
+    const uint8_t *init;
+    TRY(dupload(h, &init, img.data(), h->dev_bytes));
+    h->dev_init = reinterpret_cast<const DevRec *>(init);
+    uint8_t *devp;
+    TRY(dalloc(h, &devp, h->dev_bytes));
+    M.dev = reinterpret_cast<DevRec *>(devp);
   }
   TRY(dalloc(h, &M.q_buf, (size_t)D * qcap));
   TRY(dalloc(h, &M.app_flags, A));
@@ -881,13 +999,13 @@ extern "C" int nsgpu_p2p_reset(nsgpu_p2p *h, void *stream) {
   if (!h) return set_error(NSGPU_EINVAL, "nsgpu_p2p_reset: null");
   hipStream_t s = (hipStream_t)stream;
   P2PDev &M = h->M;
-  const uint32_t D = M.n_devices, A = M.n_apps, n0 = M.n_init;
+  const uint32_t A = M.n_apps, n0 = M.n_init;
   NSGPU_HIP(hipMemcpyAsync(M.ev_ts[0], h->init_ts, n0 * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
   NSGPU_HIP(hipMemcpyAsync(M.ev_uid[0], h->init_uid, n0 * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
   NSGPU_HIP(hipMemcpyAsync(M.ev_ctx[0], h->init_ctx, n0 * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
   NSGPU_HIP(hipMemcpyAsync(M.ev_kind[0], h->init_kind, n0 * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
   NSGPU_HIP(hipMemcpyAsync(M.ev_a[0], h->init_a, n0 * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
-  NSGPU_HIP(hipMemcpyAsync(M.dev, h->dev_init, D * sizeof(DevRec), hipMemcpyDeviceToDevice, s));
+  NSGPU_HIP(hipMemcpyAsync(M.dev, h->dev_init, h->dev_bytes, hipMemcpyDeviceToDevice, s));
   NSGPU_HIP(hipMemsetAsync(M.app_flags, 0, A * sizeof(uint32_t), s));
   NSGPU_HIP(hipMemsetAsync(M.app_send_gen, 0, A * sizeof(uint32_t), s));
   NSGPU_HIP(hipMemsetAsync(M.app_ss_gen, 0, A * sizeof(uint32_t), s));
@@ -954,9 +1072,9 @@ bool launch_kernel(nsgpu_p2p *h, int k, hipStream_t s, bool df, hipEvent_t ev0 =
       else NSGPU_KLAUNCH((k2_pa<false, false>), dim3(pa_grid_rt<false>(h->M)), dim3(TB), s, ev0, ev1, h->M);
       return true;
     case 1:
-      // (a scenario with ports or frag: the extended handlers — the endpoint lookup, UdpClient, UdpServer, IPv4
-      // fragmentation and reassembly — nsgpu_p2p_ports.hip)
-      if (h->loss_init || h->M.frag) launch_handle_ports(h->M, wide, false, df, K2_GRID, s, ev0, ev1);
+      // (a scenario with ports, frag or a receive error model: the extended handlers — the endpoint lookup, UdpClient,
+      // UdpServer, IPv4 fragmentation and reassembly, the error models — nsgpu_p2p_ports.hip)
+      if (h->loss_init || h->M.frag || h->M.errm) launch_handle_ports(h->M, wide, false, df, K2_GRID, s, ev0, ev1);
       else if (df) NSGPU_KLAUNCH((k2_handle<true, false, true>), dim3(K2_GRID), dim3(HB), s, ev0, ev1, h->M);
       else if (wide) NSGPU_KLAUNCH(k2_handle<true>, dim3(K2_GRID), dim3(HB), s, ev0, ev1, h->M);
       else NSGPU_KLAUNCH(k2_handle<false>, dim3(K2_GRID), dim3(HB), s, ev0, ev1, h->M);
@@ -1253,7 +1371,7 @@ static int launch_windows_dist(nsgpu_p2p *h, hipStream_t s, int nwin = NWIN) {
   for (int w = 0; w < nwin && !rc; w++) {
     dist_pa(M, s);
     rc = x_allgather(h, M.x0_send, M.x0_recv, X0B, s);
-    dist_handle(M, s, h->loss_init != nullptr || M.frag != 0);
+    dist_handle(M, s, h->loss_init != nullptr || M.frag != 0 || M.errm != 0);
     dist_rank(M, s);
     if (!rc) rc = x_allgather(h, M.x1_send, M.x1_recv, X1B, s);
     dist_rank_fin(M, s);
@@ -1512,6 +1630,10 @@ extern "C" int nsgpu_p2p_setup_uid(nsgpu_p2p *h, uint32_t *uid) {
   if (h->M.frag)
     return set_error(NSGPU_ESTATE, "nsgpu_p2p_setup_uid: a scenario with IPv4 fragmentation (frag) cannot be attached "
                      "to a host-closure runtime");
+  // (... and so does an engine with a receive error model: no test covers the combination)
+  if (h->M.errm)
+    return set_error(NSGPU_ESTATE, "nsgpu_p2p_setup_uid: a scenario with a receive error model cannot be attached to a "
+                     "host-closure runtime");
   *uid = h->C0.uid;
   return NSGPU_OK;
 }
@@ -1577,6 +1699,8 @@ extern "C" int nsgpu_p2p_inject_send(nsgpu_p2p *h, uint32_t app, uint64_t now, u
   // whose receivers read the upper half of a descriptor's identification as fragment fields)
   if (h->M.frag)
     return set_error(NSGPU_ESTATE, "nsgpu_p2p_inject_send: not available in a scenario with IPv4 fragmentation (frag)");
+  if (h->M.errm)
+    return set_error(NSGPU_ESTATE, "nsgpu_p2p_inject_send: not available in a scenario with a receive error model");
   hipStream_t s = h->s;
   if (const int rc = join_in(h, (hipStream_t)stream)) return rc;
   if (const int rc = read_ctl(h)) return rc;
@@ -1890,6 +2014,21 @@ extern "C" int nsgpu_p2p_frag_stats(nsgpu_p2p *h, nsgpu_frag_stats *out, void *s
   return NSGPU_OK;
 }
 
+// The receive error models' counters per device (zeros without an enabled model).  A partitioned engine's models
+// advance on the rank that owns the device's node; another rank's stay at zero here.
+extern "C" int nsgpu_p2p_error_models(nsgpu_p2p *h, nsgpu_error_model_record *out, void *stream) {
+  if (!h || !out) return set_error(NSGPU_EINVAL, "nsgpu_p2p_error_models: null");
+  hipStream_t s = (hipStream_t)stream;
+  const P2PDev &M = h->M;
+  memset(out, 0, M.n_devices * sizeof(*out));
+  if (!h->em_models) return NSGPU_OK;
+  std::vector<EmRec> er(h->em_models);
+  NSGPU_HIP(hipMemcpyAsync(er.data(), em_recs(M.dev, M.n_devices), er.size() * sizeof(EmRec), hipMemcpyDeviceToHost, s));
+  NSGPU_HIP(hipStreamSynchronize(s));
+  for (const EmRec &r : er) out[r.dev] = nsgpu_error_model_record{r.invoked, r.corrupted};
+  return NSGPU_OK;
+}
+
 extern "C" int nsgpu_p2p_results(nsgpu_p2p *h, nsgpu_p2p_stats *stats, nsgpu_dev_counters *devc,
                                  nsgpu_app_counters *appc, uint64_t *log_ts, uint32_t *log_uid, uint32_t *log_ctx,
                                  uint64_t log_n, uint32_t *error, void *stream) {
@@ -1948,7 +2087,7 @@ static void launch_windows_group(nsgpu_p2p_group *g, hipStream_t s, int nwin = N
   for (int w = 0; w < nwin; w++) {
     for (auto *h : g->m) dist_pa(h->M, s);
     hipLaunchKernelGGL(k_copies, dim3(n * n), dim3(256), 0, s, (const CopyDesc *)g->d_x[0]);
-    for (auto *h : g->m) dist_handle(h->M, s, h->loss_init != nullptr || h->M.frag != 0);
+    for (auto *h : g->m) dist_handle(h->M, s, h->loss_init != nullptr || h->M.frag != 0 || h->M.errm != 0);
     for (auto *h : g->m) dist_rank(h->M, s);
     hipLaunchKernelGGL(k_copies, dim3(n * n), dim3(256), 0, s, (const CopyDesc *)g->d_x[1]);
     for (auto *h : g->m) dist_rank_fin(h->M, s);

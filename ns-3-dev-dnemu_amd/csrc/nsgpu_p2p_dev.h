@@ -25,6 +25,7 @@
 #include "nsgpu_internal.h"
 #include "nsgpu_loss_counter.h"
 #include "nsgpu_p2p_span.h"
+#include "nsgpu_rng_stream.h"
 #include "nsgpu_wave.h"
 
 namespace nsgpu {
@@ -97,8 +98,8 @@ struct Pkt {
 // from another XCD's writes: measured 2.8 -> 1.6 MB HBM fetch per k2_handle launch on config 4).
 struct DevRec {
   uint32_t busy, cnt, head, qmax;  // PointToPointNetDevice m_txMachineState, DropTail count / ring head, MaxPackets
-  uint32_t peer, peer_node, rkind, pad1;  // rkind: the Receive child's kind word (K_RECEIVE | REMOTEBIT when
-  uint64_t bps;                            //   another rank owns the peer's node)
+  uint32_t peer, peer_node, rkind, em;  // rkind: the Receive child's kind word (K_RECEIVE | REMOTEBIT when another
+  uint64_t bps;                          //   rank owns the peer's node); em: its enabled receive error model + 1 (0: none)
   int64_t ifg, delay;              // InterframeGap, channel Delay
   uint64_t pad2;
   nsgpu_dev_counters c;            // (copied out strided by nsgpu_p2p_results / _counters)
@@ -341,7 +342,8 @@ struct P2PDev {
   nsgpu_trace_record *trace;
   uint64_t trace_cap;
   unsigned long long *trace_n;
-  uint32_t trace_kinds, pad_tk;  // nsgpu_trace_kind bits recorded (nsgpu_p2p_set_trace_kinds)
+  uint32_t trace_kinds, errm;  // nsgpu_trace_kind bits recorded (nsgpu_p2p_set_trace_kinds); some device has an
+                               // enabled receive error model (the extended handlers)
   // ---- single-GPU engine (k2_*) ----
   uint64_t runcap;        // capacity of the window record arrays (a sorted run may hold the whole pool)
   uint32_t *wsrc;         // pool slot each window record came from (NOSRC: a child of the last window)
@@ -568,6 +570,68 @@ __device__ __noinline__ uint32_t frag_partial_size(const FragNode *F) {
 // ---------------- model (runs on the thread that owns the event's node) ----------------
 // Children of the event being run go to its slot's child records in Schedule-call order; the ones
 // that stay pending fold into the next window's reduction (tmn, wnd).
+// ---------------- receive error models (nsgpu_p2p_scenario.dev_em_kind) ----------------
+// PointToPointNetDevice::Receive asks m_receiveErrorModel->IsCorrupt (packet) first (point-to-point-net-device.cc:
+// 304-317); a corrupt frame fires m_phyRxDropTrace, which no ascii / pcap helper hooks, and nothing else.  An enabled
+// model's state — ReceiveListErrorModel's m_timesInvoked and the cursor into its sorted list, RateErrorModel's
+// RngStream — is per device and advances in the device's own event order, like its DropTail ring: it belongs to the
+// serial pass of the device's node (no atomics), and a Receive on such a device is never "stateless" for the hub
+// blocks (nsgpu_p2p_win.h).  The records lie behind the DevRecs in their allocation (P2PDev takes no further
+// pointer, see hub_slot): the EmHdr, an EmRec for every enabled model (DevRec::em - 1), the threshold tables of the
+// EU_BYTE / EU_BIT models (the host's pow: create), then the lists.  All of it is part of the reset image.
+constexpr uint32_t EM_NOTAB = 0xffffffffu;
+struct EmRec {
+  uint32_t kind, tab;            // NSGPU_EM_*; a Rate model's threshold table (EM_NOTAB: EU_PKT, the rate itself)
+  uint32_t invoked, corrupted;   // IsCorrupt calls (ReceiveList: m_timesInvoked), frames declared corrupt
+  nsgpu_rng_stream g;            // Rate: the variable's RngStream
+  uint32_t cur, end;             // ReceiveList: the next list entry not yet reached, the list's end (list words)
+  double rate;                   // Rate: m_rate
+  uint32_t dev, pad;
+};
+static_assert(sizeof(EmRec) == 64, "EmRec");
+struct EmHdr {
+  uint32_t n_models, n_tables;
+  uint64_t list_words;
+};
+__host__ __device__ __forceinline__ EmHdr *em_hdr(DevRec *dev, uint32_t n_devices) {
+  return reinterpret_cast<EmHdr *>(dev + n_devices);
+}
+__host__ __device__ __forceinline__ EmRec *em_recs(DevRec *dev, uint32_t n_devices) {
+  return reinterpret_cast<EmRec *>(em_hdr(dev, n_devices) + 1);
+}
+__host__ __device__ __forceinline__ size_t em_bytes(uint32_t n_models, uint32_t n_tables, uint64_t list_words) {
+  return sizeof(EmHdr) + (size_t)n_models * sizeof(EmRec) + (size_t)n_tables * NSGPU_EM_TABLE_SIZE * sizeof(double) +
+         (size_t)list_words * sizeof(uint32_t);
+}
+// ErrorModel::IsCorrupt on enabled model em - 1 for a frame of `size` bytes (PppHeader included: Receive has not
+// stripped it yet).  Out of line: the handlers of a scenario without a model never reach it.
+__device__ __noinline__ bool em_is_corrupt(DevRec *dev, uint32_t n_devices, uint32_t em, uint32_t size) {
+  const EmHdr *H = em_hdr(dev, n_devices);
+  EmRec *r = em_recs(dev, n_devices) + (em - 1);
+  const double *tabs = reinterpret_cast<const double *>(em_recs(dev, n_devices) + H->n_models);
+  bool corrupt;
+  if (r->kind == NSGPU_EM_RECEIVE_LIST) {
+    // ReceiveListErrorModel::DoCorrupt (error-model.cc:343-360): m_timesInvoked += 1; m_timesInvoked - 1 in the list.
+    // The list is sorted without duplicates and the ordinal goes up by one a call: the cursor's entry is the only
+    // candidate
+    const uint32_t *list = reinterpret_cast<const uint32_t *>(tabs + (size_t)H->n_tables * NSGPU_EM_TABLE_SIZE);
+    const uint32_t ord = r->invoked;
+    corrupt = r->cur < r->end && list[r->cur] == ord;
+    if (corrupt) r->cur++;
+  } else {
+    // RateErrorModel::DoCorrupt (:178-223): m_ranvar.GetValue () < m_rate (EU_PKT), < 1 - pow (1.0 - m_rate, size)
+    // (EU_BYTE), < 1 - pow (1.0 - m_rate, 8 * size) (EU_BIT); one U01 a frame at any rate.  (No frame is above
+    // MTU + PPP; the index is clamped to the table all the same.)
+    const double u = nsgpu_rng_u01(&r->g);
+    const uint32_t i = size < NSGPU_EM_TABLE_SIZE ? size : NSGPU_EM_TABLE_SIZE - 1;
+    const double x = r->tab == EM_NOTAB ? r->rate : tabs[(size_t)r->tab * NSGPU_EM_TABLE_SIZE + i];
+    corrupt = u < x;
+  }
+  r->invoked++;
+  if (corrupt) r->corrupted++;
+  return corrupt;
+}
+
 struct Emit {
   uint64_t now;
   uint32_t ctx;
@@ -1004,6 +1068,11 @@ __device__ __forceinline__ NodeOut node_part(const P2PDev &M, Emit &E, uint32_t 
   if (kind == K_RECEIVE) {  // PointToPointNetDevice::Receive -> Ipv4L3Protocol::Receive (ipv4-l3-protocol.cc:434-537)
     if (rx_atomic) atomicAdd(&M.dev[a].c.rx_packets, 1u);
     else M.dev[a].c.rx_packets++;
+    // m_receiveErrorModel->IsCorrupt (packet): m_phyRxDropTrace and nothing else (no sink hooks it)
+    if constexpr (PORTS) {
+      const uint32_t em = M.errm ? M.dev[a].em : 0u;
+      if (em && em_is_corrupt(M.dev, M.n_devices, em, pkt.size)) return NodeOut{act, post, cancelled, xdrop};
+    }
     Pkt p = pkt;
     p.size -= 2;                             // ProcessHeader strips the PppHeader
     trace_call(M, E, NSGPU_TR_RX, a, p);     // m_macRxTrace

@@ -1,6 +1,7 @@
-// nsgpu_p2p_ports.hip — the p2p subset's extended handler kernels, for scenarios with UDP ports or IPv4 fragmentation
-// (k2_handle<.., PORTS = true>: the per-flow endpoint lookup, UdpClient, UdpServer; fragments sent by the device
-// step, reassembly and its timeout; nsgpu_p2p_dev.h "UDP ports", "IPv4 fragmentation"), and PacketLossCounter on its own.
+// nsgpu_p2p_ports.hip — the p2p subset's extended handler kernels, for scenarios with UDP ports, IPv4 fragmentation
+// or receive error models (k2_handle<.., PORTS = true>: the per-flow endpoint lookup, UdpClient, UdpServer; fragments
+// sent by the device step, reassembly and its timeout; ReceiveListErrorModel and RateErrorModel; nsgpu_p2p_dev.h "UDP
+// ports", "IPv4 fragmentation", "receive error models"), and PacketLossCounter and RngStream on their own.
 // A translation unit of its own, and so a code object of its own: nsgpu_p2p.hip's holds exactly the kernels it held
 // before ports existed, so the engines of scenarios without ports run the same code at the same layout.  The window
 // header is compiled here for k2_handle alone (NSGPU_P2P_HANDLERS_ONLY): its other kernels stay nsgpu_p2p.hip's.
@@ -60,3 +61,32 @@ extern "C" int nsgpu_loss_counter_run(uint32_t window, const uint32_t *seq, uint
   return NSGPU_OK;
 }
 
+// RngStream::U01 of the stream_index-th stream: out[0 .. n).  on_device = 0 runs nsgpu_rng_u01 on the host, 1 in a
+// one-thread kernel (the function the handlers call); the initial state is the host's either way (nsgpu_rng_stream_init).
+__global__ void k_rng_stream(nsgpu_rng_stream g, uint64_t n, double *out) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  for (uint64_t k = 0; k < n; k++) out[k] = nsgpu_rng_u01(&g);
+}
+extern "C" int nsgpu_rng_stream_run(uint32_t seed, uint32_t run, uint32_t stream_index, uint64_t n, double *out,
+                                    int on_device, void *stream) {
+  if (n && !out) return set_error(NSGPU_EINVAL, "nsgpu_rng_stream_run: null");
+  nsgpu_rng_stream g;
+  if (!nsgpu_rng_stream_init(&g, seed, run, stream_index))
+    return set_error(NSGPU_EINVAL, "nsgpu_rng_stream_run: seed %u is not a seed RngStream::CheckSeed accepts (below "
+                     "4294944443)", seed);
+  if (!on_device) {
+    for (uint64_t k = 0; k < n; k++) out[k] = nsgpu_rng_u01(&g);
+    return NSGPU_OK;
+  }
+  if (!n) return NSGPU_OK;
+  hipStream_t s = (hipStream_t)stream;
+  double *d = nullptr;
+  NSGPU_HIP(hipMalloc((void **)&d, n * sizeof(double)));
+  hipLaunchKernelGGL(k_rng_stream, dim3(1), dim3(64), 0, s, g, n, d);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpyAsync(out, d, n * sizeof(double), hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  (void)hipFree(d);
+  if (e != hipSuccess) return set_error(NSGPU_EHIP, "nsgpu_rng_stream_run: %s", hipGetErrorString(e));
+  return NSGPU_OK;
+}

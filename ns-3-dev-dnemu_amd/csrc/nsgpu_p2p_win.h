@@ -1354,10 +1354,17 @@ __device__ __forceinline__ void handle_node2(const P2PDev &M, Ctl &C, uint32_t i
 
 // ---- k2_handle: hub blocks ----
 // Events whose node part touches no node state: TransmitComplete, and a Receive that IpForward
-// sends on (its node is not the datagram's destination).
-__device__ __forceinline__ bool stateless_event(const P2PDev &M, uint32_t c, uint32_t kind, const Pkt &p) {
+// sends on (its node is not the datagram's destination) — unless its device (a) has an enabled receive error model,
+// whose counter or RngStream advances in the device's arrival order (em_stateful).
+template <bool PORTS>
+__device__ __forceinline__ bool em_stateful(const P2PDev &M, uint32_t a) {
+  return PORTS && M.errm && M.dev[a].em != 0;
+}
+template <bool PORTS = false>
+__device__ __forceinline__ bool stateless_event(const P2PDev &M, uint32_t c, uint32_t kind, const Pkt &p, uint32_t a) {
   if (kind == K_TX_COMPLETE || kind == K_DEV_START) return true;  // (NetDevice::Start: no-op)
   if (kind != K_RECEIVE) return false;
+  if (em_stateful<PORTS>(M, a)) return false;
   if (M.icmp && (p.ttl & 0xffu) <= 1u) return false;  // a TTL expiry sends an ICMP error: m_identification++
   return pkt_dst_node(M, p) != c;
 }
@@ -1651,8 +1658,11 @@ __device__ __forceinline__ void hub_help(const P2PDev &M, Ctl &C, uint32_t i0, u
       }
       if (c < M.n_nodes && M.node_tab[(uint64_t)c * NTAB] > (uint32_t)CH) {
         mark = c;
-        const bool sl = kind == K_TX_COMPLETE || kind == K_DEV_START ||
-                        (kind == K_RECEIVE && !(M.icmp && (sp.pkt.ttl & 0xffu) <= 1u) && dn != c);
+        bool sl = kind == K_TX_COMPLETE || kind == K_DEV_START ||
+                  (kind == K_RECEIVE && !(M.icmp && (sp.pkt.ttl & 0xffu) <= 1u) && dn != c);
+        if constexpr (PORTS) {  // (a Receive on a device with a receive error model: the hub block's, in key order)
+          if (sl && kind == K_RECEIVE && em_stateful<PORTS>(M, sp.a)) sl = false;
+        }
         if (!sl) {
           ser = true;
           M.hx[i0].op = HOP_SER;
@@ -1915,6 +1925,9 @@ __device__ __forceinline__ void hub_node(const P2PDev &M, Ctl &C, uint32_t c, ui
         const uint32_t kind = kw_[u] & 0xffu;
         sl_[u] = j < n && (kind == K_TX_COMPLETE || kind == K_DEV_START ||
                            (kind == K_RECEIVE && !(M.icmp && (p_[u].ttl & 0xffu) <= 1u) && dn_[u] != c));
+        if constexpr (PORTS) {  // (a Receive on a device with a receive error model: lane 0's, in key order)
+          if (sl_[u] && kind == K_RECEIVE && em_stateful<PORTS>(M, a_[u])) sl_[u] = false;
+        }
         ser_[u] = __ballot(j < n && !sl_[u]);
       }
 #pragma unroll

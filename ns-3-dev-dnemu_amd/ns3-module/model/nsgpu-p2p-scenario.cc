@@ -8,6 +8,10 @@
 #include "ns3/point-to-point-channel.h"
 #include "ns3/loopback-net-device.h"
 #include "ns3/drop-tail-queue.h"
+#include "ns3/error-model.h"
+#include "ns3/pointer.h"
+#include "ns3/global-value.h"
+#include "ns3/integer.h"
 #include "ns3/ipv4.h"
 #include "ns3/ipv4-l3-protocol.h"
 #include "ns3/ipv4-list-routing.h"
@@ -50,6 +54,8 @@ NsgpuP2pScenario::NsgpuP2pScenario ()
     m_icmp (true),
     m_frag (false),
     m_fragTimeout (0),
+    m_rngSeed (0),
+    m_rngRun (0),
     m_stop (-1),
     m_firstLink (true),
     m_engine (0),
@@ -197,6 +203,58 @@ NsgpuP2pScenario::SetFragmentation (bool on, Time timeout)
 {
   m_frag = on;
   m_fragTimeout = timeout.GetTimeStep ();
+}
+
+void
+NsgpuP2pScenario::SetReceiveListErrorModel (uint32_t dev, const std::vector<uint32_t> &packets, bool enabled)
+{
+  if (dev >= m_dev.size ())
+    {
+      NS_FATAL_ERROR ("NsgpuP2pScenario::SetReceiveListErrorModel: no device " << dev);
+    }
+  Em none = {NSGPU_EM_NONE, 0, NSGPU_EU_BYTE, 0, 0.0, std::vector<uint32_t> ()};
+  m_em.resize (m_dev.size (), none);
+  Em e = {NSGPU_EM_RECEIVE_LIST, enabled ? 1u : 0u, NSGPU_EU_BYTE, 0, 0.0, packets};
+  m_em[dev] = e;
+}
+
+void
+NsgpuP2pScenario::SetRateErrorModel (uint32_t dev, double rate, uint32_t unit, uint32_t stream, bool enabled)
+{
+  if (dev >= m_dev.size ())
+    {
+      NS_FATAL_ERROR ("NsgpuP2pScenario::SetRateErrorModel: no device " << dev);
+    }
+  Em none = {NSGPU_EM_NONE, 0, NSGPU_EU_BYTE, 0, 0.0, std::vector<uint32_t> ()};
+  m_em.resize (m_dev.size (), none);
+  Em e = {NSGPU_EM_RATE, enabled ? 1u : 0u, unit, stream, rate, std::vector<uint32_t> ()};
+  m_em[dev] = e;
+}
+
+void
+NsgpuP2pScenario::SetRng (uint32_t seed, uint32_t run)
+{
+  m_rngSeed = seed;
+  m_rngRun = run;
+}
+
+void
+NsgpuP2pScenario::SetErrorStream (Ptr<NetDevice> device, uint32_t stream)
+{
+  m_errorStream.push_back (std::make_pair (device, stream));
+}
+
+void
+NsgpuP2pScenario::GetErrorModel (uint32_t dev, uint32_t &invoked, uint32_t &corrupted) const
+{
+  if (m_engine == 0 || dev >= m_dev.size ())
+    {
+      NS_FATAL_ERROR ("NsgpuP2pScenario::GetErrorModel: no engine or no device " << dev);
+    }
+  std::vector<nsgpu_error_model_record> rec (m_dev.size ());
+  NSGPU_TRY (nsgpu_p2p_error_models (m_engine, &rec[0], 0));
+  invoked = rec[dev].invoked;
+  corrupted = rec[dev].corrupted;
 }
 
 namespace {
@@ -403,6 +461,66 @@ NsgpuP2pScenario::FromNodeList (Ptr<HipSimulatorImpl> impl)
       Dev x = {devs[d]->GetNode ()->GetId (), devIndex[other], UintAttribute (q, "MaxPackets"), rate.Get ().GetBitRate (),
                TimeAttribute (p, "InterframeGap").GetTimeStep (), TimeAttribute (ch, "Delay").GetTimeStep ()};
       m_dev[d] = x;
+    }
+  // ---- the devices' ReceiveErrorModel attributes: mirrored, or fatal — never ignored ----
+  for (uint32_t d = 0; d < D; d++)
+    {
+      PointerValue emv;
+      devs[d]->GetAttribute ("ReceiveErrorModel", emv);
+      Ptr<ErrorModel> em = emv.Get<ErrorModel> ();
+      if (em == 0)
+        {
+          continue;
+        }
+      Ptr<ReceiveListErrorModel> rl = DynamicCast<ReceiveListErrorModel> (em);
+      Ptr<RateErrorModel> rt = DynamicCast<RateErrorModel> (em);
+      if (rl != 0)
+        {
+          const std::list<uint32_t> l = rl->GetList ();
+          SetReceiveListErrorModel (d, std::vector<uint32_t> (l.begin (), l.end ()), em->IsEnabled ());
+        }
+      else if (rt != 0)
+        {
+          bool named = false;
+          uint32_t stream = 0;
+          for (size_t i = 0; i < m_errorStream.size (); i++)
+            {
+              if (m_errorStream[i].first == devs[d])
+                {
+                  named = true;
+                  stream = m_errorStream[i].second;
+                }
+            }
+          if (!named)
+            {
+              NS_FATAL_ERROR ("NsgpuP2pScenario::FromNodeList: device " << d << " has a RateErrorModel whose "
+                              "RngStream was not named (SetErrorStream): the engine cannot discover the order in "
+                              "which the program constructs its streams");
+            }
+          // (a RanVar other than the default UniformVariable (0, 1) cannot be told apart here: DESIGN.md 6)
+          const enum ErrorUnit u = rt->GetUnit ();
+          SetRateErrorModel (d, rt->GetRate (), u == EU_PKT ? (uint32_t) NSGPU_EU_PKT
+                             : u == EU_BIT ? (uint32_t) NSGPU_EU_BIT : (uint32_t) NSGPU_EU_BYTE,
+                             stream, em->IsEnabled ());
+        }
+      else if (DynamicCast<ListErrorModel> (em) != 0)
+        {
+          NS_FATAL_ERROR ("NsgpuP2pScenario::FromNodeList: device " << d << " has a ListErrorModel, which selects "
+                          "by Packet::GetUid: the engine carries no packet uids");
+        }
+      else
+        {
+          NS_FATAL_ERROR ("NsgpuP2pScenario::FromNodeList: device " << d << " has a ReceiveErrorModel of type "
+                          << em->GetInstanceTypeId ().GetName () << ", which the engine does not model");
+        }
+    }
+  if (!m_em.empty ())
+    {
+      IntegerValue gv;
+      GlobalValue::GetValueByName ("RngSeed", gv);
+      m_rngSeed = gv.Get ();
+      GlobalValue::GetValueByName ("RngRun", gv);
+      m_rngRun = gv.Get ();
     }
   // ---- Ipv4: interface addresses and indices, DefaultTtl ----
   std::vector<uint32_t> ttl (N, 64);
@@ -666,6 +784,26 @@ NsgpuP2pScenario::Fill (void)
   sc.frag = m_frag ? 1u : 0u;
   sc.pad_frag_ = 0;
   sc.frag_timeout_ns = m_fragTimeout;
+  if (!m_em.empty ())
+    {
+      m_cEmKind.assign (D, 0), m_cEmEnabled.assign (D, 0), m_cEmUnit.assign (D, 0), m_cEmStream.assign (D, 0);
+      m_cEmRate.assign (D, 0.0), m_cEmOff.assign (D + 1, 0), m_cEmList.clear ();
+      for (size_t d = 0; d < D; d++)
+        {
+          if (d < m_em.size ())
+            {
+              m_cEmKind[d] = m_em[d].kind, m_cEmEnabled[d] = m_em[d].enabled, m_cEmUnit[d] = m_em[d].unit;
+              m_cEmStream[d] = m_em[d].stream, m_cEmRate[d] = m_em[d].rate;
+              m_cEmList.insert (m_cEmList.end (), m_em[d].list.begin (), m_em[d].list.end ());
+            }
+          m_cEmOff[d + 1] = m_cEmList.size ();
+        }
+      m_cEmList.push_back (0);  // (never empty: its address is taken)
+      sc.dev_em_kind = &m_cEmKind[0], sc.dev_em_enabled = &m_cEmEnabled[0], sc.dev_em_unit = &m_cEmUnit[0];
+      sc.dev_em_rate = &m_cEmRate[0], sc.dev_em_stream = &m_cEmStream[0];
+      sc.em_list_off = &m_cEmOff[0], sc.em_list = &m_cEmList[0];
+      sc.rng_seed = m_rngSeed, sc.rng_run = m_rngRun;
+    }
   sc.n_setup = m_setup.size ();
   sc.setup_kind = m_cSk.empty () ? 0 : &m_cSk[0];
   sc.setup_index = m_cSi.empty () ? 0 : &m_cSi[0];

@@ -69,6 +69,22 @@ public:
    * it on when an application's PacketSize needs it and reads the timeout from the nodes' Ipv4L3Protocol: one positive
    * value for all nodes (a timeout set here before must equal it; 0 is fatal, it would mean "default" to the engine). */
   void SetFragmentation (bool on, Time timeout = Time ());
+  /* PointToPointNetDevice::SetReceiveErrorModel on engine device `dev` (point-to-point-net-device.cc:304-317: a frame
+   * the model declares corrupt fires PhyRxDrop and nothing else).  ReceiveListErrorModel: the frames whose 0-based
+   * arrival ordinal at the device is in `packets`.  RateErrorModel: ErrorRate `rate`, ErrorUnit `unit`
+   * (NSGPU_EU_PKT / _BYTE / _BIT), and `stream`: the model's UniformVariable (0, 1) is the stream-th RngStream the
+   * program constructs (0-based) — the engine cannot discover that order, the caller names it.  A disabled model
+   * counts, draws and drops nothing.  Enable / Disable / Reset / SetList / SetRate during Run are not modelled. */
+  void SetReceiveListErrorModel (uint32_t dev, const std::vector<uint32_t> &packets, bool enabled = true);
+  void SetRateErrorModel (uint32_t dev, double rate, uint32_t unit, uint32_t stream, bool enabled = true);
+  /* RngSeed / RngRun of the Rate models' streams (0: the reference's default, 1); FromNodeList reads the GlobalValues */
+  void SetRng (uint32_t seed, uint32_t run);
+  /* FromNodeList mirrors a device's RateErrorModel only when its stream was named here before (the device is the
+   * program's own PointToPointNetDevice); without it FromNodeList ends in a fatal error */
+  void SetErrorStream (Ptr<NetDevice> device, uint32_t stream);
+  /* IsCorrupt calls on engine device `dev`'s enabled model and the frames it declared corrupt, as the engine counts
+   * them now */
+  void GetErrorModel (uint32_t dev, uint32_t &invoked, uint32_t &corrupted) const;
   /* Ipv4GlobalRoutingHelper::PopulateRoutingTables on the GPU (nsgpu_route_global): next hops towards every
    * flow destination and, with ICMP, every sender.  With every device addressed the ties are global
    * routing's (lowest peer address, then interface); an unaddressed topology takes the lowest device. */
@@ -86,8 +102,11 @@ public:
    * application bound to its destination port, a node may host several bound applications on distinct ports.  The setup list follows `impl`'s journal: per node, its first
    * zero-delay call is Node::Start, the next ones its devices' NetDevice::Start then its applications'
    * Application::Start (the helpers add devices before applications); the Stop event; every other call
-   * keeps its uid on the host (NSGPU_SETUP_UID).  Anything outside the GPU-resident subset (another device
-   * type, a random OnTime, two applications bound to one port of a node, ...) is a fatal error. */
+   * keeps its uid on the host (NSGPU_SETUP_UID).  A device's ReceiveErrorModel attribute is mirrored: a
+   * ReceiveListErrorModel (GetList, IsEnabled), a RateErrorModel (GetRate, GetUnit, IsEnabled) whose stream
+   * SetErrorStream named, RngSeed / RngRun from the GlobalValues.  Anything outside the GPU-resident subset (another
+   * device type, a random OnTime, two applications bound to one port of a node, a ListErrorModel or any other
+   * ErrorModel subclass, a RateErrorModel without a named stream, ...) is a fatal error. */
   void FromNodeList (Ptr<HipSimulatorImpl> impl);
   /* The journal entries the engine dispatches from now on (FromNodeList) */
   const std::vector<uint32_t> &GetOwnedSetupCalls (void) const { return m_owned; }
@@ -124,6 +143,12 @@ private:
     uint32_t port;         // bound port of a PacketSink / UdpEchoServer / UdpServer
     uint32_t window;       // UdpServer PacketWindowSize
   };
+  struct Em
+  {
+    uint32_t kind, enabled, unit, stream;  // NSGPU_EM_*, IsEnabled (), NSGPU_EU_*, the RngStream's index
+    double rate;
+    std::vector<uint32_t> list;
+  };
   uint32_t AddApp (const App &a);
   /* the engine's view (kept alive for the trace codec) */
   void Fill (void);
@@ -138,10 +163,13 @@ private:
   std::vector<uint32_t> m_nif;                          // next interface index per node
   std::vector<uint32_t> m_owned;                        // FromNodeList: the journal entries the engine owns
   std::vector<Ptr<NetDevice> > m_devObj;                // FromNodeList: the ns-3 device of each engine device
+  std::vector<Em> m_em;                                 // per device (empty: no device has a receive error model)
+  std::vector<std::pair<Ptr<NetDevice>, uint32_t> > m_errorStream;  // SetErrorStream
   uint32_t m_nDst;
   bool m_icmp;
   bool m_frag;
   int64_t m_fragTimeout;                                // FragmentExpirationTimeout (ns; 0: the default)
+  uint32_t m_rngSeed, m_rngRun;                         // RngSeed / RngRun of the Rate error models' streams (0: 1)
   int64_t m_stop;
   bool m_firstLink;
   nsgpu_p2p *m_engine;
@@ -149,8 +177,10 @@ private:
   // the C view (Fill)
   nsgpu_p2p_scenario m_sc;
   std::vector<uint32_t> m_cDevNode, m_cDevPeer, m_cDevQmax, m_cKind, m_cNode, m_cDst, m_cSlot, m_cSrc, m_cSize,
-    m_cMaxb, m_cTtl, m_cCount, m_cSk, m_cSi, m_cRaddr, m_cRport, m_cPort, m_cWindow;
-  std::vector<uint64_t> m_cDevBps, m_cRate;
+    m_cMaxb, m_cTtl, m_cCount, m_cSk, m_cSi, m_cRaddr, m_cRport, m_cPort, m_cWindow, m_cEmKind, m_cEmEnabled,
+    m_cEmUnit, m_cEmStream, m_cEmList;
+  std::vector<uint64_t> m_cDevBps, m_cRate, m_cEmOff;
+  std::vector<double> m_cEmRate;
   std::vector<int64_t> m_cDevIfg, m_cDevDelay, m_cStart, m_cStop, m_cIvl;
   std::vector<double> m_cOn, m_cOff;
 };

@@ -49,6 +49,9 @@ class ScenarioStruct(C.Structure):
         ("route_exc_dev", C.c_void_p), ("uid_first", C.c_uint32), ("pad_uid_", C.c_uint32),
         ("app_port", C.c_void_p), ("app_remote_port", C.c_void_p), ("app_loss_window", C.c_void_p),
         ("frag", C.c_uint32), ("pad_frag_", C.c_uint32), ("frag_timeout_ns", C.c_int64),
+        ("dev_em_kind", C.c_void_p), ("dev_em_enabled", C.c_void_p), ("dev_em_unit", C.c_void_p),
+        ("dev_em_rate", C.c_void_p), ("dev_em_stream", C.c_void_p), ("em_list_off", C.c_void_p),
+        ("em_list", C.c_void_p), ("rng_seed", C.c_uint32), ("rng_run", C.c_uint32),
     ]
 
 
@@ -69,12 +72,21 @@ UDP_SERVER_DTYPE = np.dtype([("received", "<u4"), ("lost", "<u4"), ("last_max_se
 # nsgpu_frag_stats: the IPv4 fragmentation counters of a run (Scenario (frag=True))
 FRAG_STATS_FIELDS = ("fragmented", "fragments_sent", "reassembled", "timeouts", "cancelled_timers", "max_list")
 FRAG_CAP = 128  # entries of a node's reassembly list (a run that would pass it fails)
+# receive error models (nsgpu_p2p_scenario.dev_em_kind): NSGPU_EM_*, NSGPU_EU_*, nsgpu_error_model_record
+EM_NONE, EM_RECEIVE_LIST, EM_RATE, EM_LIST = 0, 1, 2, 3
+EM_UNITS = {"pkt": 0, "byte": 1, "bit": 2}
+EM_MAX_TABLES, EM_TABLE_SIZE = 16, 1503
+ERROR_MODEL_DTYPE = np.dtype([("invoked", "<u4"), ("corrupted", "<u4")])
 
 
 class Scenario:
     """Arrays of a nsgpu_p2p_scenario plus the order of setup-time Schedule calls."""
 
-    def __init__(self, n_nodes, icmp=False, ports=False, frag=False, frag_timeout_ns=0):
+    def __init__(self, n_nodes, icmp=False, ports=False, frag=False, frag_timeout_ns=0, rng_seed=0, rng_run=0):
+        # receive error models (PointToPointNetDevice::SetReceiveErrorModel): device -> dict (kind "list" / "rate",
+        # enabled, packets | rate, unit, stream); RngSeed / RngRun of the Rate models' streams (0: the default, 1)
+        self.error_models = {}
+        self.rng_seed, self.rng_run = rng_seed, rng_run
         # IPv4 fragmentation and reassembly on the device (nsgpu_p2p_scenario.frag): payloads up to 65507 bytes;
         # frag_timeout_ns = Ipv4L3Protocol::FragmentExpirationTimeout (0: the reference's 30 s)
         self.frag = frag
@@ -173,6 +185,23 @@ class Scenario:
             # Ipv4L3Protocol::AddInterface: the loopback is interface 0 (SetupLoopback at Install)
             self.dev_ifindex[d] = self._nif.get(node, 1)
             self._nif[node] = self.dev_ifindex[d] + 1
+
+    def set_receive_list_error_model(self, dev, packets, enabled=True):
+        """ReceiveListErrorModel on device `dev`: the frames whose 0-based arrival ordinal is in `packets` (any order,
+        duplicates allowed) are corrupt."""
+        self.error_models[dev] = dict(kind="list", packets=[int(x) for x in packets], enabled=bool(enabled))
+
+    def set_rate_error_model(self, dev, rate, unit="byte", stream=0, enabled=True):
+        """RateErrorModel on device `dev` with ErrorRate `rate` and ErrorUnit `unit` ("byte", the default, "pkt" or
+        "bit"); its UniformVariable (0, 1) is the `stream`-th RngStream the program constructs (0-based)."""
+        if unit not in EM_UNITS:
+            raise ValueError("unit: 'byte', 'pkt' or 'bit'")
+        self.error_models[dev] = dict(kind="rate", rate=float(rate), unit=unit, stream=int(stream),
+                                      enabled=bool(enabled))
+
+    def set_list_error_model(self, dev, uids, enabled=True):
+        """ListErrorModel selects by Packet::GetUid, which the engine does not carry: always refused."""
+        raise NotImplementedError("ListErrorModel (by Packet::GetUid) is not modelled: the engine carries no packet uids")
 
     def _slot_nodes(self):
         # route-table columns: every datagram destination (sender apps' dst), echo clients' own nodes, and
@@ -309,6 +338,30 @@ class Scenario:
         s.uid_first = self.uid_first
         s.frag = 1 if self.frag else 0
         s.frag_timeout_ns = self.frag_timeout_ns
+        if self.error_models:
+            nd = len(self.dev)
+            kind, enabled, unit, stream = (np.zeros(max(nd, 1), np.uint32) for _ in range(4))
+            rate = np.zeros(max(nd, 1), np.float64)
+            off = np.zeros(nd + 1, np.uint64)
+            lists = []
+            for d in range(nd):
+                e = self.error_models.get(d)
+                if e is not None:
+                    enabled[d] = 1 if e["enabled"] else 0
+                    if e["kind"] == "list":
+                        kind[d] = EM_RECEIVE_LIST
+                        lists.extend(e["packets"])
+                    else:
+                        kind[d], unit[d], stream[d], rate[d] = EM_RATE, EM_UNITS[e["unit"]], e["stream"], e["rate"]
+                off[d + 1] = len(lists)
+            if any(d >= nd for d in self.error_models):
+                raise ValueError("error model on a device that does not exist")
+            em = dict(dev_em_kind=kind, dev_em_enabled=enabled, dev_em_unit=unit, dev_em_rate=rate,
+                      dev_em_stream=stream, em_list_off=off, em_list=np.array(lists or [0], np.uint32))
+            for k, v in em.items():
+                setattr(s, k, v.ctypes.data)
+            arrays.update(em)
+        s.rng_seed, s.rng_run = self.rng_seed, self.rng_run
         s._keep = arrays  # keep the arrays alive with the struct
         return s
 
@@ -620,6 +673,13 @@ class Engine:
         nsgpu.check(nsgpu.lib().nsgpu_p2p_frag_stats(self.h, out.ctypes.data, self.stream))
         return {k: int(v) for k, v in zip(FRAG_STATS_FIELDS, out)}
 
+    def error_models(self):
+        """Per device, the IsCorrupt calls on its enabled receive error model and the frames it declared corrupt
+        (nsgpu_p2p_error_models: ERROR_MODEL_DTYPE; zeros without an enabled model)."""
+        out = np.zeros(self.s.n_devices, ERROR_MODEL_DTYPE)
+        nsgpu.check(nsgpu.lib().nsgpu_p2p_error_models(self.h, out.ctypes.data, self.stream))
+        return out
+
     def results(self, log_n=0):
         st = P2PStats()
         devc = np.zeros(self.s.n_devices, DEV_COUNTERS_DTYPE)
@@ -841,6 +901,16 @@ class LoopbackGroup:
         per = [m.frag_stats() for m in self.members]
         return {k: (max if k == "max_list" else sum)(p[k] for p in per) for k in FRAG_STATS_FIELDS}
 
+    def error_models(self):
+        """Every device's error-model record from the rank owning its node (the model's state lives there)."""
+        per = [m.error_models() for m in self.members]
+        dev_node = self.members[0].s._keep["dev_node"]
+        out = per[0].copy()
+        for r, rec in enumerate(per):
+            m = self.owner[dev_node] == r
+            out[m] = rec[m]
+        return out
+
     def run(self, log_n=0):
         self.reset()
         self.launch()
@@ -851,6 +921,21 @@ class LoopbackGroup:
             nsgpu.lib().nsgpu_p2p_group_destroy(self.h)
         except Exception:
             pass
+
+
+def rng_stream(seed, run, stream, n, on_device=False, hip_stream=None):
+    """The first n RngStream::U01 values of the `stream`-th (0-based) RngStream of a program with RngSeed `seed` and
+    RngRun `run` (nsgpu_rng_stream_run): on the host, or in a one-thread kernel by the function the handlers call."""
+    out = np.zeros(n, np.float64)
+    nsgpu.check(nsgpu.lib().nsgpu_rng_stream_run(seed, run, stream, n, out.ctypes.data, int(on_device), hip_stream))
+    return out
+
+
+def error_model_thresholds(unit, rate):
+    """The threshold table create builds for an EU_BYTE / EU_BIT Rate model (nsgpu_error_model_thresholds)."""
+    out = np.zeros(EM_TABLE_SIZE, np.float64)
+    nsgpu.check(nsgpu.lib().nsgpu_error_model_thresholds(EM_UNITS[unit], float(rate), out.ctypes.data))
+    return out
 
 
 class TraceAddressing(C.Structure):
