@@ -9,12 +9,11 @@ import frag_cases as F
 import nsgpu
 import p2p
 import p2p_frag_pyref
-import trace
+from p2p_model_compare import assert_equals_frag_model as assert_equals_model
 
 pytestmark = pytest.mark.gpu
 
 ALL_KINDS = p2p.TRACE_DEVICE_KINDS | p2p.TRACE_IPV4_KINDS
-TRACE_FIELDS = ("ts", "uid", "seq", "kind", "dev", "app", "ipid", "size", "ttl")
 _models = {}
 
 
@@ -24,23 +23,6 @@ def model(name, *args):
         sc = getattr(F, name)(*args)
         _models[(name, args)] = (sc, p2p_frag_pyref.run(sc, ALL_KINDS))
     return _models[(name, args)]
-
-
-def assert_equals_model(m, st, devc, appc, log, servers, frag, tr=None):
-    for k, v in m["stats"].items():
-        assert int(getattr(st, k)) == v, k
-    for name, a, b in zip(("ts", "uid", "ctx"), log, m["log"]):
-        assert np.array_equal(a, b), "log " + name
-    assert np.array_equal(devc, m["devc"])
-    assert np.array_equal(appc, m["appc"])
-    for f in ("received", "lost", "last_max_seq"):
-        assert np.array_equal(servers[f], m["servers"][f]), f
-    assert frag == m["frag"]
-    if tr is not None:
-        tr, want = trace.sort_records(tr), trace.sort_records(m["trace"])
-        assert len(tr) == len(want)
-        for f in TRACE_FIELDS:
-            assert np.array_equal(tr[f], want[f]), "trace " + f
 
 
 def run_traced(sc, m):
