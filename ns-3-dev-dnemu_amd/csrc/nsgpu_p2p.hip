@@ -124,6 +124,13 @@ int dupload(nsgpu_p2p *h, const T **dst, const T *src, size_t n) {
   *dst = p;
   return NSGPU_OK;
 }
+// The device-resident copy of the engine descriptor the handlers' out-of-line code reads (nsgpu_p2p_dev.h "cold
+// paths"): written when create has filled h->M, and again by every call that changes a field of it afterwards
+// (nsgpu_p2p_set_trace, nsgpu_p2p_set_trace_kinds).  The copy is done when this returns; no run is in flight then.
+int mdev_sync(nsgpu_p2p *h) {
+  NSGPU_HIP(hipMemcpy(reinterpret_cast<char *>(h->M.C) + CTL_MDEV_OFF, &h->M, sizeof(P2PDev), hipMemcpyHostToDevice));
+  return NSGPU_OK;
+}
 }  // namespace
 
 #define TRY(x)            \
@@ -878,7 +885,7 @@ static int create_engine(const nsgpu_p2p_scenario *sc, const uint32_t *owner, in
   }
   {  // the run control, and behind it the deferred pipeline's partial records (Part), empty
     uint8_t *cb;
-    TRY(dalloc(h, &cb, CTL_PARTS_OFF + (size_t)NPARTS * PART_LINE));
+    TRY(dalloc(h, &cb, CTL_MDEV_OFF + sizeof(P2PDev)));  // (... and behind those the descriptor's copy: mdev_sync)
     M.C = reinterpret_cast<Ctl *>(cb);
     hipLaunchKernelGGL(k_part_clear, dim3((NPARTS + 255) / 256), dim3(256), 0, nullptr, M.C);
     NSGPU_HIP(hipGetLastError());
@@ -943,6 +950,10 @@ static int create_engine(const nsgpu_p2p_scenario *sc, const uint32_t *owner, in
     h->snap = nullptr;
     nsgpu_p2p_destroy(h);
     return set_error(NSGPU_ENOMEM, "nsgpu_p2p_create: hipHostMalloc failed");
+  }
+  if (const int rc = mdev_sync(h)) {
+    nsgpu_p2p_destroy(h);
+    return rc;
   }
   *out = h;
   return NSGPU_OK;
@@ -1783,6 +1794,10 @@ extern "C" int nsgpu_p2p_phase_read(uint64_t *out, int n, int reset) {
     NSGPU_HIP(hipMemcpyFromSymbol(out + 64, HIP_SYMBOL(g_blk), nb * sizeof(uint64_t)));
     const int ng = std::min(n - 64 - 3 * BLK_MAX * 2, GT_BLK_MAX * 8);  // (then k_gtile's stamps)
     if (ng > 0) NSGPU_HIP(hipMemcpyFromSymbol(out + 64 + 3 * BLK_MAX * 2, HIP_SYMBOL(g_gt), ng * sizeof(uint64_t)));
+    // (then the holder blocks' kind counts: BLKK_MAX x BLKK_N 32-bit words, two to an output word)
+    const int nk = std::min(n - 64 - 3 * BLK_MAX * 2 - GT_BLK_MAX * 8, BLKK_MAX * BLKK_N / 2);
+    if (nk > 0)
+      NSGPU_HIP(hipMemcpyFromSymbol(out + 64 + 3 * BLK_MAX * 2 + GT_BLK_MAX * 8, HIP_SYMBOL(g_blkk), nk * sizeof(uint64_t)));
     n = 64;
   }
   NSGPU_HIP(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_phase), n * sizeof(uint64_t)));
@@ -1795,6 +1810,7 @@ extern "C" int nsgpu_p2p_phase_read(uint64_t *out, int n, int reset) {
     NSGPU_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_blk_win), &w, sizeof(w)));
     std::vector<uint64_t> zb(3 * BLK_MAX * 2, 0);
     NSGPU_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_blk), zb.data(), zb.size() * sizeof(uint64_t)));
+    NSGPU_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_blkk), zb.data(), sizeof(uint32_t) * BLKK_MAX * BLKK_N));
   }
   return NSGPU_OK;
 #else
@@ -1820,6 +1836,7 @@ extern "C" int nsgpu_p2p_set_trace(nsgpu_p2p *h, uint64_t cap) {
                                  //  uids would need the single engine's patch pass)
   NSGPU_HIP(hipMemset(h->M.trace_n, 0, sizeof(unsigned long long)));
   h->M.trace_cap = cap;
+  if (const int rc2 = mdev_sync(h)) return rc2;
   if (h->gexec) {
     (void)hipGraphExecDestroy(h->gexec);
     h->gexec = nullptr;
@@ -1841,6 +1858,7 @@ extern "C" int nsgpu_p2p_set_trace_kinds(nsgpu_p2p *h, uint32_t mask) {
   if (!h) return set_error(NSGPU_EINVAL, "nsgpu_p2p_set_trace_kinds: null");
   if (mask & ~0x7fu) return set_error(NSGPU_EINVAL, "nsgpu_p2p_set_trace_kinds: unknown kind bits 0x%x", mask);
   h->M.trace_kinds = mask;
+  if (const int rc = mdev_sync(h)) return rc;
   for (hipGraphExec_t *g : {&h->gexec, &h->gexec_df, &h->gtail[0], &h->gtail[1]})
     if (*g) {
       (void)hipGraphExecDestroy(*g);

@@ -381,6 +381,31 @@ struct P2PDev {
   uint32_t *rn_ctx, *rn_kind, *rn_a, *rn_src;
   Pkt *rn_pkt;
 };
+// ---- cold paths ----
+// The handlers' rare code (the application kinds, the Sends, ICMP, a missing route, trace records, ...) is not
+// inlined into k2_handle: inlined, it kept about 130 fields of the by-value kernel argument live across the holders'
+// event loop, and every pointer the hot path used came back through two v_readlane of a spilled SGPR.  The
+// out-of-line functions do not take a reference to the kernel argument (that made the compiler copy it into
+// scratch: see hub_slot); they read a device-resident copy of it, which lies in the run control's allocation behind
+// the partial records, so that P2PDev takes no pointer to it.  The host writes the copy at create and again
+// whenever it changes a field of its descriptor afterwards (nsgpu_p2p.hip: mdev_sync).
+constexpr size_t CTL_MDEV_OFF = 128 * 1024;  // (past the partial records: nsgpu_p2p_win.h asserts it)
+__device__ __forceinline__ const P2PDev *mdev_of(const Ctl *C) {
+  return reinterpret_cast<const P2PDev *>(reinterpret_cast<const char *>(C) + CTL_MDEV_OFF);
+}
+// The copy as an out-of-line function reads it.  The pointer arrives in vector registers like every argument, but it is
+// the same in every lane and the copy does not change while a kernel runs: made a scalar value in the constant address
+// space, its fields are read with scalar loads through the scalar cache, as the kernel argument's are, not with a
+// vector memory trip in front of every first use.
+__device__ __forceinline__ const P2PDev &mdev_ref(const P2PDev *G) {
+  typedef __attribute__((address_space(4))) const P2PDev CDev;
+  const uint64_t v = reinterpret_cast<uint64_t>(G);
+  // (the builtin returns int: each half goes through uint32_t, or a low half with bit 31 set would sign-extend)
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));
+  const uint64_t u = ((uint64_t)hi << 32) | (uint64_t)lo;
+  return *(const P2PDev *)(CDev *)u;
+}
 
 // ---------------- wave / block helpers (the wave reductions, scans and DPP moves: nsgpu_wave.h) ----------------
 // Block exclusive scan of one value per thread (NTH threads); *total = block sum.
@@ -677,6 +702,22 @@ struct Emit {
       }
     }
   }
+  // An out-of-line node part (node_part_cold) made this event's children [n, n1) through an Emit of its own: the
+  // same fold of their records into the minima as child()'s (a node part makes no TransmitComplete: none is local).
+  __device__ __forceinline__ void adopt(uint32_t n1) {
+    for (; n < n1; n++) {
+      const uint32_t kind = ch_kind[slot0 + n];
+      if ((kind & 0xffu) == K_FWD_UP || (kind & LOCALBIT)) continue;
+      const uint64_t ts = ch_ts[slot0 + n];
+      tmn = ts < tmn ? ts : tmn;
+      const uint64_t e = ts + (uint64_t)lookahead[kind & 0xffu];
+      wnd = e < wnd ? e : wnd;
+      if (lookw) {
+        const uint64_t ew = ts + (uint64_t)lookw[kind & 0xffu];
+        wndw = ew < wndw ? ew : wndw;
+      }
+    }
+  }
 };
 
 // Run statistics of one handler thread.
@@ -698,22 +739,28 @@ enum : uint32_t { ACT_NONE = 0, ACT_SEND = 1, ACT_KICK = 2 };
 // One ascii trace sink call (AsciiTraceHelper::Default*SinkWithContext, trace-helper.cc:303-390, as
 // hooked by PointToPointHelper::EnableAsciiInternal, point-to-point-helper.cc:113-219): appended
 // unordered; the host orders the records by (ts, uid, seq).
-__device__ __forceinline__ void trace_call(const P2PDev &M, Emit &E, uint32_t kind, uint32_t d, const Pkt &p) {
-  if (!M.trace || !((M.trace_kinds >> kind) & 1u)) return;
+// The record itself is written out of line (cold paths, above): an untraced engine's handlers hold only the test.
+__device__ __noinline__ void trace_append(const P2PDev *G, uint64_t now, uint32_t uid, uint32_t seq, uint32_t kind,
+                                          uint32_t tloc, uint32_t d, Pkt p) {
   nsgpu_trace_record r;
-  r.ts = E.now;
-  r.uid = E.uid;
-  r.seq = (uint16_t)E.trseq++;
+  r.ts = now;
+  r.uid = uid;
+  r.seq = (uint16_t)seq;
   r.kind = (uint8_t)kind;
-  r.pad_ = E.tloc ? 1 : 0;  // (k_tpatch replaces a local record's index by its uid and clears the flag)
+  r.pad_ = tloc ? 1 : 0;  // (k_tpatch replaces a local record's index by its uid and clears the flag)
   r.dev = d;
   r.app = p.app;
   r.ipid = p.ipid;
   r.size = p.size;
   r.ttl = p.ttl;
   r.pad2_ = 0;
+  const P2PDev &M = mdev_ref(G);
   const unsigned long long i = atomicAdd(M.trace_n, 1ull);
   if (i < M.trace_cap) M.trace[i] = r;
+}
+__device__ __forceinline__ void trace_call(const P2PDev &M, Emit &E, uint32_t kind, uint32_t d, const Pkt &p) {
+  if (!M.trace || !((M.trace_kinds >> kind) & 1u)) return;
+  trace_append(mdev_of(M.C), E.now, E.uid, E.trseq++, kind, E.tloc ? 1u : 0u, d, p);
 }
 struct Act {
   uint32_t op, dev;
@@ -1003,11 +1050,10 @@ __device__ __forceinline__ Pkt icmp_error(const Pkt &p, bool unreach) {
 }
 
 // Ipv4 route lookup: the static next-hop device of node n towards route-table slot `slot`.
-__device__ __forceinline__ uint32_t route_at(const P2PDev &M, uint32_t n, uint32_t slot) {
-  if (slot == 0xffffffffu) return 0xffffffffu;
-  if (M.route) return M.route[(uint64_t)n * M.n_dst + slot];
-  // compressed: binary search of the node's exceptions (a dumbbell router holds one per leaf); a node
-  // with an exception for every slot has them at their slot's position (ascending, distinct)
+// The compressed table (out of line: cold paths): binary search of the node's exceptions (a dumbbell router holds
+// one per leaf); a node with an exception for every slot has them at their slot's position (ascending, distinct).
+__device__ __noinline__ uint32_t route_compressed(const P2PDev *G, uint32_t n, uint32_t slot) {
+  const P2PDev &M = mdev_ref(G);
   const uint64_t e1 = M.route_exc_off[n + 1];
   uint64_t lo = M.route_exc_off[n], hi = e1;
   if (hi - lo == M.n_dst) return M.route_exc_dev[lo + slot];
@@ -1017,6 +1063,11 @@ __device__ __forceinline__ uint32_t route_at(const P2PDev &M, uint32_t n, uint32
     else hi = mid;
   }
   return (lo < e1 && M.route_exc_slot[lo] == slot) ? M.route_exc_dev[lo] : M.route_def[n];
+}
+__device__ __forceinline__ uint32_t route_at(const P2PDev &M, uint32_t n, uint32_t slot) {
+  if (slot == 0xffffffffu) return 0xffffffffu;
+  if (M.route) return M.route[(uint64_t)n * M.n_dst + slot];
+  return route_compressed(mdev_of(M.C), n, slot);
 }
 // ... towards the packet's destination.
 __device__ __forceinline__ uint32_t route_of(const P2PDev &M, uint32_t n, const Pkt &p) {
@@ -1053,10 +1104,13 @@ struct DstHint {
 };
 // rx_atomic: the device's rx counter is added with an atomic (hub blocks: other lanes add to it too;
 // holders: a no-return atomic, so the event does not wait for the counter's line).
+// The whole node part, every kind.  It is compiled once per translation unit, inside node_part_cold (out of line);
+// the handlers inline node_part below, which runs the common kinds itself.  resumed: the event is a Receive whose
+// first steps (the rx counter, the error model, the two Rx trace calls) node_part has already taken.
 template <bool PORTS = false>
-__device__ __forceinline__ NodeOut node_part(const P2PDev &M, Emit &E, uint32_t kind_word, uint32_t a,
-                                             const Pkt &pkt, int32_t sink, HStat &hs, bool rx_atomic = false,
-                                             DstHint hint = DstHint{false, 0, 0}) {
+__device__ __forceinline__ NodeOut node_part_full(const P2PDev &M, Emit &E, uint32_t kind_word, uint32_t a,
+                                                  const Pkt &pkt, int32_t sink, HStat &hs, bool rx_atomic, bool resumed,
+                                                  DstHint hint = DstHint{false, 0, 0}) {
   const uint32_t kind = kind_word & 0xffu;
   const uint32_t gen = kind_word >> 8;
   Act act{ACT_NONE, 0, Pkt{0, 0, 0, 0}};
@@ -1066,17 +1120,19 @@ __device__ __forceinline__ NodeOut node_part(const P2PDev &M, Emit &E, uint32_t 
   // (a frag scenario's senders write the header's 16-bit identification: the upper half is the fragment's)
   const uint32_t idm = (PORTS && M.frag) ? 0xffffu : 0xffffffffu;
   if (kind == K_RECEIVE) {  // PointToPointNetDevice::Receive -> Ipv4L3Protocol::Receive (ipv4-l3-protocol.cc:434-537)
-    if (rx_atomic) atomicAdd(&M.dev[a].c.rx_packets, 1u);
-    else M.dev[a].c.rx_packets++;
-    // m_receiveErrorModel->IsCorrupt (packet): m_phyRxDropTrace and nothing else (no sink hooks it)
-    if constexpr (PORTS) {
-      const uint32_t em = M.errm ? M.dev[a].em : 0u;
-      if (em && em_is_corrupt(M.dev, M.n_devices, em, pkt.size)) return NodeOut{act, post, cancelled, xdrop};
-    }
     Pkt p = pkt;
-    p.size -= 2;                             // ProcessHeader strips the PppHeader
-    trace_call(M, E, NSGPU_TR_RX, a, p);     // m_macRxTrace
-    trace_call(M, E, NSGPU_TR_IP_RX, a, p);  // Ipv4L3Protocol::Receive: m_rxTrace (:455)
+    p.size -= 2;  // ProcessHeader strips the PppHeader
+    if (!resumed) {
+      if (rx_atomic) atomicAdd(&M.dev[a].c.rx_packets, 1u);
+      else M.dev[a].c.rx_packets++;
+      // m_receiveErrorModel->IsCorrupt (packet): m_phyRxDropTrace and nothing else (no sink hooks it)
+      if constexpr (PORTS) {
+        const uint32_t em = M.errm ? M.dev[a].em : 0u;
+        if (em && em_is_corrupt(M.dev, M.n_devices, em, pkt.size)) return NodeOut{act, post, cancelled, xdrop};
+      }
+      trace_call(M, E, NSGPU_TR_RX, a, p);     // m_macRxTrace
+      trace_call(M, E, NSGPU_TR_IP_RX, a, p);  // Ipv4L3Protocol::Receive: m_rxTrace (:455)
+    }
     // the receiving node: the context ScheduleWithContext gave the Receive (point-to-point-channel.cc:100)
     const uint32_t n = E.ctx < M.n_nodes ? E.ctx : M.dev_node[a];
     const bool reply = (p.app & NSGPU_PKT_REPLY) != 0;
@@ -1320,6 +1376,111 @@ __device__ __forceinline__ NodeOut node_part(const P2PDev &M, Emit &E, uint32_t 
   }
   return NodeOut{act, post, cancelled, xdrop};
 }
+// What node_part_cold hands back, in registers (a function's result travels in at most 16, and a reference to the
+// caller's Emit would keep that in scratch): the NodeOut (the trailing child as in HubEv: pkind == 0, none), the
+// event's children and trace calls so far, and what the event added to the HStat, four bits a counter.
+struct ColdOut {
+  uint32_t op, dev;
+  Pkt p;
+  int64_t pdelay;
+  uint32_t pkind, pa;
+  uint32_t xdrop, n, trseq;
+  uint32_t stat;  // ttl_drops | no_route << 4 | unreach << 8 | icmp << 12 | stop << 16 | cancelled << 17
+};
+static_assert(sizeof(ColdOut) <= 64, "ColdOut is returned in registers");
+enum : uint32_t { CF_TLOC = 1, CF_DEMOTE = 2, CF_RX_ATOMIC = 4, CF_RESUMED = 8 };
+// The node part of an event node_part does not run itself, out of line and against the device-resident descriptor G
+// (cold paths, above).  The event's Emit is rebuilt from its scalars; the children are written where the caller's
+// would write them, and the caller folds them into its minima (Emit::adopt).
+template <bool PORTS>
+__device__ __noinline__ ColdOut node_part_cold(const P2PDev *G, uint64_t now, uint32_t ctx, uint32_t slot0, uint32_t n,
+                                               uint32_t uid, uint32_t trseq, uint32_t flags, uint32_t kind_word,
+                                               uint32_t a, Pkt pkt, int32_t sink) {
+  const P2PDev &M = mdev_ref(G);
+  Emit E;
+  E.now = now;
+  E.ctx = ctx;
+  E.slot0 = slot0;
+  E.n = n;
+  E.ch_ts = M.ch_ts;
+  E.ch_ctx = M.ch_ctx;
+  E.ch_kind = M.ch_kind;
+  E.ch_a = M.ch_a;
+  E.ch_pkt = M.ch_pkt;
+  E.lookahead = M.lookahead;
+  E.lookw = nullptr;
+  E.tmn = E.wnd = E.wndw = ~0ull;
+  E.lim_abs = 0;
+  E.uid = uid;
+  E.tloc = (flags & CF_TLOC) != 0;
+  E.trseq = trseq;
+  E.demote = (flags & CF_DEMOTE) != 0;
+  E.lj = -1;
+  HStat hs{0, 0, 0, 0, 0, false};
+  const NodeOut o = node_part_full<PORTS>(M, E, kind_word, a, pkt, sink, hs, (flags & CF_RX_ATOMIC) != 0,
+                                          (flags & CF_RESUMED) != 0);
+  return ColdOut{o.act.op, o.act.dev, o.act.p, o.post.delay, o.post.valid ? o.post.kind : 0u, o.post.a, o.xdrop, E.n,
+                 E.trseq, hs.ttl_drops | (hs.no_route << 4) | (hs.unreach << 8) | (hs.icmp << 12) |
+                              ((hs.stop ? 1u : 0u) << 16) | ((o.cancelled ? 1u : 0u) << 17)};
+}
+// The node part as the handlers inline it: a TransmitComplete, and a Receive that is forwarded (route found, TTL
+// alive) or delivered to the node's bound PacketSink, run here; every other kind, and a Receive that ends any other
+// way (no route, TTL expiry, no endpoint, an echo application, an ICMP error, a fragment), goes to node_part_cold.
+// The order of an event's side effects is node_part_full's: a Receive's first steps are the same statements, and the
+// cold function continues after them (CF_RESUMED).
+// SPLIT = false (the narrow kernel's holders and hub blocks): the whole node part inline, as before.  The dumbbell,
+// which runs that kernel and whose events are one quarter Sends and application starts, lost 0.6-1.3 % with the split
+// (DESIGN.md 4.4, r15).
+template <bool PORTS = false, bool SPLIT = true>
+__device__ __forceinline__ NodeOut node_part(const P2PDev &M, Emit &E, uint32_t kind_word, uint32_t a,
+                                             const Pkt &pkt, int32_t sink, HStat &hs, bool rx_atomic = false,
+                                             DstHint hint = DstHint{false, 0, 0}) {
+  if constexpr (!SPLIT) return node_part_full<PORTS>(M, E, kind_word, a, pkt, sink, hs, rx_atomic, false, hint);
+  const uint32_t kind = kind_word & 0xffu;
+  const Act noact{ACT_NONE, 0, Pkt{0, 0, 0, 0}};
+  const Post nopost{false, 0, 0, 0};
+  if (kind == K_TX_COMPLETE) return NodeOut{Act{ACT_KICK, a, Pkt{0, 0, 0, 0}}, nopost, false, 0};
+  uint32_t flags = (E.tloc ? CF_TLOC : 0u) | (E.demote ? CF_DEMOTE : 0u) | (rx_atomic ? CF_RX_ATOMIC : 0u);
+  if (kind == K_RECEIVE) {  // PointToPointNetDevice::Receive -> Ipv4L3Protocol::Receive (ipv4-l3-protocol.cc:434-537)
+    if (rx_atomic) atomicAdd(&M.dev[a].c.rx_packets, 1u);
+    else M.dev[a].c.rx_packets++;
+    if constexpr (PORTS) {
+      const uint32_t em = M.errm ? M.dev[a].em : 0u;
+      if (em && em_is_corrupt(M.dev, M.n_devices, em, pkt.size)) return NodeOut{noact, nopost, false, 0};
+    }
+    Pkt p = pkt;
+    p.size -= 2;                             // ProcessHeader strips the PppHeader
+    trace_call(M, E, NSGPU_TR_RX, a, p);     // m_macRxTrace
+    trace_call(M, E, NSGPU_TR_IP_RX, a, p);  // Ipv4L3Protocol::Receive: m_rxTrace (:455)
+    const uint32_t n = E.ctx < M.n_nodes ? E.ctx : M.dev_node[a];
+    if ((hint.valid ? hint.node : pkt_dst_node(M, p)) == n) {
+      // LocalDeliver of a whole UDP datagram to the node's PacketSink: ForwardUp, run inline
+      bool plain = !(p.app & (NSGPU_PKT_REPLY | NSGPU_PKT_ICMP)) && sink >= 0;
+      if constexpr (PORTS) plain = plain && !(M.frag && (p.ipid >> NSGPU_PKT_FRAG_SHIFT) != 0);
+      if (plain && (M.app_flags[sink] & 2u) && M.app_kind[sink] != NSGPU_APP_ECHO_SERVER) {
+        E.child(0, E.ctx, K_FWD_UP, (uint32_t)sink, p);
+        return NodeOut{noact, nopost, false, 0};
+      }
+    } else {
+      const uint32_t out = hint.valid ? route_at(M, n, hint.slot) : route_of(M, n, p);
+      if (out != 0xffffffffu && ((p.ttl - 1u) & 0xffu) != 0) {  // IpForward (:815-841)
+        p.ttl -= 1;
+        return NodeOut{Act{ACT_SEND, out, p}, nopost, false, 0};
+      }
+    }
+    flags |= CF_RESUMED;
+  }
+  const ColdOut o = node_part_cold<PORTS>(mdev_of(M.C), E.now, E.ctx, E.slot0, E.n, E.uid, E.trseq, flags, kind_word, a,
+                                          pkt, sink);
+  E.adopt(o.n);
+  E.trseq = o.trseq;
+  hs.ttl_drops += o.stat & 15u;
+  hs.no_route += (o.stat >> 4) & 15u;
+  hs.unreach += (o.stat >> 8) & 15u;
+  hs.icmp += (o.stat >> 12) & 15u;
+  if (o.stat & (1u << 16)) hs.stop = true;
+  return NodeOut{Act{o.op, o.dev, o.p}, Post{o.pkind != 0, o.pdelay, o.pkind, o.pa}, ((o.stat >> 17) & 1u) != 0, o.xdrop};
+}
 __device__ __forceinline__ bool run_event(const P2PDev &M, Emit &E, uint32_t kind_word, uint32_t a, const Pkt &pkt,
                                           int32_t sink, HStat &hs) {
   const NodeOut o = node_part(M, E, kind_word, a, pkt, sink, hs);
@@ -1390,10 +1551,31 @@ __device__ uint64_t g_gt[GT_BLK_MAX][8];
       g_blk[k][blockIdx.x][1] = __builtin_amdgcn_s_memrealtime();                                \
     }                                                                                            \
   } while (0)
+// What the lanes of each of k2_handle's holder blocks ran in the sampled window: g_blkk[block] = {Receives, gen-0
+// TransmitCompletes, local records, Sends, events of other kinds, the busiest lane's events, holder lanes}
+constexpr int BLKK_MAX = 64, BLKK_N = 8;
+__device__ uint32_t g_blkk[BLKK_MAX][BLKK_N];
+#define BLK_KINDS_T0(C)             \
+  uint32_t bk_[5] = {0, 0, 0, 0, 0}; \
+  const uint64_t bkw_ = (C).windows
+#define BLK_KINDS_EV(kind, local) \
+  bk_[(local) ? 2 : (kind) == K_RECEIVE ? 0 : (kind) == K_TX_COMPLETE ? 1 : (kind) == K_SEND ? 3 : 4]++
+#define BLK_KINDS_REC(holder)                                                                    \
+  do {                                                                                           \
+    if (bkw_ == g_blk_win && blockIdx.x < (uint32_t)BLKK_MAX && (holder)) {                      \
+      for (int k_ = 0; k_ < 5; k_++)                                                             \
+        if (bk_[k_]) atomicAdd(&g_blkk[blockIdx.x][k_], bk_[k_]);                                \
+      atomicMax(&g_blkk[blockIdx.x][5], bk_[0] + bk_[1] + bk_[2] + bk_[3] + bk_[4]);             \
+      atomicAdd(&g_blkk[blockIdx.x][6], 1u);                                                     \
+    }                                                                                            \
+  } while (0)
 #else
 #define BLK_T0() (void)0
 #define BLK_REC(k, win) (void)0
 #define BLK_MARK(i, win) (void)0
+#define BLK_KINDS_T0(C) (void)0
+#define BLK_KINDS_EV(kind, local) (void)0
+#define BLK_KINDS_REC(holder)      (void)0
 #endif
 
 // ================================ window pipeline ================================

@@ -465,6 +465,7 @@ inline int pa_grid_rt(const P2PDev &M) {
 // The deferred pipeline's partial records (Part): one per block of k2_pa's largest grid, then one per holder / hub
 // block of k2_handle
 constexpr int PA_PARTS = pa_grid<true>() + GRID_POOL_BIG - GRID_POOL, HD_PARTS = NLR, NPARTS = PA_PARTS + HD_PARTS;
+static_assert(CTL_PARTS_OFF + (size_t)NPARTS * PART_LINE <= CTL_MDEV_OFF, "the descriptor's copy lies behind the partial records");
 __device__ __forceinline__ Part *pa_part(Ctl &C, uint32_t b) { return part_rec(&C, b); }
 __device__ __forceinline__ Part *hd_part(Ctl &C, uint32_t b) { return part_rec(&C, (uint32_t)PA_PARTS + b); }
 // DF: the deferred pipeline's variant (single wide engine): when the last window is staged (C.pdf) its records
@@ -1160,6 +1161,18 @@ __device__ __forceinline__ void device_step(const P2PDev &M, Emit &E, const Act 
   }
 }
 
+// A node with more than NSLOT events in the window (at most CH): the ones its slot table does not hold, found by a
+// scan of the window for entries of node c, into the holder's list my[NSLOT, n) (out of line: cold paths).
+__device__ __noinline__ void node_rest_scan(const P2PDev *G, uint32_t c, uint32_t W, uint32_t base, uint32_t n,
+                                            uint32_t *my) {
+  const P2PDev &M = mdev_ref(G);
+  uint32_t m = NSLOT;
+  for (uint32_t x = 0; x < W && m < n; x++)
+    if (M.widx[x] >= (uint32_t)NSLOT && M.widx[x] != NOHOLD &&
+        lp_of(M, M.wctx[base + x], M.wkind[base + x], M.wa[base + x]) == c)
+      my[m++] = x;
+}
+
 template <bool WIDE, bool DF = false, bool PORTS = false>
 __device__ __forceinline__ void handle_node2(const P2PDev &M, Ctl &C, uint32_t i0, uint32_t W, uint32_t base, Red &R,
                                              uint32_t *lds, const HCtl &hc, SlotPre sp, uint32_t *lcnt_sh) {
@@ -1167,6 +1180,7 @@ __device__ __forceinline__ void handle_node2(const P2PDev &M, Ctl &C, uint32_t i
   uint64_t *chk = reinterpret_cast<uint64_t *>(lds + HB * CH);
   uint64_t tmn = ~0ull, wnd = ~0ull, wndw = ~0ull;
   HStat hs{0, 0, 0, 0, false};
+  BLK_KINDS_T0(C);
   if (base != 0 && i0 < W) {
     sp.ctx = M.wctx[base + i0];
     sp.kind = M.wkind[base + i0];
@@ -1199,13 +1213,7 @@ __device__ __forceinline__ void handle_node2(const P2PDev &M, Ctl &C, uint32_t i
       if (n > 1) {
         const uint32_t ns = n < (uint32_t)NSLOT ? n : (uint32_t)NSLOT;
         for (uint32_t j = 0; j < ns; j++) my[j] = M.node_tab[(uint64_t)c * NTAB + 1 + j];
-        if (n > (uint32_t)NSLOT) {  // the rest: window entries of node c not in the table
-          uint32_t m = NSLOT;
-          for (uint32_t x = 0; x < W && m < n; x++)
-            if (M.widx[x] >= (uint32_t)NSLOT && M.widx[x] != NOHOLD &&
-                lp_of(M, M.wctx[base + x], M.wkind[base + x], M.wa[base + x]) == c)
-              my[m++] = x;
-        }
+        if (n > (uint32_t)NSLOT) node_rest_scan(mdev_of(M.C), c, W, base, n, my);
         for (uint32_t j = 0; j < n; j++) mk[j] = M.wkey[base + my[j]];
         for (uint32_t a = 1; a < n; a++) {  // insertion sort by key
           const uint32_t v = my[a];
@@ -1305,8 +1313,9 @@ __device__ __forceinline__ void handle_node2(const P2PDev &M, Ctl &C, uint32_t i
         E.n = 0;
         E.trseq = 0;
         E.lj = -1;
+        BLK_KINDS_EV(kw & 0xffu, E.tloc);
         {  // run_event with the device step on the cached state
-          const NodeOut o = node_part<PORTS>(M, E, kw, a, pk, sink, hs, true, hint);
+          const NodeOut o = node_part<PORTS, WIDE>(M, E, kw, a, pk, sink, hs, true, hint);
           device_step<PORTS>(M, E, o.act, D);
           if (o.xdrop) xdrop_record<PORTS>(M, E, o.xdrop, o.act.p);
           if (o.post.valid) E.child(o.post.delay, E.ctx, o.post.kind, o.post.a, Pkt{0, 0, 0, 0});
@@ -1328,6 +1337,7 @@ __device__ __forceinline__ void handle_node2(const P2PDev &M, Ctl &C, uint32_t i
       wndw = E.wndw;
     }
   }
+  BLK_KINDS_REC(wi == 0);
   if constexpr (DF) {  // (the deferred pipeline: the block's record, minima and child totals; df_fold folds them)
     publish_part<HB>(hd_part(C, blockIdx.x), tmn, wnd, wndw, (uint64_t)xa.tc | ((uint64_t)xa.ti << 32));
   } else {
@@ -1863,7 +1873,7 @@ __device__ __forceinline__ void hub_node(const P2PDev &M, Ctl &C, uint32_t c, ui
           E.uid = (uint32_t)key, E.tloc = false;
           E.trseq = 0;
           E.demote = rel == slo || rel == shi;
-          const NodeOut o = node_part<PORTS>(M, E, kw, a, pk, sink, hs, true);
+          const NodeOut o = node_part<PORTS, WIDE>(M, E, kw, a, pk, sink, hs, true);
           uint32_t ni = 0;
           for (uint32_t jj = 0; jj < E.n; jj++) ni += (M.ch_kind[E.slot0 + jj] & 0xffu) == K_FWD_UP;
           M.hx[s] = HubEv{o.act.op, o.act.dev, o.act.p, o.post.delay, o.post.valid ? o.post.kind : 0u, o.post.a, E.n,
@@ -2009,7 +2019,7 @@ __device__ __forceinline__ void hub_node(const P2PDev &M, Ctl &C, uint32_t c, ui
             E.uid = (uint32_t)c_key[q], E.tloc = false;
             E.trseq = 0;
             E.demote = rel == slo || rel == shi;
-            const NodeOut o = node_part<PORTS>(M, E, c_kind[q], c_a[q], c_pkt[q], sink, hs, true);
+            const NodeOut o = node_part<PORTS, WIDE>(M, E, c_kind[q], c_a[q], c_pkt[q], sink, hs, true);
             uint32_t ni = 0;
             for (uint32_t jj = 0; jj < E.n; jj++) ni += (M.ch_kind[E.slot0 + jj] & 0xffu) == K_FWD_UP;
             M.hx[s] = HubEv{o.act.op, o.act.dev, o.act.p, o.post.delay, o.post.valid ? o.post.kind : 0u, o.post.a, E.n,
