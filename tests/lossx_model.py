@@ -7,7 +7,8 @@ send's mobility updates).  Distances, delays, receivers, uids and contexts still
 (nsref.fanout_yans); with no extended chain in force so does the power.  One more closure action, ("loss", spec),
 installs a chain at its place among the closure's actions: spec is (links, entries) — loss_ref links and Matrix
 (a, b, loss_db) triples — or None for the config's chain again.  It names no phy, so the closure probes nothing for
-it.  Every reception's power is kept (rx_powers) for the tests' threshold-margin check."""
+it.  Every reception's power is kept (rx_powers) for the tests' threshold-margin check.  send_packet takes the frame's
+mode, preamble and tx power per call, as wsm.Model.send_packet does (default: the model's own)."""
 import numpy as np
 
 import loss_ref
@@ -26,44 +27,22 @@ class Model(wsm.Model):
     def set_loss(self, spec):
         self.lx = None if spec is None else (list(spec[0]), loss_ref.matrix_of(spec[1]))
 
-    # wsm.Model.run with the "loss" action
-    def run(self, closures, stop_ns):
-        for ts, actions in closures:
-            self._schedule(ts, wsm.NO_CONTEXT, "closure", list(actions))
-        self._schedule(stop_ns, wsm.NO_CONTEXT, "stop", None)
-        while self.q:
-            ts, uid, ctx, kind, arg = self.q.pop(0)
-            self.now, self.cur_uid, self.ctx = ts, uid, ctx
-            self.log.append((ts, uid, ctx))
-            if kind == "stop":
-                break
-            if kind == "closure":
-                for a in arg:
-                    if a[0] not in ("noop", "loss"):  # (("probe", phy) does nothing more)
-                        p = self.phy[a[1]]
-                        self.probes.append((ts, uid, a[1], p.state(ts), p.delay_until_idle(ts)))
-                for a in arg:
-                    if a[0] == "send":
-                        self.send_packet(a[1], a[2])
-                    elif a[0] == "switch":
-                        self.set_channel_number(a[1], a[2], a[3])
-                    elif a[0] == "loss":
-                        self.set_loss(a[1])
-            elif kind == "retry":
-                self.set_channel_number(*arg)
-            elif kind == "rx":
-                self.start_receive(*arg)
-            else:
-                self.end_receive(arg)
-        return self
+    NO_PHY = wsm.Model.NO_PHY + ("loss",)  # (("probe", phy) does nothing more than the closure's probe)
+
+    def act(self, a):
+        if a[0] == "loss":
+            self.set_loss(a[1])
+        else:
+            super().act(a)
 
     # wsm.Model.send_packet with the power of the chain in force
-    def send_packet(self, s, size):
+    def send_packet(self, s, size, mode=None, preamble=None, dbm=None):
+        mode, preamble, dbm = self.frame_of(mode, preamble, dbm)
         p, now = self.phy[s], self.now
         st = p.state(now)
         if st in (wsm.TX, wsm.SWITCHING):
             raise wsm.SendError(f"SendPacket of phy {s} at {now} in state {st}")
-        dur = int(wifi.tx_duration_ns(int(size), self.mode, self.preamble))
+        dur = int(wifi.tx_duration_ns(int(size), mode, preamble))
         if st == wsm.RX:
             p.live["cancelled"] = True
             p.locked.remove(p.live["k"])
@@ -74,20 +53,21 @@ class Model(wsm.Model):
         k = len(self.txs)
         self.txs.append((now, self.cur_uid, s))
         self.tx_sizes.append(int(size))
+        self.tx_frames.append((mode, preamble, dbm))
         for j in mobility_ref.send_updates(self.chan, s):
             if j in self.mob:
                 self.mob[j].update(now)
                 self.x[j], self.y[j], self.z[j] = self.mob[j].position()
-        fo = nsref.fanout_yans(self.x, self.y, self.z, self.chan, self.node, s, self.dbm, self.chain, self.cfg.speed,
+        fo = nsref.fanout_yans(self.x, self.y, self.z, self.chan, self.node, s, dbm, self.chain, self.cfg.speed,
                                now, self.uid)
         pos = lambda i: (float(self.x[i]), float(self.y[i]), float(self.z[i]))
         for r in fo:
             j, taken = int(r["phy"]), []
             if self.lx is None:
-                dbm = float(r["rx_dbm"])
+                rx_dbm = float(r["rx_dbm"])
             else:  # PropagationLossModel::CalcRxPower (txPowerDbm, senderMobility, receiverMobility)
-                dbm = loss_ref.calc(self.lx[0], self.lx[1], s, j, pos(s), pos(j), self.dbm, taken)
-            w = wsm._dbm_to_w(dbm + self.cfg.rx_gain_db)
+                rx_dbm = loss_ref.calc(self.lx[0], self.lx[1], s, j, pos(s), pos(j), dbm, taken)
+            w = wsm._dbm_to_w(rx_dbm + self.cfg.rx_gain_db)
             self.rx_powers.append((k, j, w, tuple(taken)))
             uid = self._schedule(int(r["ts"]), int(r["context"]), "rx", (j, k, w, dur))
             assert uid == int(r["uid"])

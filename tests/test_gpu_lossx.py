@@ -3,7 +3,7 @@ k_wl_rx<true> / k_wl_send<true> over the device-resident chain and Matrix table)
 plain-Python PHY of tests/wifi_switch_model.py with tests/loss_ref.py's CalcRxPower — on the scenarios of
 tests/lossx_cases.py, which tests/test_lossx_model_cpu.py checks on the model alone.
 
-Exactly equal (test_gpu_wifi_switch.equal_model): the pop log (ts, uid, context), the dispatch count and next uid, the
+Exactly equal (wifi_model_compare.equal_model): the pop log (ts, uid, context), the dispatch count and next uid, the
 per-phy counters and state fields, the end records' integer fields, every switch call's outcome, get_channel's records,
 and GetState / GetDelayUntilIdle at every probing closure.  rx_w and snr within the project's 1e-9 relative (device and
 host log10 / pow differ in the last bits), per within test_gpu_wifi_per.compare_record's bound — the tolerances
@@ -22,7 +22,7 @@ import nsgpu
 import test_wifi_switch_cpu as sc
 import wifi
 import wifi_switch_model as wsm
-from test_gpu_wifi_switch import equal_model, error_code, finish
+from wifi_model_compare import equal_model, error_code, finish
 from test_lossx_model_cpu import run_model
 
 pytestmark = pytest.mark.gpu

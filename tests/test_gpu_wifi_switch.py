@@ -5,9 +5,8 @@ tests/test_wifi_switch_cpu.py holds to the C++ oracle and to hand-derived branch
 Exactly equal: the pop log (ts, uid, context), the dispatch count and next uid, the per-phy counters and state fields,
 the end records' integer fields, the notes, every switch call's outcome, get_channel's records, and GetState /
 GetDelayUntilIdle at every closure.  snr / per / rx_w: tests/test_gpu_wifi_per.py's compare_record (its bound function,
-K_DEVICE) against the model's 60-digit reference values."""
-import re
-
+K_DEVICE) against the model's 60-digit reference values.  The comparison itself is tests/wifi_model_compare.py's
+equal_model, which tests/test_gpu_lossx.py and tests/test_gpu_wifi_fuzz.py share."""
 import numpy as np
 import pytest
 
@@ -16,16 +15,11 @@ import nsgpu
 import test_wifi_switch_cpu as sc
 import wifi
 import wifi_switch_model as wsm
-from test_gpu_wifi_per import compare_record
+from wifi_model_compare import equal_model, error_code, finish
 
 pytestmark = pytest.mark.gpu
 
 EINVAL, ESTATE = 1, 4
-PHY_FIELDS = wsm.COUNTERS + ("end_tx", "end_rx", "end_cca_busy", "rxing", "ni_len")
-
-
-def error_code(e):
-    return int(re.match(r"nsgpu error (\d+)", str(e)).group(1))
 
 
 def run_device(case, notify=(), mob=None, log_cap=1 << 16):
@@ -71,37 +65,6 @@ def run_device(case, notify=(), mob=None, log_cap=1 << 16):
                ends=lp.read_ends(), phys=lp.read_phys(), notes=lp.read_notes(), probes=probes, switches=switches,
                channels=[lp.get_channel(j) for j in range(ph.n_phy)], sim=sim, lp=lp)
     return out
-
-
-def equal_model(g, m, what=""):
-    mts, muid, mctx = m.log_arrays()
-    assert (g["dispatched"], g["next_uid"]) == (len(mts), m.uid), (what, g["dispatched"], len(mts), g["next_uid"], m.uid)
-    for a, b, f in zip(g["log"], (mts, muid, mctx), ("ts", "uid", "ctx")):
-        assert np.array_equal(a, b), (what, f, np.flatnonzero(a != b)[:5])
-    mc_ = m.counters()
-    for f in PHY_FIELDS:
-        assert np.array_equal(g["phys"][f], mc_[f]), (what, f, np.flatnonzero(g["phys"][f] != mc_[f])[:8])
-    gends, mends = g["ends"], m.end_records()
-    assert len(gends) == len(mends)
-    for f in sc.END_FIELDS:
-        assert np.array_equal(gends[f], mends[f]), (what, f)
-    worst = -1.0
-    for e, r in zip(gends, m.end_refs):
-        if r is None:
-            assert int(e["flags"]) & wifi.END_CANCELLED and e["snr"] == 0.0 and e["per"] == 0.0 and e["rx_w"] == 0.0
-            continue
-        snr, per, chunks, rx_w = r
-        worst = max(worst, compare_record(e, snr, per, chunks, rx_w, (what, int(e["phy"]), int(e["tx"]))))
-    retried = set(m.retries)
-    assert g["switches"] == [s for s in m.switches if (s[0], s[1]) not in retried], what
-    assert g["probes"] == m.probes, what
-    assert g["channels"] == m.channel_records(), what
-    print(f"{what}: {len(mts)} events, {len(gends)} ends, worst per ratio {worst:.2f}")
-
-
-def finish(g):
-    g["lp"].close()
-    g["sim"].close()
 
 
 # ---------------------------------------------------------------- device vs model

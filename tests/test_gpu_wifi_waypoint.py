@@ -111,7 +111,7 @@ def test_two_ray_ground_follows_a_climbing_waypoint_phy_and_a_channel_switch():
     24 ms and so keeps its m_current.time from then on.  Against tests/lossx_model.py, driven by the waypoint
     restatement."""
     from test_gpu_lossx import run_device
-    from test_gpu_wifi_switch import equal_model, finish
+    from wifi_model_compare import equal_model, finish
     from test_lossx_model_cpu import run_model
     import lossx_model
     base = lc.two_ray_case()

@@ -264,12 +264,15 @@ def chunk_nbits(duration_ns, mode):
     return int(float(phy_rate(mode)) * nsref.get_seconds(duration_ns)) & 0xffffffff
 
 
-def snr_per(model, noise_figure_db, events, k, synced=None):
+def snr_per(model, noise_figure_db, events, k, synced=None, rxing_at=None):
     """CalculateSnrPer (:347-366) of events[k] at one phy.
 
     events: [(start_ns, end_ns, rx_w, mode, preamble)] in the order their StartReceivePacket calls are dispatched
     (AppendEvent :192-212 runs for every one of them, whatever the PHY does with the frame).  synced: the indices
     the PHY locked on (m_rxing from NotifyRxStart at their start to NotifyRxEnd at their EndReceive); default (k,).
+    rxing_at: m_rxing at each event's AppendEvent, where the caller kept it (a PHY model does); it then replaces what
+    is derived from `synced` — and holds where a StartReceive shares a nanosecond with a synced frame's end, which
+    the derivation refuses.
     Returns (snr, per, chunks): snr a float, per an mpf, chunks the CalculateChunkSuccessRate calls of CalculatePer
     (:260-345) in order as (is_header, duration_ns, noise_before, nbits); a zero duration is listed with nbits 0.
     """
@@ -291,8 +294,8 @@ def snr_per(model, noise_figure_db, events, k, synced=None):
             # (a StartReceive in the EndReceive's nanosecond lands behind the frame's own end entry, upper_bound
             # :378, where CalculateNoiseInterferenceW has already stopped: dispatched before or after, no effect)
             break
-        rxing = False
-        for s in synced:
+        rxing = False if rxing_at is None else bool(rxing_at[i])
+        for s in synced if rxing_at is None else ():
             if s < i:
                 assert events[s][1] != start, "a StartReceive in a synced frame's last nanosecond"
                 rxing = rxing or events[s][0] <= start < events[s][1]

@@ -12,15 +12,18 @@ Written from the reference's lines alone:
 Arithmetic it does not restate: arrival time and rx power of every (send, receiver) pair are nsref.fanout_yans's,
 called with the channel numbers (and positions) current at the send; durations are wifi.tx_duration_ns's; an
 EndReceive's (snr, per) is wifi_per_ref.snr_per's over the phy's StartReceivePacket calls since its last
-EraseEvents.  snr_per derives m_rxing from the frames it is told the phy locked on; a lock that a SendPacket
-cancelled is left out of that list (the rest of its frame is then folded into m_firstPower at the next arrival
-instead of at the next arrival after the frame: the same additions in the same time order, so the same doubles,
-unless two list entries share a nanosecond).
+EraseEvents.  snr_per is given m_rxing as it stood at each of those calls (AppendEvent's branch), kept beside the
+window: a lock that a SendPacket or a switch cancelled, and a StartReceive in the nanosecond of a frame's EndReceive (a
+reply sent with delay 0 arrives so at a third phy on the line), then fold into m_firstPower as the reference does.
 
 Setup order: the oracle replay's — the closures are scheduled in the order given (the tests list every send, then
 every switch, where nsref_wifil_sends puts its moves), then Simulator::Stop.  A closure is (ts, [actions]); actions:
 ("send", phy, size), ("switch", phy, nch, delay_ns), ("noop",).  Every closure first records GetState of the phys its
-actions name (a probe: (ts, uid, phy, state, delay until idle))."""
+actions name (a probe: (ts, uid, phy, state, delay until idle)).
+
+Frames: the model's mode, preamble and tx power are the defaults of send_packet, which takes all three per call; a
+reception keeps the (mode, preamble) of its own frame (tx_frames), so frames of different modes may overlap at a phy
+(tests/wifi_fuzz_model.py sends them)."""
 import bisect
 import math
 
@@ -57,6 +60,7 @@ class _Phy:
         self.switches = self.drop_switching = 0
         self.live = None                     # the pending EndReceive of the frame being received
         self.window, self.locked = [], []    # StartReceivePacket calls since the last EraseEvents; the locked ones
+        self.window_rxing = []               # m_rxing at each of them (AppendEvent's branch)
 
     def state(self, now):  # GetState (wifi-phy-state-helper.cc:159-183)
         if self.end_tx > now:
@@ -92,8 +96,10 @@ class Model:
         self.uid = 4         # DefaultSimulatorImpl: m_uid (4)
         self.now, self.cur_uid, self.ctx = 0, 0, NO_CONTEXT
         self.log, self.ends, self.notes, self.txs, self.switches, self.probes = [], [], [], [], [], []
+        self.log_kinds = []  # per pop-log entry: "closure" | "retry" | "rx" | "end" | "stop"
         self.retries = []    # (ts, uid) of the retry events postponed switches scheduled
         self.tx_sizes = []   # per SendPacket
+        self.tx_frames = []  # per SendPacket: (mode, preamble, dbm)
 
     # ---- Simulator
     def _schedule(self, ts, ctx, kind, arg):
@@ -110,18 +116,16 @@ class Model:
             ts, uid, ctx, kind, arg = self.q.pop(0)
             self.now, self.cur_uid, self.ctx = ts, uid, ctx
             self.log.append((ts, uid, ctx))
+            self.log_kinds.append(kind)
             if kind == "stop":
                 break
             if kind == "closure":
                 for a in arg:
-                    if a[0] != "noop":
+                    if a[0] not in self.NO_PHY:
                         p = self.phy[a[1]]
                         self.probes.append((ts, uid, a[1], p.state(ts), p.delay_until_idle(ts)))
                 for a in arg:
-                    if a[0] == "send":
-                        self.send_packet(a[1], a[2])
-                    elif a[0] == "switch":
-                        self.set_channel_number(a[1], a[2], a[3])
+                    self.act(a)
             elif kind == "retry":
                 self.set_channel_number(*arg)
             elif kind == "rx":
@@ -130,13 +134,28 @@ class Model:
                 self.end_receive(arg)
         return self
 
+    NO_PHY = ("noop",)  # the actions that name no phy: a closure probes nothing for them
+
+    def act(self, a):
+        """One action of a closure, at its place among the closure's actions (the subclasses add theirs)."""
+        if a[0] == "send":
+            self.send_packet(a[1], a[2])
+        elif a[0] == "switch":
+            self.set_channel_number(a[1], a[2], a[3])
+
+    def frame_of(self, mode, preamble, dbm):
+        return (self.mode if mode is None else mode, self.preamble if preamble is None else preamble,
+                self.dbm if dbm is None else float(dbm))
+
     # ---- YansWifiPhy::SendPacket (:499-522) and YansWifiChannel::Send (yans-wifi-channel.cc:77-115)
-    def send_packet(self, s, size):
+    def send_packet(self, s, size, mode=None, preamble=None, dbm=None):
+        """mode, preamble, dbm: this frame's (default: the model's own)."""
+        mode, preamble, dbm = self.frame_of(mode, preamble, dbm)
         p, now = self.phy[s], self.now
         st = p.state(now)
         if st in (TX, SWITCHING):
             raise SendError(f"SendPacket of phy {s} at {now} in state {st}")
-        dur = int(wifi.tx_duration_ns(int(size), self.mode, self.preamble))
+        dur = int(wifi.tx_duration_ns(int(size), mode, preamble))
         if st == RX:  # m_endRxEvent.Cancel (); NotifyRxEnd (); SwitchToTx's RX case
             p.live["cancelled"] = True
             p.locked.remove(p.live["k"])  # (see the module docstring)
@@ -147,11 +166,12 @@ class Model:
         k = len(self.txs)
         self.txs.append((now, self.cur_uid, s))
         self.tx_sizes.append(int(size))
+        self.tx_frames.append((mode, preamble, dbm))
         for j in mobility_ref.send_updates(self.chan, s):  # MobilityModel::GetDistanceFrom's Updates
             if j in self.mob:
                 self.mob[j].update(now)
                 self.x[j], self.y[j], self.z[j] = self.mob[j].position()
-        fo = nsref.fanout_yans(self.x, self.y, self.z, self.chan, self.node, s, self.dbm, self.chain, self.cfg.speed,
+        fo = nsref.fanout_yans(self.x, self.y, self.z, self.chan, self.node, s, dbm, self.chain, self.cfg.speed,
                                now, self.uid)
         for r in fo:  # the receiver loop's ScheduleWithContext calls, in m_phyList order
             w = _dbm_to_w(float(r["rx_dbm"]) + self.cfg.rx_gain_db)  # StartReceivePacket: rxPowerDbm += m_rxGainDb
@@ -172,7 +192,8 @@ class Model:
             p.ni.insert(bisect.bisect_right([e[0] for e in p.ni], now), [now, w])
         p.ni.insert(bisect.bisect_right([e[0] for e in p.ni], end_new), [end_new, -w])
         k = len(p.window)
-        p.window.append((now, end_new, w, self.mode, self.preamble))
+        p.window_rxing.append(p.rxing)
+        p.window.append((now, end_new, w) + self.tx_frames[tx][:2])
         st = p.state(now)
         p.c["rx"] += 1
         maybe, rx_duration = False, 0
@@ -221,12 +242,15 @@ class Model:
             self.ends.append((self.now, self.cur_uid, ev["phy"], 0.0, 0.0, ev["tx"], wifi.END_CANCELLED, 0.0))
             self.end_refs.append(None)
             return
-        snr, per, chunks = wifi_per_ref.snr_per(self.cfg.error_model, self.cfg.noise_figure_db, p.window, ev["k"],
-                                                 synced=p.locked)
+        snr, per, chunks = self.snr_per(p, ev["k"])
         self.ends.append((self.now, self.cur_uid, ev["phy"], snr, float(per), ev["tx"], 0, ev["w"]))
         self.end_refs.append((snr, per, chunks, ev["w"]))
         p.rxing = False  # NotifyRxEnd; SwitchFromRxEndOk / Error
         p.live = None
+
+    def snr_per(self, p, k):
+        return wifi_per_ref.snr_per(self.cfg.error_model, self.cfg.noise_figure_db, p.window, k, synced=p.locked,
+                                    rxing_at=p.window_rxing)
 
     # ---- YansWifiPhy::SetChannelNumber (:327-374)
     def set_channel_number(self, j, nch, delay):
@@ -253,7 +277,7 @@ class Model:
         p.start_sw, p.end_sw = now, now + delay
         if self.erase:
             p.ni, p.first_power = [], 0.0  # m_interference.EraseEvents ()
-            p.window, p.locked = [], []
+            p.window, p.locked, p.window_rxing = [], [], []
         p.switches += 1
         self.chan[j] = p.channel = nch
         rec(DONE)
@@ -368,7 +392,7 @@ def drive_state_helpers(m, delays):
             if got != arg[3]:
                 raise wifi_note_model.Precondition(f"GetState of phy {arg[2]} at {ts}: helper {got}, model {arg[3]}")
         elif what == 2 and len(arg) == 2:
-            hs[arg[0]].on_send(ts, int(wifi.tx_duration_ns(int(sizes[arg[1]]), m.mode, m.preamble)))
+            hs[arg[0]].on_send(ts, int(wifi.tx_duration_ns(int(sizes[arg[1]]), *m.tx_frames[arg[1]][:2])))
         elif what == 2:
             hs[arg[2]].on_switch(ts, delays[(arg[0], arg[1])])
         else:
