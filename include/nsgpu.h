@@ -30,7 +30,9 @@ enum {
   NSGPU_ESTATE = 4,   /* call not valid in the current state (e.g. empty queue) */
   NSGPU_ERANGE = 5    /* the uid counter would pass 0xfffffffe: DefaultSimulatorImpl's uint32 m_uid wraps to 0 after
                        * 0xffffffff (default-simulator-impl.cc:52-56,188-219), which no engine replicates;
-                       * the run fails before an event with such a uid is dispatched */
+                       * the run fails before an event with such a uid is dispatched.  Also a monitored p2p node's
+                       * IPv4 identification reaching 16 bits (nsgpu_p2p_flow_stats): the other counter whose wrap
+                       * is not replicated */
 };
 
 /* ---------------- library / device plumbing ---------------- */
@@ -603,6 +605,16 @@ int nsgpu_loss_counter_run(uint32_t window, const uint32_t *seq, uint64_t n, uin
  * engine returns its own nodes' devices: the owner's values count).  An engine with an enabled model cannot join a
  * host-closure runtime (nsgpu_p2p_setup_uid, nsgpu_sim_attach_p2p / _adopt_p2p) and refuses nsgpu_p2p_inject_send. */
 int nsgpu_p2p_error_models(nsgpu_p2p *h, nsgpu_error_model_record *out, void *stream);
+/* Per-flow statistics (nsgpu_p2p_scenario.flowmon): FlowMonitor's FlowStats of every flow, 2 * n_apps records
+ * (nsgpu_flow_record; zeros for an unmonitored engine).  lost_packets includes FlowMonitor::CheckForLostPackets
+ * (max_delay_ns) at the run's last dispatched time: a sweep kernel counts the packets still tracked whose last
+ * report is at least max_delay_ns old (10 s is the reference's MaxPerHopDelay).  The sweep changes nothing: the call
+ * may be repeated, with other delays.  A negative delay is NSGPU_EINVAL.  A monitored node whose IPv4 identification
+ * reaches its tracked-packet table's size (65,536 at most: the 16-bit identification would wrap, which is not
+ * modelled) fails the run with NSGPU_ERANGE (error code 16384).  A monitored engine cannot join a host-closure
+ * runtime (nsgpu_p2p_setup_uid, nsgpu_sim_attach_p2p / _adopt_p2p) and refuses nsgpu_p2p_inject_send; flowmon with
+ * frag or on a partitioned engine is refused at create. */
+int nsgpu_p2p_flow_stats(nsgpu_p2p *h, int64_t max_delay_ns, nsgpu_flow_record *out, void *stream);
 /* The threshold table nsgpu_p2p_create builds for an EU_BYTE / EU_BIT Rate model (host only): out[n] =
  * 1 - pow (1.0 - rate, n or 8 n) for frame sizes n = 0 .. NSGPU_EM_TABLE_SIZE - 1, with the host's pow. */
 int nsgpu_error_model_thresholds(uint32_t unit, double rate, double *out);

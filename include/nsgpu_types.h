@@ -192,7 +192,7 @@ typedef struct nsgpu_p2p_scenario {
    * such UdpEchoClient on it: the reply's fragments return there); DESIGN.md §6 says why.
    *   frag_timeout_ns   Ipv4L3Protocol::FragmentExpirationTimeout; 0: the reference's default, Seconds (30) */
   uint32_t frag;
-  uint32_t pad_frag_;
+  uint32_t flowmon;  /* per-flow statistics, below: the word that was frag's padding (the struct keeps its size) */
   int64_t frag_timeout_ns;
   /* ---- receive error models (appended: the fields above keep their offsets) ----
    * dev_em_kind == NULL: no device has a model (the other fields are then ignored).  Given: device d's
@@ -219,7 +219,32 @@ typedef struct nsgpu_p2p_scenario {
   const uint32_t *em_list;
   uint32_t rng_seed;
   uint32_t rng_run;
+  /* ---- per-flow statistics: `flowmon`, the word behind `frag` that was padding until now (callers zeroed it), so
+   * every field keeps its offset and the struct its size ----
+   * flowmon == 1: FlowMonitor's FlowStats (flow-monitor.cc:121-300, ipv4-flow-probe.cc:192-346,
+   * ipv4-flow-classifier.cc:102-155) are accumulated on the device while the run goes on; nsgpu_p2p_flow_stats reads
+   * them.  The run itself is the unmonitored one: no event is added or reordered.  Not with frag, not on a partitioned
+   * engine, not under a host-closure runtime (refused). */
 } nsgpu_p2p_scenario;
+
+/* What nsgpu_p2p_flow_stats returns per flow, 2 * n_apps records: flow a = application a's datagrams, flow
+ * n_apps + a = the echo replies to UdpEchoClient a (zeros for a flow that sent nothing).  FlowMonitor::FlowStats
+ * without the histograms; times in ns.  Only UDP datagrams are classified: ICMP messages report nothing. */
+#define NSGPU_FLOW_DROP_REASONS 4u
+enum { NSGPU_FLOW_DROP_NO_ROUTE = 0, NSGPU_FLOW_DROP_TTL_EXPIRE = 1, NSGPU_FLOW_DROP_BAD_CHECKSUM = 2 /* stays 0 */,
+       NSGPU_FLOW_DROP_QUEUE = 3 };
+typedef struct nsgpu_flow_record {
+  uint64_t tx_packets, tx_bytes;        /* ReportFirstTx (Ipv4L3Protocol::Send, m_sendOutgoingTrace) */
+  uint64_t rx_packets, rx_bytes;        /* ReportLastRx (LocalDeliver, m_localDeliverTrace: before the endpoint lookup) */
+  int64_t delay_sum_ns, jitter_sum_ns, last_delay_ns;
+  int64_t time_first_tx_ns, time_last_tx_ns, time_first_rx_ns, time_last_rx_ns;
+  uint64_t times_forwarded;             /* the received packets' ReportForwarding calls (m_unicastForwardTrace) */
+  uint64_t lost_packets;                /* the drops below + the tracked packets not seen for max_delay_ns */
+  uint64_t packets_dropped[NSGPU_FLOW_DROP_REASONS], bytes_dropped[NSGPU_FLOW_DROP_REASONS];
+  uint64_t first_tx_ts;                 /* the dispatched event of the flow's first ReportFirstTx: its (ts, uid) — */
+  uint32_t first_tx_uid;                /*   FlowIds follow that order (Ipv4FlowClassifier numbers a flow when first seen) */
+  uint32_t pad_;
+} nsgpu_flow_record;                    /* 184 bytes */
 
 enum { NSGPU_EM_NONE = 0, NSGPU_EM_RECEIVE_LIST = 1, NSGPU_EM_RATE = 2,
        NSGPU_EM_LIST = 3 /* ListErrorModel (by Packet::GetUid): named so that it can be refused */ };

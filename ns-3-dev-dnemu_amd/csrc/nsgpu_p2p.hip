@@ -22,7 +22,16 @@ namespace nsgpu {
 // so a code object, of their own — this one holds the kernels it held before ports existed, laid out as they were)
 void launch_handle_ports(const P2PDev &M, bool wide, bool xl, bool df, int grid, hipStream_t s, hipEvent_t ev0,
                          hipEvent_t ev1);
+// k_flow_sweep (the same translation unit: the per-flow statistics are the extended handlers')
+void launch_flow_sweep(const P2PDev &M, int64_t now, int64_t max_delay, uint64_t n_entries, unsigned long long *lost,
+                       hipStream_t s);
 }  // namespace nsgpu
+static_assert(sizeof(nsgpu_flow_record) == 184 && offsetof(nsgpu_flow_record, packets_dropped) == 104 &&
+              offsetof(nsgpu_flow_record, first_tx_ts) == 168, "nsgpu_flow_record");
+static_assert(offsetof(nsgpu_p2p_scenario, flowmon) == offsetof(nsgpu_p2p_scenario, frag) + 4 &&
+              offsetof(nsgpu_p2p_scenario, frag_timeout_ns) == offsetof(nsgpu_p2p_scenario, frag) + 8 &&
+              sizeof(nsgpu_p2p_scenario) == offsetof(nsgpu_p2p_scenario, rng_run) + 4,
+              "flowmon takes the padding word behind frag: no field moves, the struct keeps its size");
 
 // (nsgpu_comm, NCCL_TRY: nsgpu_internal.h)
 
@@ -98,6 +107,10 @@ struct nsgpu_p2p {
   const uint32_t *frag_init = nullptr;
   size_t frag_words = 0, frag_bytes = 0;
   uint32_t frag_nf = 0;
+  // a monitored engine (scenario flowmon) keeps its reset image in frag_init / frag_words / frag_bytes too (the two
+  // share the place behind node_ipid and exclude each other): the tracked-packet tables' entries, the sweep's counts
+  uint64_t fm_entries = 0;
+  unsigned long long *fm_lost = nullptr;
   // partitioned run
   nsgpu_comm *comm = nullptr;  // RCCL transport (null: a loopback group member)
   X1Hdr x1h0{};                // empty X1 summary (reset template)
@@ -180,6 +193,9 @@ struct EnginePlan {
   std::vector<EmRec> em_recs;
   std::vector<double> em_tabs;
   std::vector<uint32_t> em_list;
+  // per-flow statistics (scenario flowmon): each node's tracked-packet table size (plan_flowmon)
+  bool flowmon = false;
+  std::vector<uint32_t> fm_cap;
   // the setup-time events (this rank's, partitioned) and the bound of window 0 (the whole setup: every rank)
   std::vector<uint64_t> its;
   std::vector<uint32_t> iuid, ictx, ikind, ia;
@@ -274,6 +290,68 @@ static int plan_error_models(const nsgpu_p2p_scenario *sc, EnginePlan &P) {
     P.em_recs.push_back(r);
     P.dev_em[d] = (uint32_t)P.em_recs.size();
   }
+  return NSGPU_OK;
+}
+
+// Per-flow statistics (nsgpu_p2p_scenario.flowmon): the refusals, and each node's tracked-packet table size — a bound
+// on the identifications the node hands out before the run ends (nsgpu_p2p_dev.h "per-flow statistics"), at most
+// FM_NODE_CAP.  A node originates its senders' datagrams, the echo replies to the clients that address it, and with
+// icmp its ICMP errors, which take identifications too: at most one error a datagram of the scenario.  Called once
+// the applications are validated.
+static int plan_flowmon(const nsgpu_p2p_scenario *sc, const uint32_t *owner, EnginePlan &P) {
+  // (the word was padding before: a value other than 0 or 1 is a caller that never set it, not a request)
+  if (sc->flowmon > 1)
+    return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: flowmon is %u (0 or 1: the word behind frag, padding in earlier "
+                     "versions of the struct, must be zeroed)", sc->flowmon);
+  P.flowmon = sc->flowmon == 1;
+  if (!P.flowmon) return NSGPU_OK;
+  if (sc->frag)
+    return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: flowmon with frag is not modelled (the reference classifies a "
+                     "non-first fragment by reading payload bytes as a UDP header, and so invents flows)");
+  if (owner)
+    return set_error(NSGPU_EINVAL, "nsgpu_p2p_create_dist: flowmon on a partitioned engine is not modelled (a tracked "
+                     "packet's entry belongs to the rank of its originating node)");
+  const uint32_t N = sc->n_nodes, A = sc->n_apps;
+  bool has_stop = false;
+  for (uint32_t i = 0; i < sc->n_setup; i++) has_stop = has_stop || sc->setup_kind[i] == NSGPU_SETUP_STOP;
+  const uint64_t CAP = FM_NODE_CAP;
+  auto sender = [&](uint32_t k) { return k == NSGPU_APP_ONOFF || k == NSGPU_APP_ECHO_CLIENT || k == NSGPU_APP_UDP_CLIENT; };
+  // the datagrams application a can send before the run (or the application) stops, CAP when nothing bounds them
+  auto bound = [&](uint32_t a) -> uint64_t {
+    int64_t t1 = has_stop ? sc->stop_ns : -1;
+    if (sc->app_stop_ns[a] != 0 && (t1 < 0 || sc->app_stop_ns[a] < t1)) t1 = sc->app_stop_ns[a];
+    const int64_t dur = t1 < 0 ? -1 : std::max<int64_t>(0, t1 - sc->app_start_ns[a]);
+    if (sc->app_kind[a] != NSGPU_APP_ONOFF) {  // MaxPackets, one an Interval
+      uint64_t b = sc->app_count[a];
+      if (dur >= 0 && sc->app_interval_ns[a] > 0) b = std::min<uint64_t>(b, (uint64_t)(dur / sc->app_interval_ns[a]) + 1);
+      return std::min(b, CAP);
+    }
+    // OnOff: MaxBytes (a packet while m_totBytes < m_maxBytes); the rate paces size * 8 bits a packet over the on
+    // time, the residual bits included; each interval is rounded to a ns, so an eighth more and a few for the ends
+    const uint64_t size = sc->app_pkt_size[a];
+    uint64_t b = CAP;
+    if (sc->app_max_bytes[a]) b = std::min<uint64_t>(b, (sc->app_max_bytes[a] + size - 1) / size);
+    if (dur >= 0 && (u128)size * 8 * 1000000000ull >= (u128)sc->app_rate_bps[a] * 8) {  // (intervals of 8 ns or more)
+      const u128 est = (u128)sc->app_rate_bps[a] * (uint64_t)dur / ((u128)size * 8 * 1000000000ull);
+      if (est < CAP) b = std::min<uint64_t>(b, (uint64_t)est + (uint64_t)est / 8 + 16);
+    }
+    return b;
+  };
+  std::vector<uint64_t> cap(N, 0);
+  uint64_t total = 0;
+  for (uint32_t a = 0; a < A; a++) {
+    if (!sender(sc->app_kind[a])) continue;
+    const uint64_t b = bound(a);
+    cap[sc->app_node[a]] += b;
+    total += b;
+    if (sc->app_kind[a] == NSGPU_APP_ECHO_CLIENT) {  // (a reply at most a request)
+      cap[sc->app_dst_node[a]] += b;
+      total += b;
+    }
+  }
+  P.fm_cap.assign(N, 0);
+  for (uint32_t n = 0; n < N; n++)
+    if (cap[n]) P.fm_cap[n] = (uint32_t)std::min(cap[n] + (sc->icmp ? total : 0), CAP);
   return NSGPU_OK;
 }
 
@@ -462,6 +540,7 @@ static int plan_engine(const nsgpu_p2p_scenario *sc, const uint32_t *owner, int 
                          "one: the reference's nodes have one reassembly buffer for all sources)", n, P.frag_flows[n]);
     P.frag_timeout = sc->frag_timeout_ns ? sc->frag_timeout_ns : 30000000000ll;  // Seconds (30) (:61-64)
   }
+  if (int rcf = plan_flowmon(sc, owner, P)) return rcf;
   uint32_t &maxapps = P.maxapps;
   maxapps = 0;
   for (uint32_t n = 0; n < N; n++) maxapps = std::max(maxapps, napps[n + 1]);
@@ -757,6 +836,28 @@ static int create_engine(const nsgpu_p2p_scenario *sc, const uint32_t *owner, in
     TRY(dupload(h, &h->frag_init, img.data(), img.size()));
     TRY(dalloc(h, &M.node_ipid, h->frag_bytes / 4));
     M.frag = 1;
+  } else if (P.flowmon) {
+    // behind the identifications: the FmHdr, the nodes' table bases and sizes, the flows' records and the tracked-
+    // packet tables (nsgpu_p2p_dev.h "per-flow statistics"); header, bases and sizes are the reset image, the rest
+    // starts as zeros
+    std::vector<uint32_t> img(fm_rec_off(N) / 4, 0);
+    uint64_t ne = 0;
+    uint64_t *base = fm_node_base(img.data(), N);
+    uint32_t *cap = fm_node_cap(img.data(), N);
+    for (uint32_t n = 0; n < N; n++) {
+      base[n] = ne;
+      cap[n] = P.fm_cap[n];
+      ne += P.fm_cap[n];
+    }
+    const FmHdr fh{2 * A, N, ne, {}};
+    memcpy(reinterpret_cast<char *>(img.data()) + fm_hdr_off(N), &fh, sizeof(fh));
+    h->frag_words = img.size();
+    h->frag_bytes = fm_bytes(N, 2 * A, ne);
+    h->fm_entries = ne;
+    TRY(dupload(h, &h->frag_init, img.data(), img.size()));
+    TRY(dalloc(h, &M.node_ipid, h->frag_bytes / 4));
+    TRY(dalloc(h, &h->fm_lost, 2 * (size_t)A));
+    M.flowmon = 1;
   } else {
     TRY(dalloc(h, &M.node_ipid, N));
   }
@@ -1022,7 +1123,9 @@ extern "C" int nsgpu_p2p_reset(nsgpu_p2p *h, void *stream) {
   NSGPU_HIP(hipMemsetAsync(M.app_ss_gen, 0, A * sizeof(uint32_t), s));
   NSGPU_HIP(hipMemsetAsync(M.app_residual, 0, A * sizeof(uint32_t), s));
   NSGPU_HIP(hipMemsetAsync(M.app_tot, 0, A * sizeof(uint32_t), s));
-  if (M.frag) {  // (the identifications, the FragNode indices and header, empty FragNodes)
+  // (the identifications, the FragNode indices and header, empty FragNodes; a monitored engine: the tables' bases
+  // and sizes, empty flow records and tracked-packet tables)
+  if (M.frag || M.flowmon) {
     NSGPU_HIP(hipMemsetAsync(M.node_ipid, 0, h->frag_bytes, s));
     NSGPU_HIP(hipMemcpyAsync(M.node_ipid, h->frag_init, h->frag_words * 4, hipMemcpyDeviceToDevice, s));
   } else {
@@ -1083,9 +1186,10 @@ bool launch_kernel(nsgpu_p2p *h, int k, hipStream_t s, bool df, hipEvent_t ev0 =
       else NSGPU_KLAUNCH((k2_pa<false, false>), dim3(pa_grid_rt<false>(h->M)), dim3(TB), s, ev0, ev1, h->M);
       return true;
     case 1:
-      // (a scenario with ports, frag or a receive error model: the extended handlers — the endpoint lookup, UdpClient,
-      // UdpServer, IPv4 fragmentation and reassembly, the error models — nsgpu_p2p_ports.hip)
-      if (h->loss_init || h->M.frag || h->M.errm) launch_handle_ports(h->M, wide, false, df, K2_GRID, s, ev0, ev1);
+      // (a scenario with ports, frag, a receive error model or per-flow statistics: the extended handlers — the
+      // endpoint lookup, UdpClient, UdpServer, IPv4 fragmentation and reassembly, the error models, the flow monitor —
+      // nsgpu_p2p_ports.hip)
+      if (h->loss_init || h->M.frag || h->M.errm || h->M.flowmon) launch_handle_ports(h->M, wide, false, df, K2_GRID, s, ev0, ev1);
       else if (df) NSGPU_KLAUNCH((k2_handle<true, false, true>), dim3(K2_GRID), dim3(HB), s, ev0, ev1, h->M);
       else if (wide) NSGPU_KLAUNCH(k2_handle<true>, dim3(K2_GRID), dim3(HB), s, ev0, ev1, h->M);
       else NSGPU_KLAUNCH(k2_handle<false>, dim3(K2_GRID), dim3(HB), s, ev0, ev1, h->M);
@@ -1224,9 +1328,10 @@ int launch_windows(nsgpu_p2p *h, hipStream_t s, bool df, int nwin = NWIN) {
     for (int k = 0; k < NKERN; k++) launch_kernel(h, k, s, df);
   return NSGPU_OK;
 }
-// The deferred pipeline is used for untraced single wide engines.
+// The deferred pipeline is used for untraced single wide engines.  (Not for a monitored one: a flow's first
+// transmission records the uid of the event being run, which that pipeline's handlers know only provisionally.)
 bool df_usable(const nsgpu_p2p *h) {
-  return h->M.wide && !h->M.dist && !h->M.trace && h->M.maxc <= PROV_MAXC && h->M.n_nodes < (1u << 24);
+  return h->M.wide && !h->M.dist && !h->M.trace && !h->M.flowmon && h->M.maxc <= PROV_MAXC && h->M.n_nodes < (1u << 24);
 }
 // When the deferred pipeline paused itself (a sorted run, a compaction, a host closure) after window n's
 // bookkeeping: window n's dispatch accounting from its records (k2_scan<true, true>: sinfo for the next
@@ -1466,6 +1571,10 @@ static int build_graph(nsgpu_p2p *h, bool df = false, bool tail = false) {
 
 // A run that set the engine's error word: capacity exceeded (the simulation is truncated).
 static int engine_error(uint32_t err) {
+  if (err & ERR_FLOWMON_ID)
+    return set_error(NSGPU_ERANGE, "nsgpu_p2p: a monitored node's IPv4 identification reached the size of its "
+                     "tracked-packet table (flowmon; code %u: at most 65536 datagrams a node, the 16-bit identification "
+                     "would wrap there, which the per-flow statistics do not model)", err);
   return set_error((err & 2048u) ? NSGPU_ERANGE : NSGPU_ENOMEM, "nsgpu_p2p: engine capacity exceeded (code %u: 1 = event pool, 4 = window limit, "
                                  "8 = window cut, 16 = a window's remote events beyond the X2 capacity, 32 = local "
                                  "records, 64 = window records, 256 = deferred uid resolution (internal), 512 = uids "
@@ -1641,6 +1750,9 @@ extern "C" int nsgpu_p2p_setup_uid(nsgpu_p2p *h, uint32_t *uid) {
   if (h->M.frag)
     return set_error(NSGPU_ESTATE, "nsgpu_p2p_setup_uid: a scenario with IPv4 fragmentation (frag) cannot be attached "
                      "to a host-closure runtime");
+  if (h->M.flowmon)
+    return set_error(NSGPU_ESTATE, "nsgpu_p2p_setup_uid: a scenario with per-flow statistics (flowmon) cannot be attached "
+                     "to a host-closure runtime");
   // (... and so does an engine with a receive error model: no test covers the combination)
   if (h->M.errm)
     return set_error(NSGPU_ESTATE, "nsgpu_p2p_setup_uid: a scenario with a receive error model cannot be attached to a "
@@ -1712,6 +1824,9 @@ extern "C" int nsgpu_p2p_inject_send(nsgpu_p2p *h, uint32_t app, uint64_t now, u
     return set_error(NSGPU_ESTATE, "nsgpu_p2p_inject_send: not available in a scenario with IPv4 fragmentation (frag)");
   if (h->M.errm)
     return set_error(NSGPU_ESTATE, "nsgpu_p2p_inject_send: not available in a scenario with a receive error model");
+  // (... nor on a monitored engine: the injected datagram would pass no ReportFirstTx)
+  if (h->M.flowmon)
+    return set_error(NSGPU_ESTATE, "nsgpu_p2p_inject_send: not available in a scenario with per-flow statistics (flowmon)");
   hipStream_t s = h->s;
   if (const int rc = join_in(h, (hipStream_t)stream)) return rc;
   if (const int rc = read_ctl(h)) return rc;
@@ -2044,6 +2159,48 @@ extern "C" int nsgpu_p2p_error_models(nsgpu_p2p *h, nsgpu_error_model_record *ou
   NSGPU_HIP(hipMemcpyAsync(er.data(), em_recs(M.dev, M.n_devices), er.size() * sizeof(EmRec), hipMemcpyDeviceToHost, s));
   NSGPU_HIP(hipStreamSynchronize(s));
   for (const EmRec &r : er) out[r.dev] = nsgpu_error_model_record{r.invoked, r.corrupted};
+  return NSGPU_OK;
+}
+
+// FlowMonitor's FlowStats per flow (zeros for an unmonitored engine): the three parts of each flow's record, and
+// CheckForLostPackets (max_delay_ns) at the run's last dispatched time by the sweep kernel, which only reads.
+extern "C" int nsgpu_p2p_flow_stats(nsgpu_p2p *h, int64_t max_delay_ns, nsgpu_flow_record *out, void *stream) {
+  if (!h || !out) return set_error(NSGPU_EINVAL, "nsgpu_p2p_flow_stats: null");
+  if (max_delay_ns < 0) return set_error(NSGPU_EINVAL, "nsgpu_p2p_flow_stats: negative max_delay_ns");
+  hipStream_t s = (hipStream_t)stream;
+  const P2PDev &M = h->M;
+  const uint32_t F = 2 * M.n_apps;
+  memset(out, 0, (size_t)F * sizeof(*out));
+  if (!M.flowmon || !F) return NSGPU_OK;
+  Ctl c;
+  NSGPU_HIP(hipMemcpyAsync(&c, M.C, sizeof(Ctl), hipMemcpyDeviceToHost, s));
+  NSGPU_HIP(hipStreamSynchronize(s));  // (Simulator::Now () after Run: the sweep's `now`)
+  NSGPU_HIP(hipMemsetAsync(h->fm_lost, 0, (size_t)F * sizeof(unsigned long long), s));
+  launch_flow_sweep(M, (int64_t)c.last_ts, max_delay_ns, h->fm_entries, h->fm_lost, s);
+  NSGPU_HIP(hipGetLastError());
+  std::vector<FmTx> tx(F);
+  std::vector<FmRx> rx(F);
+  std::vector<FmDrop> dr(F);
+  std::vector<unsigned long long> lost(F);
+  static_assert(sizeof(FmTx) == sizeof(FmRx) && sizeof(FmRx) == sizeof(FmDrop), "the flows' records are one copy");
+  NSGPU_HIP(hipMemcpyAsync(tx.data(), fm_tx(M.node_ipid, M.n_nodes), (size_t)F * sizeof(FmTx), hipMemcpyDeviceToHost, s));
+  NSGPU_HIP(hipMemcpyAsync(rx.data(), fm_rx(M.node_ipid, M.n_nodes, F), (size_t)F * sizeof(FmRx), hipMemcpyDeviceToHost, s));
+  NSGPU_HIP(hipMemcpyAsync(dr.data(), fm_drops(M.node_ipid, M.n_nodes, F), (size_t)F * sizeof(FmDrop), hipMemcpyDeviceToHost, s));
+  NSGPU_HIP(hipMemcpyAsync(lost.data(), h->fm_lost, (size_t)F * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+  NSGPU_HIP(hipStreamSynchronize(s));
+  for (uint32_t f = 0; f < F; f++) {
+    nsgpu_flow_record &o = out[f];
+    o.tx_packets = tx[f].packets, o.tx_bytes = tx[f].bytes;
+    o.time_first_tx_ns = tx[f].t_first, o.time_last_tx_ns = tx[f].t_last;
+    o.first_tx_ts = tx[f].first_ts, o.first_tx_uid = tx[f].first_uid;
+    o.rx_packets = rx[f].packets, o.rx_bytes = rx[f].bytes;
+    o.delay_sum_ns = rx[f].delay_sum, o.jitter_sum_ns = rx[f].jitter_sum, o.last_delay_ns = rx[f].last_delay;
+    o.time_first_rx_ns = rx[f].t_first, o.time_last_rx_ns = rx[f].t_last;
+    o.times_forwarded = rx[f].forwarded;
+    o.lost_packets = dr[f].lost + lost[f];
+    for (uint32_t k = 0; k < NSGPU_FLOW_DROP_REASONS; k++)
+      o.packets_dropped[k] = dr[f].packets[k], o.bytes_dropped[k] = dr[f].bytes[k];
+  }
   return NSGPU_OK;
 }
 

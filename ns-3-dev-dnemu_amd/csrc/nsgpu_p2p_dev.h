@@ -320,7 +320,7 @@ struct P2PDev {
   // events (0 between windows), [1 .. NSLOT] their first slots (one line per node, not two)
   uint32_t *node_tab;
   // partitioned run (dist != 0): this engine owns the nodes n with owner[n] == rank
-  uint32_t dist, rank, nranks, pad_d;
+  uint32_t dist, rank, nranks, flowmon;  // flowmon: per-flow statistics on (scenario flowmon: the extended handlers)
   const uint32_t *owner;
   uint64_t *x0_send, *x0_recv;  // X0: 16 B per rank (x0_send points at the run control's X0 payload)
   uint64_t *xk_send, *xk_recv;  // the cut's exchange (host-driven): one rank's largest fitting key (16 B)
@@ -656,6 +656,155 @@ __device__ __noinline__ bool em_is_corrupt(DevRec *dev, uint32_t n_devices, uint
   if (corrupt) r->corrupted++;
   return corrupt;
 }
+
+// ---------------- per-flow statistics (nsgpu_p2p_scenario.flowmon) ----------------
+// FlowMonitor's FlowStats (flow-monitor.cc:121-267), fed where Ipv4FlowProbe hooks Ipv4L3Protocol's trace sources
+// (ipv4-flow-probe.cc:192-346; ipv4-l3-protocol.cc:505,618,835,838,861) and the devices' TxQueue/Drop.
+// Ipv4FlowClassifier::Classify (ipv4-flow-classifier.cc:102-155) accepts UDP (and TCP) only: an ICMP message reports
+// nothing.  In this subset a five-tuple is one sending application, so the flow of a descriptor is its application,
+// or n_apps + it for an echo reply (the reverse tuple); the packet id is the IPv4 identification, the size the IPv4
+// length, which is the descriptor's size wherever the hooks sit (the PppHeader is not on).
+// m_trackedPackets becomes one table per ORIGINATING node, indexed by that node's identification (a scenario
+// without frag keeps the whole counter in the descriptor): create sizes it by a bound on what the node can send, at
+// most 65,536 entries, and a first transmission whose identification is outside fails the run (ERR_FLOWMON_ID)
+// before anything is written.  An entry is read and written only by the node that holds the packet, and a packet
+// changes node across a window boundary only (a Receive's delay is at least the lookahead): plain loads and stores.
+// A flow's record is three 128-B lines by owner: FmTx, written by the sender's node; FmRx, by the destination's, in
+// that node's event order (the jitter needs the previous delay); FmDrop, commutative counts added with atomics from
+// wherever a drop happens.  Everything lies behind node_ipid in its allocation (P2PDev takes no further pointer, see
+// hub_slot; frag, which also lives there, is refused with flowmon): [N] identifications, then at 128-B bounds the
+// FmHdr, [N] table bases (entries), [N] table sizes, the FmTx / FmRx / FmDrop arrays (2 n_apps each), the entries.
+constexpr uint32_t ERR_FLOWMON_ID = 16384u;  // the engine's error bit: a monitored node's identification left its table
+constexpr uint32_t FM_NODE_CAP = 65536u;     // entries a node at most: the identification has 16 bits
+struct FmEnt {  // FlowMonitor::TrackedPacket, and the flow + 1 while it is tracked (0: erased, or never sent)
+  int64_t first, last;
+  uint32_t fwd, flow1, size, pad;
+};
+static_assert(sizeof(FmEnt) == 32, "FmEnt");
+struct FmTx {
+  uint64_t packets, bytes;
+  int64_t t_first, t_last;
+  uint64_t first_ts;  // the event that made the flow's first ReportFirstTx: (ts, uid)
+  uint32_t first_uid, pad;
+  uint64_t pad2[10];
+};
+struct FmRx {
+  uint64_t packets, bytes;
+  int64_t delay_sum, jitter_sum, last_delay, t_first, t_last;
+  uint64_t forwarded;
+  uint64_t pad[8];
+};
+struct FmDrop {
+  unsigned long long lost, packets[NSGPU_FLOW_DROP_REASONS], bytes[NSGPU_FLOW_DROP_REASONS];
+  uint64_t pad[7];
+};
+struct FmHdr {
+  uint32_t n_flows, n_nodes;
+  uint64_t n_entries;
+  uint64_t pad[14];
+};
+static_assert(sizeof(FmTx) == 128 && sizeof(FmRx) == 128 && sizeof(FmDrop) == 128 && sizeof(FmHdr) == 128,
+              "one 128-B line a part: no line is written from two nodes");
+__host__ __device__ __forceinline__ size_t fm_hdr_off(uint32_t n_nodes) {  // bytes behind node_ipid
+  return ((size_t)n_nodes * 4 + 127) / 128 * 128;
+}
+__host__ __device__ __forceinline__ size_t fm_rec_off(uint32_t n_nodes) {
+  return (fm_hdr_off(n_nodes) + sizeof(FmHdr) + (size_t)n_nodes * 12 + 127) / 128 * 128;
+}
+__host__ __device__ __forceinline__ size_t fm_bytes(uint32_t n_nodes, uint32_t n_flows, uint64_t n_entries) {
+  return fm_rec_off(n_nodes) + (size_t)n_flows * 3 * 128 + (size_t)n_entries * sizeof(FmEnt);
+}
+__host__ __device__ __forceinline__ uint64_t *fm_node_base(uint32_t *node_ipid, uint32_t n_nodes) {
+  return reinterpret_cast<uint64_t *>(reinterpret_cast<char *>(node_ipid) + fm_hdr_off(n_nodes) + sizeof(FmHdr));
+}
+__host__ __device__ __forceinline__ uint32_t *fm_node_cap(uint32_t *node_ipid, uint32_t n_nodes) {
+  return reinterpret_cast<uint32_t *>(fm_node_base(node_ipid, n_nodes) + n_nodes);
+}
+__host__ __device__ __forceinline__ FmTx *fm_tx(uint32_t *node_ipid, uint32_t n_nodes) {
+  return reinterpret_cast<FmTx *>(reinterpret_cast<char *>(node_ipid) + fm_rec_off(n_nodes));
+}
+__host__ __device__ __forceinline__ FmRx *fm_rx(uint32_t *node_ipid, uint32_t n_nodes, uint32_t n_flows) {
+  return reinterpret_cast<FmRx *>(fm_tx(node_ipid, n_nodes) + n_flows);
+}
+__host__ __device__ __forceinline__ FmDrop *fm_drops(uint32_t *node_ipid, uint32_t n_nodes, uint32_t n_flows) {
+  return reinterpret_cast<FmDrop *>(fm_rx(node_ipid, n_nodes, n_flows) + n_flows);
+}
+__host__ __device__ __forceinline__ FmEnt *fm_ents(uint32_t *node_ipid, uint32_t n_nodes, uint32_t n_flows) {
+  return reinterpret_cast<FmEnt *>(fm_drops(node_ipid, n_nodes, n_flows) + n_flows);
+}
+// The monitor's functions are out of line and read the device-resident descriptor (cold paths, above): the handlers
+// of an unmonitored engine hold the test of M.flowmon and a call.
+// Classify + the tracked entry of datagram p (null: its identification is outside its node's table).
+__device__ __forceinline__ FmEnt *fm_entry(const P2PDev &M, const Pkt &p, uint32_t *flow) {
+  const uint32_t fa = p.app & NSGPU_PKT_APP;
+  const bool reply = (p.app & NSGPU_PKT_REPLY) != 0;
+  *flow = reply ? M.n_apps + fa : fa;
+  const uint32_t o = reply ? M.app_dst_node[fa] : M.app_node[fa];  // (the reply is the server's node's datagram)
+  if (p.ipid >= fm_node_cap(M.node_ipid, M.n_nodes)[o]) return nullptr;
+  return fm_ents(M.node_ipid, M.n_nodes, 2 * M.n_apps) + fm_node_base(M.node_ipid, M.n_nodes)[o] + p.ipid;
+}
+// SendOutgoingLogger -> ReportFirstTx (flow-monitor.cc:121-146): Ipv4L3Protocol::Send after BuildHeader, before
+// SendRealOut (:618).  (now, uid): the event being run.
+__device__ __noinline__ void fm_first_tx(const P2PDev *G, Pkt p, uint64_t now, uint32_t uid) {
+  const P2PDev &M = mdev_ref(G);
+  uint32_t flow;
+  FmEnt *e = fm_entry(M, p, &flow);
+  if (!e) {  // (with create's bound: the 16-bit identification would wrap; the overwrite-on-wrap is not modelled)
+    atomicOr(M.error, ERR_FLOWMON_ID);
+    return;
+  }
+  *e = FmEnt{(int64_t)now, (int64_t)now, 0u, flow + 1u, p.size, 0u};
+  FmTx *t = fm_tx(M.node_ipid, M.n_nodes) + flow;
+  t->bytes += p.size;
+  if (t->packets++ == 0) {
+    t->t_first = (int64_t)now;
+    t->first_ts = now;
+    t->first_uid = uid;
+  }
+  t->t_last = (int64_t)now;
+}
+// ForwardLogger -> ReportForwarding (:149-170): IpForward after the TTL check (:838).
+__device__ __noinline__ void fm_forward(const P2PDev *G, Pkt p, uint64_t now) {
+  const P2PDev &M = mdev_ref(G);
+  uint32_t flow;
+  FmEnt *e = fm_entry(M, p, &flow);
+  if (!e || e->flow1 != flow + 1u) return;  // "not known to be transmitted"
+  e->fwd++;
+  e->last = (int64_t)now;
+}
+// ForwardUpLogger -> ReportLastRx (:173-234): LocalDeliver (:861), before the UDP endpoint lookup.
+__device__ __noinline__ void fm_last_rx(const P2PDev *G, Pkt p, uint64_t now) {
+  const P2PDev &M = mdev_ref(G);
+  uint32_t flow;
+  FmEnt *e = fm_entry(M, p, &flow);
+  if (!e || e->flow1 != flow + 1u) return;
+  FmRx *r = fm_rx(M.node_ipid, M.n_nodes, 2 * M.n_apps) + flow;
+  const int64_t delay = (int64_t)now - e->first;
+  r->delay_sum += delay;
+  if (r->packets > 0) {
+    const int64_t jitter = r->last_delay - delay;
+    r->jitter_sum += jitter > 0 ? jitter : -jitter;
+  }
+  r->last_delay = delay;
+  r->bytes += p.size;
+  if (r->packets++ == 0) r->t_first = (int64_t)now;
+  r->t_last = (int64_t)now;
+  r->forwarded += e->fwd;
+  e->flow1 = 0;  // m_trackedPackets.erase
+}
+// DropLogger / QueueDropLogger -> ReportDrop (:236-267): counted whether or not the packet is tracked, then erased.
+__device__ __noinline__ void fm_drop(const P2PDev *G, Pkt p, uint32_t reason) {
+  const P2PDev &M = mdev_ref(G);
+  uint32_t flow;
+  FmEnt *e = fm_entry(M, p, &flow);
+  FmDrop *d = fm_drops(M.node_ipid, M.n_nodes, 2 * M.n_apps) + flow;
+  atomicAdd(&d->lost, 1ull);
+  atomicAdd(&d->packets[reason], 1ull);
+  atomicAdd(&d->bytes[reason], (unsigned long long)p.size);
+  if (e && e->flow1 == flow + 1u) e->flow1 = 0;
+}
+// The hooks as the handlers call them: nothing for an unmonitored engine or an ICMP message.
+__device__ __forceinline__ bool fm_on(const P2PDev &M, const Pkt &p) { return M.flowmon && !(p.app & NSGPU_PKT_ICMP); }
 
 struct Emit {
   uint64_t now;
@@ -1141,6 +1290,9 @@ __device__ __forceinline__ NodeOut node_part_full(const P2PDev &M, Emit &E, uint
       // LocalDeliver -> UdpL4Protocol::Receive (udp-l4-protocol.cc:312-407): the bound endpoint is the
       // client's own socket for an echo reply, else the node's PacketSink / UdpEchoServer.  An ICMP error
       // ends in Icmpv4L4Protocol::Receive -> UdpL4Protocol::ReceiveIcmp (no event, no counter).
+      if constexpr (PORTS) {  // m_localDeliverTrace (:861): a datagram no endpoint takes counts as received too
+        if (fm_on(M, p)) fm_last_rx(mdev_of(M.C), p, E.now);
+      }
       int32_t k = reply ? (int32_t)fa : sink;
       // (per flow: not for an ICMP error, whose word holds flag bits above the flow and finds no endpoint anyway)
       if (PORTS && !reply && sink == EP_BY_FLOW)
@@ -1179,8 +1331,17 @@ __device__ __forceinline__ NodeOut node_part_full(const P2PDev &M, Emit &E, uint
       if (out == 0xffffffffu) {
         hs.no_route++;
         trace_ip_drop(M, E, a, p);  // DROP_NO_ROUTE
+        if constexpr (PORTS) {
+          if (fm_on(M, p)) fm_drop(mdev_of(M.C), p, NSGPU_FLOW_DROP_NO_ROUTE);
+        }
       } else {
         p.ttl -= 1;  // IpForward (:815-841)
+        if constexpr (PORTS) {  // m_dropTrace (:835, with or without an ICMP error) or m_unicastForwardTrace (:838)
+          if (fm_on(M, p)) {
+            if ((p.ttl & 0xffu) == 0) fm_drop(mdev_of(M.C), p, NSGPU_FLOW_DROP_TTL_EXPIRE);
+            else fm_forward(mdev_of(M.C), p, E.now);
+          }
+        }
         if ((p.ttl & 0xffu) == 0) {
           hs.ttl_drops++;  // (no ICMP about an ICMP message)
           if (M.icmp && !(p.app & NSGPU_PKT_ICMP)) act = icmp_act(M, n, icmp_error(p, false), hs);
@@ -1214,6 +1375,9 @@ __device__ __forceinline__ NodeOut node_part_full(const P2PDev &M, Emit &E, uint
       } else {
         p.ipid = M.node_ipid[an]++ & idm;
         act = Act{ACT_SEND, out, p};
+        if constexpr (PORTS) {  // m_sendOutgoingTrace (:618)
+          if (M.flowmon) fm_first_tx(mdev_of(M.C), p, E.now, E.uid);
+        }
       }
       const uint32_t sent = ++M.app_tot[a];  // ++m_sent
       if (sent < M.app_count[a]) {           // ScheduleTransmit (m_interval)
@@ -1234,6 +1398,9 @@ __device__ __forceinline__ NodeOut node_part_full(const P2PDev &M, Emit &E, uint
       } else {  // ++m_sent only when Send returned >= 0
         p.ipid = M.node_ipid[an]++ & idm;
         act = Act{ACT_SEND, out, p};
+        if constexpr (PORTS) {  // m_sendOutgoingTrace (:618)
+          if (M.flowmon) fm_first_tx(mdev_of(M.C), p, E.now, E.uid);
+        }
         M.app_tot[a] = ++sent;
         M.appc[a].tx_packets++;
         M.appc[a].tx_bytes += sz;
@@ -1257,6 +1424,9 @@ __device__ __forceinline__ NodeOut node_part_full(const P2PDev &M, Emit &E, uint
       } else {
         p.ipid = M.node_ipid[an]++ & idm;  // Ipv4L3Protocol::BuildHeader: SetIdentification (m_identification++)
         act = Act{ACT_SEND, out, p};
+        if constexpr (PORTS) {  // m_sendOutgoingTrace (:618)
+          if (M.flowmon) fm_first_tx(mdev_of(M.C), p, E.now, E.uid);
+        }
       }
       M.app_tot[a] += sz;
       M.app_last_start[a] = E.now;
@@ -1341,6 +1511,9 @@ __device__ __forceinline__ NodeOut node_part_full(const P2PDev &M, Emit &E, uint
             } else {
               r.ipid = M.node_ipid[an]++ & idm;
               act = Act{ACT_SEND, out, r};
+              if constexpr (PORTS) {  // m_sendOutgoingTrace (:618)
+                if (M.flowmon) fm_first_tx(mdev_of(M.C), r, E.now, E.uid);
+              }
             }
           }
         }
@@ -1458,6 +1631,9 @@ __device__ __forceinline__ NodeOut node_part(const P2PDev &M, Emit &E, uint32_t 
       bool plain = !(p.app & (NSGPU_PKT_REPLY | NSGPU_PKT_ICMP)) && sink >= 0;
       if constexpr (PORTS) plain = plain && !(M.frag && (p.ipid >> NSGPU_PKT_FRAG_SHIFT) != 0);
       if (plain && (M.app_flags[sink] & 2u) && M.app_kind[sink] != NSGPU_APP_ECHO_SERVER) {
+        if constexpr (PORTS) {  // m_localDeliverTrace (:861); every other delivery: node_part_full's
+          if (M.flowmon) fm_last_rx(mdev_of(M.C), p, E.now);
+        }
         E.child(0, E.ctx, K_FWD_UP, (uint32_t)sink, p);
         return NodeOut{noact, nopost, false, 0};
       }
@@ -1465,6 +1641,9 @@ __device__ __forceinline__ NodeOut node_part(const P2PDev &M, Emit &E, uint32_t 
       const uint32_t out = hint.valid ? route_at(M, n, hint.slot) : route_of(M, n, p);
       if (out != 0xffffffffu && ((p.ttl - 1u) & 0xffu) != 0) {  // IpForward (:815-841)
         p.ttl -= 1;
+        if constexpr (PORTS) {  // m_unicastForwardTrace (:838); a drop instead: node_part_full's
+          if (fm_on(M, p)) fm_forward(mdev_of(M.C), p, E.now);
+        }
         return NodeOut{Act{ACT_SEND, out, p}, nopost, false, 0};
       }
     }

@@ -18,6 +18,41 @@ void launch_handle_ports(const P2PDev &M, bool wide, bool xl, bool df, int grid,
   else if (wide) hipExtLaunchKernelGGL((k2_handle<true, false, false, true>), g, b, 0, s, ev0, ev1, 0, M);
   else hipExtLaunchKernelGGL((k2_handle<false, false, false, true>), g, b, 0, s, ev0, ev1, 0, M);
 }
+
+// FlowMonitor::CheckForLostPackets (maxDelay) (flow-monitor.cc:276-300) at `now`, without the erase: lost[f] += the
+// entries of flow f still tracked with now - lastSeenTime >= max_delay.  A grid-stride pass over every node's table
+// (the tables are contiguous); the tables are only read, so the answer for another delay is another launch.  A
+// wave's hits are summed per flow before the atomic: a table's neighbours are one node's datagrams, a few flows.
+__global__ __launch_bounds__(TB) void k_flow_sweep(const FmEnt *ents, uint64_t n_entries, int64_t now, int64_t max_delay,
+                                                   unsigned long long *lost) {
+  const uint64_t stride = (uint64_t)gridDim.x * TB;
+  const int lane = threadIdx.x & 63;
+  for (uint64_t i0 = (uint64_t)blockIdx.x * TB; i0 < n_entries; i0 += stride) {  // (block-uniform bound)
+    const uint64_t i = i0 + threadIdx.x;
+    uint32_t flow1 = 0;
+    if (i < n_entries) {
+      const FmEnt e = ents[i];
+      if (e.flow1 != 0 && now - e.last >= max_delay) flow1 = e.flow1;
+    }
+    uint64_t pend = __ballot(flow1 != 0);
+    while (pend) {  // (wave-uniform: one round per distinct flow among the wave's hits)
+      const int lead = __ffsll((unsigned long long)pend) - 1;
+      const uint32_t f1 = rl32(flow1, lead);
+      const bool same = flow1 == f1;
+      const uint32_t cnt = wave_sum32(same ? 1u : 0u);
+      if (lane == lead) atomicAdd(&lost[f1 - 1], (unsigned long long)cnt);
+      pend &= ~__ballot(same);
+    }
+  }
+}
+void launch_flow_sweep(const P2PDev &M, int64_t now, int64_t max_delay, uint64_t n_entries, unsigned long long *lost,
+                       hipStream_t s) {
+  if (!n_entries) return;
+  // (the pool sweeps' sizing: GRID_POOL blocks, GRID_POOL_BIG above 2^20 entries)
+  const int grid = n_entries > (1ull << 20) ? GRID_POOL_BIG : GRID_POOL;
+  hipLaunchKernelGGL(k_flow_sweep, dim3(grid), dim3(TB), 0, s, fm_ents(M.node_ipid, M.n_nodes, 2 * M.n_apps), n_entries,
+                     now, max_delay, lost);
+}
 }  // namespace nsgpu
 
 using namespace nsgpu;

@@ -1076,6 +1076,9 @@ struct DevCache {
 
 // device_act with the device state in a register cache (the same steps, point-to-point-net-device.cc
 // :206-269,462-518, queue.cc:61-97, drop-tail-queue.cc:83-100).
+// EXT (the extended handlers): a monitored engine reports the DropTail drop of a UDP datagram (QueueDropLogger,
+// ipv4-flow-probe.cc:324-346: the tagged packet, whichever queue on its path drops it; act.p has the tagged size).
+template <bool EXT = false>
 __device__ __forceinline__ void device_act_cached(const P2PDev &M, Emit &E, const Act &act, DevCache &D) {
   if (act.op == ACT_NONE) return;
   if (D.d != act.dev) {
@@ -1094,6 +1097,9 @@ __device__ __forceinline__ void device_act_cached(const P2PDev &M, Emit &E, cons
       trace_call(M, E, NSGPU_TR_DROP, d, p);
       D.q[2]++;
       D.q[3] += p.size;
+      if constexpr (EXT) {
+        if (fm_on(M, act.p)) fm_drop(mdev_of(M.C), act.p, NSGPU_FLOW_DROP_QUEUE);
+      }
     } else {
       trace_call(M, E, NSGPU_TR_ENQUEUE, d, p);
       D.q[0]++;
@@ -1152,7 +1158,7 @@ __device__ __forceinline__ void device_step(const P2PDev &M, Emit &E, const Act 
         off += FRAG_PART;
         nf++;
       }
-      device_act_cached(M, E, f, D);
+      device_act_cached<true>(M, E, f, D);
     } while (more);
     if (fr) {
       M.dev[act.dev].frag_dgrams++;
@@ -1695,8 +1701,17 @@ __device__ __forceinline__ void hub_help(const P2PDev &M, Ctl &C, uint32_t i0, u
             if (out == 0xffffffffu) {
               hs.no_route++;
               trace_ip_drop(M, E, sp.a, p);
+              if constexpr (PORTS) {
+                if (fm_on(M, p)) fm_drop(mdev_of(M.C), p, NSGPU_FLOW_DROP_NO_ROUTE);
+              }
             } else {
               p.ttl -= 1;
+              if constexpr (PORTS) {  // (the tracked entry is the packet's: its holder's alone, in any lane)
+                if (fm_on(M, p)) {
+                  if ((p.ttl & 0xffu) == 0) fm_drop(mdev_of(M.C), p, NSGPU_FLOW_DROP_TTL_EXPIRE);
+                  else fm_forward(mdev_of(M.C), p, E.now);
+                }
+              }
               // (ICMP off: a stateless event; with ports the word's upper bits may hold a sequence number)
               if (PORTS ? (p.ttl & 0xffu) == 0 : p.ttl == 0) {
                 hs.ttl_drops++;
@@ -1972,8 +1987,17 @@ __device__ __forceinline__ void hub_node(const P2PDev &M, Ctl &C, uint32_t c, ui
             if (out == 0xffffffffu) {
               hs.no_route++;
               trace_ip_drop(M, E, a, p);
+              if constexpr (PORTS) {
+                if (fm_on(M, p)) fm_drop(mdev_of(M.C), p, NSGPU_FLOW_DROP_NO_ROUTE);
+              }
             } else {
               p.ttl -= 1;
+              if constexpr (PORTS) {  // (the tracked entry is the packet's: its holder's alone, in any lane)
+                if (fm_on(M, p)) {
+                  if ((p.ttl & 0xffu) == 0) fm_drop(mdev_of(M.C), p, NSGPU_FLOW_DROP_TTL_EXPIRE);
+                  else fm_forward(mdev_of(M.C), p, E.now);
+                }
+              }
               if (PORTS ? (p.ttl & 0xffu) == 0 : p.ttl == 0) {  // (ICMP off: stateless_event)
                 hs.ttl_drops++;
                 trace_ip_drop(M, E, out, Pkt{p.app, p.ipid, p.size, PORTS ? p.ttl + 1u : 1u});
@@ -2082,6 +2106,8 @@ __device__ __forceinline__ void hub_node(const P2PDev &M, Ctl &C, uint32_t c, ui
   // (not in a wide window: a TransmitStart there makes a local record the scan cannot place)
   bool fast = dmin != NOSRC && dmin == dmax && inl == 0 && (!WIDE || hc.lim == 0) && M.dev[dmin].qmax >= 1 &&
               !(M.dev[dmin].busy == 0 && M.dev[dmin].cnt != 0);
+  // (a monitored engine: the scan resolves the queue's drops without the dropped descriptors' reports; the serial pass)
+  if constexpr (PORTS) fast = fast && !M.flowmon;
   X1Acc xa{0, 0, 0};
   if (fast) fast = hub_device_scan<WIDE>(M, E, c, dmin, gs, gk, n, j0s, j1s, tmin, hs, xa, hops, hsl);
   if (!fast) {

@@ -54,6 +54,7 @@ NsgpuP2pScenario::NsgpuP2pScenario ()
     m_icmp (true),
     m_frag (false),
     m_fragTimeout (0),
+    m_flowStats (false),
     m_rngSeed (0),
     m_rngRun (0),
     m_stop (-1),
@@ -255,6 +256,29 @@ NsgpuP2pScenario::GetErrorModel (uint32_t dev, uint32_t &invoked, uint32_t &corr
   NSGPU_TRY (nsgpu_p2p_error_models (m_engine, &rec[0], 0));
   invoked = rec[dev].invoked;
   corrupted = rec[dev].corrupted;
+}
+
+void
+NsgpuP2pScenario::EnableFlowStats (void)
+{
+  if (m_engine != 0)
+    {
+      NS_FATAL_ERROR ("NsgpuP2pScenario::EnableFlowStats: call it before CreateEngine");
+    }
+  m_flowStats = true;
+}
+
+std::vector<nsgpu_flow_record>
+NsgpuP2pScenario::GetFlowStats (Time maxDelay) const
+{
+  if (m_engine == 0)
+    {
+      NS_FATAL_ERROR ("NsgpuP2pScenario::GetFlowStats: no engine");
+    }
+  std::vector<nsgpu_flow_record> rec (2 * m_app.size () + 1);  // (never empty: its address is taken)
+  NSGPU_TRY (nsgpu_p2p_flow_stats (m_engine, maxDelay.GetNanoSeconds (), &rec[0], 0));
+  rec.resize (2 * m_app.size ());
+  return rec;
 }
 
 namespace {
@@ -782,7 +806,6 @@ NsgpuP2pScenario::Fill (void)
   sc.stop_ns = m_stop;
   sc.icmp = m_icmp ? 1u : 0u;
   sc.frag = m_frag ? 1u : 0u;
-  sc.pad_frag_ = 0;
   sc.frag_timeout_ns = m_fragTimeout;
   if (!m_em.empty ())
     {
@@ -804,6 +827,7 @@ NsgpuP2pScenario::Fill (void)
       sc.em_list_off = &m_cEmOff[0], sc.em_list = &m_cEmList[0];
       sc.rng_seed = m_rngSeed, sc.rng_run = m_rngRun;
     }
+  sc.flowmon = m_flowStats ? 1u : 0u;
   sc.n_setup = m_setup.size ();
   sc.setup_kind = m_cSk.empty () ? 0 : &m_cSk[0];
   sc.setup_index = m_cSi.empty () ? 0 : &m_cSi[0];

@@ -85,6 +85,17 @@ public:
   /* IsCorrupt calls on engine device `dev`'s enabled model and the frames it declared corrupt, as the engine counts
    * them now */
   void GetErrorModel (uint32_t dev, uint32_t &invoked, uint32_t &corrupted) const;
+  /* FlowMonitor's per-flow statistics (flow-monitor.cc:121-300, ipv4-flow-probe.cc:192-346), accumulated by the
+   * engine during Run: call before CreateEngine.  The run itself is unchanged — this object installs no FlowMonitor,
+   * so the uids a real one's own events would take (StartRightNow, its check every simulated second) are not taken.
+   * Not with SetFragmentation, and not for an engine a host-closure runtime adopts (AdoptInto): both end in a
+   * fatal error at CreateEngine / AdoptInto.  GetFlowStats: 2 x applications records — flow a = application a's
+   * datagrams, flow applications + a = the echo replies to UdpEchoClient a (zeros for a flow that sent nothing);
+   * FlowIds follow the order of first_tx_ts / first_tx_uid.  lost_packets includes CheckForLostPackets (maxDelay) now
+   * (Seconds (10): the MaxPerHopDelay attribute's default).  Histograms, per-probe statistics and the XML file are
+   * not produced. */
+  void EnableFlowStats (void);
+  std::vector<nsgpu_flow_record> GetFlowStats (Time maxDelay = Seconds (10)) const;
   /* Ipv4GlobalRoutingHelper::PopulateRoutingTables on the GPU (nsgpu_route_global): next hops towards every
    * flow destination and, with ICMP, every sender.  With every device addressed the ties are global
    * routing's (lowest peer address, then interface); an unaddressed topology takes the lowest device. */
@@ -169,6 +180,7 @@ private:
   bool m_icmp;
   bool m_frag;
   int64_t m_fragTimeout;                                // FragmentExpirationTimeout (ns; 0: the default)
+  bool m_flowStats;                                     // EnableFlowStats
   uint32_t m_rngSeed, m_rngRun;                         // RngSeed / RngRun of the Rate error models' streams (0: 1)
   int64_t m_stop;
   bool m_firstLink;

@@ -165,6 +165,7 @@ SIGNATURES = {
     "nsgpu_p2p_frag_stats": (C.c_int, [_vp, _vp, _vp]),
     "nsgpu_loss_counter_run": (C.c_int, [C.c_uint32, _vp, C.c_uint64, _vp, C.c_int, _vp]),
     "nsgpu_p2p_error_models": (C.c_int, [_vp, _vp, _vp]),
+    "nsgpu_p2p_flow_stats": (C.c_int, [_vp, C.c_int64, _vp, _vp]),
     "nsgpu_rng_stream_run": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, _vp, C.c_int, _vp]),
     "nsgpu_error_model_thresholds": (C.c_int, [C.c_uint32, C.c_double, _vp]),
     "nsgpu_p2p_setup_uid": (C.c_int, [_vp, _vp]),

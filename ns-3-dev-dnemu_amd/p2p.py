@@ -48,7 +48,7 @@ class ScenarioStruct(C.Structure):
         ("route_default", C.c_void_p), ("route_exc_off", C.c_void_p), ("route_exc_slot", C.c_void_p),
         ("route_exc_dev", C.c_void_p), ("uid_first", C.c_uint32), ("pad_uid_", C.c_uint32),
         ("app_port", C.c_void_p), ("app_remote_port", C.c_void_p), ("app_loss_window", C.c_void_p),
-        ("frag", C.c_uint32), ("pad_frag_", C.c_uint32), ("frag_timeout_ns", C.c_int64),
+        ("frag", C.c_uint32), ("flowmon", C.c_uint32), ("frag_timeout_ns", C.c_int64),
         ("dev_em_kind", C.c_void_p), ("dev_em_enabled", C.c_void_p), ("dev_em_unit", C.c_void_p),
         ("dev_em_rate", C.c_void_p), ("dev_em_stream", C.c_void_p), ("em_list_off", C.c_void_p),
         ("em_list", C.c_void_p), ("rng_seed", C.c_uint32), ("rng_run", C.c_uint32),
@@ -77,12 +77,29 @@ EM_NONE, EM_RECEIVE_LIST, EM_RATE, EM_LIST = 0, 1, 2, 3
 EM_UNITS = {"pkt": 0, "byte": 1, "bit": 2}
 EM_MAX_TABLES, EM_TABLE_SIZE = 16, 1503
 ERROR_MODEL_DTYPE = np.dtype([("invoked", "<u4"), ("corrupted", "<u4")])
+# per-flow statistics (Scenario (flowmon=True)): nsgpu_flow_record, FlowMonitor::FlowStats without the histograms;
+# NSGPU_FLOW_DROP_*: the indices of packets_dropped / bytes_dropped (Ipv4FlowProbe::DropReason)
+FLOW_DROP_NO_ROUTE, FLOW_DROP_TTL_EXPIRE, FLOW_DROP_BAD_CHECKSUM, FLOW_DROP_QUEUE = 0, 1, 2, 3
+FLOW_RECORD_DTYPE = np.dtype([("tx_packets", "<u8"), ("tx_bytes", "<u8"), ("rx_packets", "<u8"), ("rx_bytes", "<u8"),
+                              ("delay_sum_ns", "<i8"), ("jitter_sum_ns", "<i8"), ("last_delay_ns", "<i8"),
+                              ("time_first_tx_ns", "<i8"), ("time_last_tx_ns", "<i8"), ("time_first_rx_ns", "<i8"),
+                              ("time_last_rx_ns", "<i8"), ("times_forwarded", "<u8"), ("lost_packets", "<u8"),
+                              ("packets_dropped", "<u8", (4,)), ("bytes_dropped", "<u8", (4,)),
+                              ("first_tx_ts", "<u8"), ("first_tx_uid", "<u4"), ("pad_", "<u4")])
+# what Engine.flow_stats returns: the record, the flow's index (application a, or n_apps + a for the replies to echo
+# client a) and its FlowId (1-based, in the order of the flows' first transmissions)
+FLOW_STATS_DTYPE = np.dtype([("flow_id", "<u4"), ("flow", "<u4")] + FLOW_RECORD_DTYPE.descr)
+MAX_PER_HOP_DELAY_NS = 10 * 10**9  # FlowMonitor's MaxPerHopDelay attribute (flow-monitor.cc:46-49)
 
 
 class Scenario:
     """Arrays of a nsgpu_p2p_scenario plus the order of setup-time Schedule calls."""
 
-    def __init__(self, n_nodes, icmp=False, ports=False, frag=False, frag_timeout_ns=0, rng_seed=0, rng_run=0):
+    def __init__(self, n_nodes, icmp=False, ports=False, frag=False, frag_timeout_ns=0, rng_seed=0, rng_run=0,
+                 flowmon=False):
+        # per-flow statistics accumulated on the device (nsgpu_p2p_scenario.flowmon): Engine.flow_stats; not with
+        # frag, not on partitioned engines
+        self.flowmon = flowmon
         # receive error models (PointToPointNetDevice::SetReceiveErrorModel): device -> dict (kind "list" / "rate",
         # enabled, packets | rate, unit, stream); RngSeed / RngRun of the Rate models' streams (0: the default, 1)
         self.error_models = {}
@@ -362,6 +379,7 @@ class Scenario:
                 setattr(s, k, v.ctypes.data)
             arrays.update(em)
         s.rng_seed, s.rng_run = self.rng_seed, self.rng_run
+        s.flowmon = 1 if getattr(self, "flowmon", False) else 0
         s._keep = arrays  # keep the arrays alive with the struct
         return s
 
@@ -680,6 +698,20 @@ class Engine:
         nsgpu.check(nsgpu.lib().nsgpu_p2p_error_models(self.h, out.ctypes.data, self.stream))
         return out
 
+    def flow_stats(self, max_delay_ns=MAX_PER_HOP_DELAY_NS):
+        """FlowMonitor's FlowStats of the flows that sent anything (nsgpu_p2p_flow_stats: FLOW_STATS_DTYPE), ordered
+        by flow_id: FlowIds are 1-based in the order of the flows' first transmissions, as Ipv4FlowClassifier numbers
+        them.  lost_packets includes CheckForLostPackets (max_delay_ns) at the end of the run (10 s: the default
+        MaxPerHopDelay).  An unmonitored engine returns no flow."""
+        return flow_stats_from_records(self.flow_records(max_delay_ns))
+
+    def flow_records(self, max_delay_ns=MAX_PER_HOP_DELAY_NS):
+        """nsgpu_p2p_flow_stats as the library returns it: 2 * n_apps records (FLOW_RECORD_DTYPE) by flow index, zeros
+        for a flow that sent nothing and for an unmonitored engine."""
+        raw = np.zeros(2 * self.s.n_apps, FLOW_RECORD_DTYPE)
+        nsgpu.check(nsgpu.lib().nsgpu_p2p_flow_stats(self.h, int(max_delay_ns), raw.ctypes.data, self.stream))
+        return raw
+
     def results(self, log_n=0):
         st = P2PStats()
         devc = np.zeros(self.s.n_devices, DEV_COUNTERS_DTYPE)
@@ -921,6 +953,19 @@ class LoopbackGroup:
             nsgpu.lib().nsgpu_p2p_group_destroy(self.h)
         except Exception:
             pass
+
+
+def flow_stats_from_records(raw):
+    """nsgpu_flow_record [2 * n_apps] -> FLOW_STATS_DTYPE: the flows that sent anything, numbered 1-based in the
+    order of their first transmissions' events (ts, uid) — the order Ipv4FlowClassifier::Classify first sees them."""
+    sent = np.flatnonzero(raw["tx_packets"] > 0)
+    order = sent[np.lexsort((raw["first_tx_uid"][sent], raw["first_tx_ts"][sent]))]
+    out = np.zeros(len(order), FLOW_STATS_DTYPE)
+    out["flow_id"] = np.arange(1, len(order) + 1)
+    out["flow"] = order
+    for name in FLOW_RECORD_DTYPE.names:
+        out[name] = raw[name][order]
+    return out
 
 
 def rng_stream(seed, run, stream, n, on_device=False, hip_stream=None):

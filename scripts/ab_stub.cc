@@ -3,8 +3,6 @@
 // older tree's library (make lib/libnsgpu.so CXXSRCS="csrc/nsgpu_trace.cc csrc/nsgpu_setup.cc csrc/ab_stub.cc", the
 // file copied to its csrc/): each stub fails when called, and the default bench line calls none of them.
 // Only what the parent of the current change lacks is defined here (an entry point the parent has would be defined
-// twice): r12's nsgpu_p2p_frag_stats stub left with r13.
-//   r13: the receive error models' entry points (the A/B of DESIGN.md 4.4d)
-extern "C" int nsgpu_p2p_error_models(void *, void *, void *) { return -1; }
-extern "C" int nsgpu_rng_stream_run(unsigned, unsigned, unsigned, unsigned long long, double *, int, void *) { return -1; }
-extern "C" int nsgpu_error_model_thresholds(unsigned, double, double *) { return -1; }
+// twice): r13's error-model stubs left with r14.
+//   r14: the per-flow statistics' entry point (the A/B of DESIGN.md 4.4e)
+extern "C" int nsgpu_p2p_flow_stats(void *, long long, void *, void *) { return -1; }
