@@ -588,6 +588,24 @@ int nsgpu_p2p_get_wide(nsgpu_p2p *h, int *wide);
  * m_lastMaxSeqNum of every application, n_apps records (zeros for every other kind; a partitioned engine returns
  * its own nodes' servers: the owner's values count). */
 int nsgpu_p2p_udp_servers(nsgpu_p2p *h, nsgpu_udp_server_record *out, void *stream);
+/* UdpTraceClient (NSGPU_APP_UDP_TRACE_CLIENT, nsgpu_types.h): a scenario with one is created through the _ex entry
+ * points, which take the trace entries in an nsgpu_p2p_scenario_ext; ext == NULL is the plain entry point, exactly.
+ * Refused at create, each with its own message: the kind without ports; no entries; every timeToSend 0 (the
+ * reference's loop would not end); MaxPacketSize 0 or above 1472 (also in a frag scenario: a trace client sends no
+ * fragments); a packet_size above 65535; a Send of more than NSGPU_UDP_TRACE_MAX_BURST datagrams; a datagram that is
+ * the 12-byte SeqTsHeader alone addressed to a port that is no UdpServer's. */
+int nsgpu_p2p_create_ex(const nsgpu_p2p_scenario *sc, const nsgpu_p2p_scenario_ext *ext, uint64_t pool_cap,
+                        uint64_t log_cap, nsgpu_p2p **out);
+/* m_sent, m_currentEntry and the Send events run of every application, n_apps records (zeros for every other kind; a
+ * partitioned engine returns its own nodes' clients: the owner's values count). */
+int nsgpu_p2p_udp_trace_clients(nsgpu_p2p *h, nsgpu_udp_trace_client_record *out, void *stream);
+/* The reference's trace loaders on the host.  nsgpu_udp_trace_load reads `path` as UdpTraceClient::LoadTrace does
+ * (udp-trace-client.cc:176-209: `index frameType time size` with ifstream >> inside while (good ()), so a file that
+ * ends in whitespace yields its last entry twice, and time - prevTime is unsigned); an unreadable file gives the
+ * default trace.  nsgpu_udp_trace_default is LoadDefaultTrace (:211-232).  *n = the entries there are; at most `cap`
+ * are written (out may be NULL with cap 0: a size query). */
+int nsgpu_udp_trace_load(const char *path, nsgpu_udp_trace_entry *out, uint64_t cap, uint64_t *n);
+int nsgpu_udp_trace_default(nsgpu_udp_trace_entry *out, uint64_t cap, uint64_t *n);
 /* IPv4 fragmentation (nsgpu_p2p_scenario.frag): the run's counters — datagrams fragmented, fragments sent,
  * datagrams reassembled, reassembly timeouts that fired, timers dispatched after they were cancelled, the longest
  * reassembly list (zeros without frag).  A partitioned engine reports its own nodes: a run's totals are the
@@ -721,6 +739,9 @@ int nsgpu_comm_destroy(nsgpu_comm *c);
 /* comm == NULL: a loopback member (all partitions in one process on one device, see below). */
 int nsgpu_p2p_create_dist(const nsgpu_p2p_scenario *sc, const uint32_t *node_owner, int rank, int nranks,
                           nsgpu_comm *comm, uint64_t pool_cap, uint64_t log_cap, nsgpu_p2p **out);
+int nsgpu_p2p_create_dist_ex(const nsgpu_p2p_scenario *sc, const nsgpu_p2p_scenario_ext *ext, const uint32_t *node_owner,
+                             int rank, int nranks, nsgpu_comm *comm, uint64_t pool_cap, uint64_t log_cap,
+                             nsgpu_p2p **out);
 /* The constants a rank's partitioned engine is built from, computed on the host (no device, no communicator):
  * what nsgpu_p2p_create_dist derives from the scenario and the owner map (the same code: create_engine runs it
  * first).  Every field except n_init and pool_cap must be equal on every rank — the exchanges' sizes (X0 / X1 /
@@ -748,6 +769,8 @@ typedef struct nsgpu_p2p_plan {
 } nsgpu_p2p_plan;
 int nsgpu_p2p_dist_plan(const nsgpu_p2p_scenario *sc, const uint32_t *node_owner, int rank, int nranks,
                         uint64_t pool_cap, nsgpu_p2p_plan *out);
+int nsgpu_p2p_dist_plan_ex(const nsgpu_p2p_scenario *sc, const nsgpu_p2p_scenario_ext *ext, const uint32_t *node_owner,
+                           int rank, int nranks, uint64_t pool_cap, nsgpu_p2p_plan *out);
 /* Loopback group: partitions 0..n-1 (created with comm == NULL) run on this device with the
  * collectives replaced by device-to-device copies — the partitioned algorithm on one GPU. */
 typedef struct nsgpu_p2p_group nsgpu_p2p_group;

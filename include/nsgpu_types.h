@@ -97,7 +97,8 @@ typedef struct nsgpu_loss_trace {
  * host pointers; devices and applications are listed in ns-3 creation order (Node::AddDevice /
  * Node::AddApplication), which fixes the setup-time uids (node-list.cc:124-131, node.cc:111-145). */
 enum nsgpu_app_kind { NSGPU_APP_ONOFF = 0, NSGPU_APP_SINK = 1, NSGPU_APP_ECHO_CLIENT = 2, NSGPU_APP_ECHO_SERVER = 3,
-                      NSGPU_APP_UDP_CLIENT = 4, NSGPU_APP_UDP_SERVER = 5 };  /* (4, 5: ports mode only, below) */
+                      NSGPU_APP_UDP_CLIENT = 4, NSGPU_APP_UDP_SERVER = 5,  /* (4, 5, 6: ports mode only, below) */
+                      NSGPU_APP_UDP_TRACE_CLIENT = 6 };
 /* UdpEchoClient (udp-echo-client.cc): app_dst_node = the server's node, app_pkt_size = PacketSize,
  * app_count = MaxPackets, app_interval_ns = Interval, app_src_slot = the route-table slot of the
  * client's own node (the echo comes back there).  UdpEchoServer (udp-echo-server.cc): the node's bound
@@ -226,6 +227,36 @@ typedef struct nsgpu_p2p_scenario {
    * them.  The run itself is the unmonitored one: no event is added or reordered.  Not with frag, not on a partitioned
    * engine, not under a host-closure runtime (refused). */
 } nsgpu_p2p_scenario;
+
+/* ---------------- UdpTraceClient (udp-trace-client.cc): NSGPU_APP_UDP_TRACE_CLIENT, ports mode only ----------------
+ * A trace client sends the frames of a trace file, cyclically: entry e is (timeToSend ms, packetSize).  One Send event
+ * (:311-335) emits, starting at m_currentEntry, every entry up to the next one whose timeToSend is not 0 — a frame
+ * above MaxPacketSize as packetSize / MaxPacketSize datagrams of MaxPacketSize bytes and one of the remainder (also
+ * when that is 0) — and schedules the next Send after that entry's timeToSend.  A datagram's UDP payload is
+ * max (size, 12) bytes: the 12-byte SeqTsHeader, whose sequence number is m_sent (it advances only when the socket's
+ * Send succeeded).  app_pkt_size = MaxPacketSize ([1, 1472]); app_remote_port, app_ttl, app_dst_*, app_src_slot as
+ * for a UdpClient.  The entries do not fit nsgpu_p2p_scenario (whose size and offsets are fixed): they travel in this
+ * size-prefixed extension record, given to the _ex forms of the entry points that read a scenario (nsgpu.h).
+ * A Send may emit at most NSGPU_UDP_TRACE_MAX_BURST datagrams; a client whose m_sent would pass 2^24 (the descriptor's
+ * sequence field) fails the run with NSGPU_ERANGE. */
+#define NSGPU_UDP_TRACE_MAX_BURST 256u
+typedef struct nsgpu_udp_trace_entry {
+  uint32_t time_to_send_ms;  /* TraceEntry::timeToSend: the delta to the previous non-B frame (0 for a B frame) */
+  uint32_t packet_size;      /* TraceEntry::packetSize (a uint16 in the reference: above 65535 is refused) */
+} nsgpu_udp_trace_entry;
+typedef struct nsgpu_p2p_scenario_ext {
+  uint32_t size;             /* sizeof (nsgpu_p2p_scenario_ext) as the caller compiled it */
+  uint32_t pad_;
+  const uint64_t *trace_off; /* CSR, n_apps + 1 offsets into trace_entries (empty for every other kind) */
+  const nsgpu_udp_trace_entry *trace_entries;
+} nsgpu_p2p_scenario_ext;
+/* What nsgpu_p2p_udp_trace_clients returns per application (zeros for every other kind). */
+typedef struct nsgpu_udp_trace_client_record {
+  uint32_t sent;           /* m_sent */
+  uint32_t current_entry;  /* m_currentEntry */
+  uint32_t sends;          /* Send events that ran (a cancelled one is dispatched, not run) */
+  uint32_t pad_;
+} nsgpu_udp_trace_client_record;
 
 /* What nsgpu_p2p_flow_stats returns per flow, 2 * n_apps records: flow a = application a's datagrams, flow
  * n_apps + a = the echo replies to UdpEchoClient a (zeros for a flow that sent nothing).  FlowMonitor::FlowStats

@@ -9,6 +9,7 @@ namespace nsgpu {
 #include "nsgpu_p2p_dist.h"
 
 #include <vector>
+#include <fstream>
 #include <algorithm>
 #include <string.h>
 #include <stdlib.h>
@@ -102,6 +103,8 @@ struct nsgpu_p2p {
   uint32_t em_models = 0;            // enabled receive error models
   const nsgpu_loss_counter *loss_init = nullptr;  // ports mode: the UdpServers' loss counters after reset
   uint32_t n_apps = 0;
+  // an engine with a UdpTraceClient: app_tot holds 3 * n_apps words (m_sent, m_currentEntry, the Send events run)
+  bool has_trace_client = false;
   // frag mode: the reset image of what lies behind node_ipid up to the FragNodes (device), its words, the whole
   // allocation's bytes, the FragNodes
   const uint32_t *frag_init = nullptr;
@@ -182,6 +185,12 @@ struct EnginePlan {
   std::vector<int32_t> sink;
   bool ports = false;               // ports mode (nsgpu_p2p_scenario.app_port given)
   std::vector<int32_t> ep_of_flow;  // ports mode: the application a sender's datagrams are delivered to (-1: none)
+  // UdpTraceClients (nsgpu_p2p_scenario_ext): what lies behind app_pkt_size on the device — n_apps + 1 offsets, the
+  // entries as (timeToSend ms, packetSize) pairs (nsgpu_p2p_dev.h "UdpTraceClient") — and per application the walk of
+  // its cycle (plan_trace_client): the datagrams it sends before the run can end, for flowmon's table bound
+  bool has_trace_client = false;
+  std::vector<uint32_t> tc_img;
+  std::vector<uint64_t> tc_bound;
   int64_t tx_min = 0, lx = 0, send_ivl = 0;
   int64_t lookahead[K_NKINDS], lookw[K_NKINDS];
   bool frag = false;                 // frag mode (nsgpu_p2p_scenario.frag)
@@ -293,6 +302,83 @@ static int plan_error_models(const nsgpu_p2p_scenario *sc, EnginePlan &P) {
   return NSGPU_OK;
 }
 
+// One UdpTraceClient's entries, validated, and the walk of its cycle (udp-trace-client.cc:311-335) from entry 0 until
+// m_currentEntry repeats at a Send's start: the smallest and largest UDP payload it puts on a wire, the largest burst,
+// the shortest delay between two Sends, and per cycle the datagrams and the time.
+struct TraceWalk {
+  uint32_t min_payload = 0xffffffffu, max_payload = 0, max_burst = 0;
+  int64_t min_delay = (int64_t)1 << 61;
+  uint64_t head_dgrams = 0, cycle_dgrams = 0;  // before the cycle is entered; one round of it
+  int64_t cycle_ns = 0;
+};
+static int plan_trace_client(const nsgpu_p2p_scenario *sc, const nsgpu_p2p_scenario_ext *ext, uint32_t a, bool ports,
+                             TraceWalk &W) {
+  if (!ports)
+    return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: app %u: UdpTraceClient needs UDP ports (app_port)", a);
+  if (!ext || ext->size < sizeof(nsgpu_p2p_scenario_ext) || !ext->trace_off)
+    return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: UdpTraceClient %u: no trace entries (an nsgpu_p2p_scenario_ext "
+                     "through the _ex entry points carries them)", a);
+  const uint64_t lo = ext->trace_off[a], hi = ext->trace_off[a + 1];
+  if (hi <= lo || !ext->trace_entries)
+    return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: UdpTraceClient %u: no trace entries", a);
+  if (hi - lo > 0x7fffffffull)
+    return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: UdpTraceClient %u: 2^31 trace entries or more", a);
+  const uint32_t N = sc->n_nodes;
+  if (sc->app_dst_node[a] >= N || sc->app_dst_slot[a] >= sc->n_dst || sc->app_ttl[a] == 0 || sc->app_ttl[a] > 255 ||
+      sc->app_dst_node[a] == sc->app_node[a] ||
+      (sc->app_src_slot && sc->app_src_slot[a] != 0xffffffffu && sc->app_src_slot[a] >= sc->n_dst))
+    return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: UdpTraceClient %u: bad destination/ttl/source slot", a);
+  // (also in a frag scenario: a trace client sends no fragments — MaxPacketSize is a uint16 the example sets to 1472)
+  const uint32_t mps = sc->app_pkt_size[a];
+  if (mps == 0 || mps > 1472)
+    return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: UdpTraceClient %u: MaxPacketSize %u outside [1, 1472]", a, mps);
+  const nsgpu_udp_trace_entry *T = ext->trace_entries + lo;
+  const uint32_t cnt = (uint32_t)(hi - lo);
+  bool any = false;
+  for (uint32_t e = 0; e < cnt; e++) {
+    if (T[e].packet_size > 65535)  // (TraceEntry::packetSize is a uint16)
+      return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: UdpTraceClient %u: entry %u: packet_size %u above 65535", a, e,
+                       T[e].packet_size);
+    any = any || T[e].time_to_send_ms != 0;
+  }
+  if (!any)  // (the do-while of Send would never end)
+    return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: UdpTraceClient %u: every entry's timeToSend is 0 (the "
+                     "reference's Send loop would not end)", a);
+  // the walk: Send k starts at entry start[k]; the state of the client between Sends is that entry alone
+  std::vector<int64_t> seen_t(cnt, -1);
+  std::vector<uint64_t> seen_d(cnt, 0);
+  uint32_t e = 0;
+  int64_t t = 0;
+  uint64_t dg = 0;
+  while (seen_t[e] < 0) {
+    seen_t[e] = t;
+    seen_d[e] = dg;
+    uint64_t burst = 0;
+    do {
+      const uint32_t ps = T[e].packet_size, nfull = ps / mps;
+      for (uint32_t i = 0; i <= nfull; i++) {
+        const uint32_t sz = i < nfull ? mps : ps % mps, pay = sz > 12 ? sz : 12;
+        W.min_payload = std::min(W.min_payload, pay);
+        W.max_payload = std::max(W.max_payload, pay);
+      }
+      burst += (uint64_t)nfull + 1;
+      e = e + 1 == cnt ? 0 : e + 1;
+    } while (T[e].time_to_send_ms == 0);
+    if (burst > NSGPU_UDP_TRACE_MAX_BURST)
+      return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: UdpTraceClient %u: a Send of %llu datagrams (at most %u: "
+                       "NSGPU_UDP_TRACE_MAX_BURST)", a, (unsigned long long)burst, NSGPU_UDP_TRACE_MAX_BURST);
+    W.max_burst = std::max<uint32_t>(W.max_burst, (uint32_t)burst);
+    dg += burst;
+    const int64_t d = (int64_t)T[e].time_to_send_ms * 1000000ll;
+    W.min_delay = std::min(W.min_delay, d);
+    t += d;
+  }
+  W.head_dgrams = seen_d[e];
+  W.cycle_dgrams = dg - seen_d[e];
+  W.cycle_ns = t - seen_t[e];
+  return NSGPU_OK;
+}
+
 // Per-flow statistics (nsgpu_p2p_scenario.flowmon): the refusals, and each node's tracked-packet table size — a bound
 // on the identifications the node hands out before the run ends (nsgpu_p2p_dev.h "per-flow statistics"), at most
 // FM_NODE_CAP.  A node originates its senders' datagrams, the echo replies to the clients that address it, and with
@@ -315,12 +401,19 @@ static int plan_flowmon(const nsgpu_p2p_scenario *sc, const uint32_t *owner, Eng
   bool has_stop = false;
   for (uint32_t i = 0; i < sc->n_setup; i++) has_stop = has_stop || sc->setup_kind[i] == NSGPU_SETUP_STOP;
   const uint64_t CAP = FM_NODE_CAP;
-  auto sender = [&](uint32_t k) { return k == NSGPU_APP_ONOFF || k == NSGPU_APP_ECHO_CLIENT || k == NSGPU_APP_UDP_CLIENT; };
+  auto sender = [&](uint32_t k) {
+    return k == NSGPU_APP_ONOFF || k == NSGPU_APP_ECHO_CLIENT || k == NSGPU_APP_UDP_CLIENT || k == NSGPU_APP_UDP_TRACE_CLIENT;
+  };
   // the datagrams application a can send before the run (or the application) stops, CAP when nothing bounds them
   auto bound = [&](uint32_t a) -> uint64_t {
     int64_t t1 = has_stop ? sc->stop_ns : -1;
     if (sc->app_stop_ns[a] != 0 && (t1 < 0 || sc->app_stop_ns[a] < t1)) t1 = sc->app_stop_ns[a];
     const int64_t dur = t1 < 0 ? -1 : std::max<int64_t>(0, t1 - sc->app_start_ns[a]);
+    if (sc->app_kind[a] == NSGPU_APP_UDP_TRACE_CLIENT) {  // (the walk of its cycle: plan_trace_client)
+      if (dur < 0) return CAP;
+      const u128 b = (u128)P.tc_bound[3 * a] + ((u128)(dur / P.tc_bound[3 * a + 2]) + 2) * P.tc_bound[3 * a + 1];
+      return b < CAP ? (uint64_t)b : CAP;
+    }
     if (sc->app_kind[a] != NSGPU_APP_ONOFF) {  // MaxPackets, one an Interval
       uint64_t b = sc->app_count[a];
       if (dur >= 0 && sc->app_interval_ns[a] > 0) b = std::min<uint64_t>(b, (uint64_t)(dur / sc->app_interval_ns[a]) + 1);
@@ -355,8 +448,8 @@ static int plan_flowmon(const nsgpu_p2p_scenario *sc, const uint32_t *owner, Eng
   return NSGPU_OK;
 }
 
-static int plan_engine(const nsgpu_p2p_scenario *sc, const uint32_t *owner, int rank, int nranks, uint64_t pool_cap,
-                       EnginePlan &P) {
+static int plan_engine(const nsgpu_p2p_scenario *sc, const nsgpu_p2p_scenario_ext *ext, const uint32_t *owner, int rank,
+                       int nranks, uint64_t pool_cap, EnginePlan &P) {
   if (!sc) return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: null");
   const uint32_t N = sc->n_nodes, D = sc->n_devices, A = sc->n_apps;
   if (N == 0 || !sc->setup_kind || !sc->setup_index) return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: empty");
@@ -409,6 +502,7 @@ static int plan_engine(const nsgpu_p2p_scenario *sc, const uint32_t *owner, int 
   bool &has_echo = P.has_echo;
   has_echo = false;
   int64_t echo_ivl = (int64_t)1 << 61;
+  std::vector<uint32_t> tc_min_payload(A, 0);  // (a trace client's smallest UDP payload)
   const bool ports = sc->app_port != nullptr;
   P.ports = ports;
   if (ports && !sc->app_remote_port) return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: app_port without app_remote_port");
@@ -416,12 +510,28 @@ static int plan_engine(const nsgpu_p2p_scenario *sc, const uint32_t *owner, int 
     if (sc->app_node[a] >= N) return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: app %u: bad node", a);
     napps[sc->app_node[a] + 1]++;
     const uint32_t ak = sc->app_kind[a];
+    if (ak == NSGPU_APP_UDP_TRACE_CLIENT && !ports)
+      return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: app %u: UdpTraceClient needs UDP ports (app_port)", a);
     if ((ak == NSGPU_APP_UDP_CLIENT || ak == NSGPU_APP_UDP_SERVER) && !ports)
       return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: app %u: UdpClient / UdpServer need UDP ports (app_port)", a);
     if (ak == NSGPU_APP_UDP_SERVER) {  // (bound like a sink: the endpoints are resolved below)
       if (!sc->app_loss_window || sc->app_loss_window[a] % 8 != 0 || sc->app_loss_window[a] < 8 ||
           sc->app_loss_window[a] > NSGPU_LOSS_WINDOW_MAX)
         return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: UdpServer %u: PacketWindowSize must be a multiple of 8 in [8, 256]", a);
+    } else if (ak == NSGPU_APP_UDP_TRACE_CLIENT) {
+      TraceWalk W;
+      if (int rct = plan_trace_client(sc, ext, a, ports, W)) return rct;
+      if (!P.has_trace_client) {
+        P.has_trace_client = true;
+        P.tc_bound.assign(3 * (size_t)A, 0);
+      }
+      P.tc_bound[3 * a] = W.head_dgrams + W.max_burst, P.tc_bound[3 * a + 1] = W.cycle_dgrams;
+      P.tc_bound[3 * a + 2] = (uint64_t)W.cycle_ns;
+      tc_min_payload[a] = W.min_payload;
+      // the smallest frame the flow can put on a wire bounds the lookaheads; the largest is at most MaxPacketSize + 30
+      // (1502: the error models' table and a frame's MTU hold it)
+      min_pkt = std::min(min_pkt, W.min_payload);
+      echo_ivl = std::min(echo_ivl, W.min_delay);  // (the next Send's delay: at least 1 ms)
     } else if (ak == NSGPU_APP_UDP_CLIENT) {
       if (!sc->app_count || !sc->app_interval_ns || sc->app_dst_node[a] >= N || sc->app_dst_slot[a] >= sc->n_dst ||
           sc->app_ttl[a] == 0 || sc->app_ttl[a] > 255 || sc->app_dst_node[a] == sc->app_node[a] ||
@@ -494,7 +604,9 @@ static int plan_engine(const nsgpu_p2p_scenario *sc, const uint32_t *owner, int 
   if (ports) {
     // Ipv4EndPointDemux for sockets bound to (Any, port): the binding (node, port) -> application is static
     auto bound = [&](uint32_t k) { return k == NSGPU_APP_SINK || k == NSGPU_APP_ECHO_SERVER || k == NSGPU_APP_UDP_SERVER; };
-    auto sender = [&](uint32_t k) { return k == NSGPU_APP_ONOFF || k == NSGPU_APP_ECHO_CLIENT || k == NSGPU_APP_UDP_CLIENT; };
+    auto sender = [&](uint32_t k) {
+      return k == NSGPU_APP_ONOFF || k == NSGPU_APP_ECHO_CLIENT || k == NSGPU_APP_UDP_CLIENT || k == NSGPU_APP_UDP_TRACE_CLIENT;
+    };
     std::vector<std::vector<uint32_t>> eps(N);
     std::vector<uint8_t> sends(N, 0);
     for (uint32_t a = 0; a < A; a++)
@@ -522,6 +634,13 @@ static int plan_engine(const nsgpu_p2p_scenario *sc, const uint32_t *owner, int 
       const int32_t e = P.ep_of_flow[a];
       if (eps[n].empty() || e != (int32_t)eps[n][0]) other[n] = 1;
       // a UdpServer reads a SeqTsHeader from every datagram (udp-server.cc:159-160)
+      if (sc->app_kind[a] == NSGPU_APP_UDP_TRACE_CLIENT) {
+        // (its payloads always hold the header; a datagram that is the header alone is for a UdpServer only)
+        if (tc_min_payload[a] == 12 && !(e >= 0 && sc->app_kind[e] == NSGPU_APP_UDP_SERVER))
+          return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: UdpTraceClient %u: a 12-byte payload (the SeqTsHeader alone) "
+                           "to port %u, which is no UdpServer's", a, sc->app_remote_port[a]);
+        continue;
+      }
       if (e >= 0 && sc->app_kind[e] == NSGPU_APP_UDP_SERVER && sc->app_pkt_size[a] < 12)
         return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: app %u: %u-byte payload to UdpServer %d holds no SeqTsHeader", a,
                          sc->app_pkt_size[a], e);
@@ -539,6 +658,23 @@ static int plan_engine(const nsgpu_p2p_scenario *sc, const uint32_t *owner, int 
         return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: node %u receives fragments of %u fragmenting flows (at most "
                          "one: the reference's nodes have one reassembly buffer for all sources)", n, P.frag_flows[n]);
     P.frag_timeout = sc->frag_timeout_ns ? sc->frag_timeout_ns : 30000000000ll;  // Seconds (30) (:61-64)
+  }
+  if (P.has_trace_client) {  // the offsets and entries as the device reads them (tc_offsets, tc_entries)
+    uint64_t tot = 0;
+    for (uint32_t a = 0; a < A; a++)
+      if (sc->app_kind[a] == NSGPU_APP_UDP_TRACE_CLIENT) tot += ext->trace_off[a + 1] - ext->trace_off[a];
+    if (tot > 0x3fffffffull)
+      return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: the UdpTraceClients' traces hold 2^30 entries or more");
+    P.tc_img.reserve((size_t)A + 1 + 2 * tot);
+    P.tc_img.assign((size_t)A + 1, 0);
+    for (uint32_t a = 0; a < A; a++) {
+      if (sc->app_kind[a] == NSGPU_APP_UDP_TRACE_CLIENT)
+        for (uint64_t j = ext->trace_off[a]; j < ext->trace_off[a + 1]; j++) {
+          P.tc_img.push_back(ext->trace_entries[j].time_to_send_ms);
+          P.tc_img.push_back(ext->trace_entries[j].packet_size);
+        }
+      P.tc_img[a + 1] = (uint32_t)((P.tc_img.size() - A - 1) / 2);
+    }
   }
   if (int rcf = plan_flowmon(sc, owner, P)) return rcf;
   uint32_t &maxapps = P.maxapps;
@@ -702,12 +838,12 @@ static int plan_engine(const nsgpu_p2p_scenario *sc, const uint32_t *owner, int 
 
 // owner == null: the whole scenario on this device; otherwise the partition `rank` of `nranks`
 // (node n belongs to rank owner[n]).
-static int create_engine(const nsgpu_p2p_scenario *sc, const uint32_t *owner, int rank, int nranks,
-                         nsgpu_comm *comm, uint64_t pool_cap, uint64_t log_cap, nsgpu_p2p **out) {
+static int create_engine(const nsgpu_p2p_scenario *sc, const nsgpu_p2p_scenario_ext *ext, const uint32_t *owner, int rank,
+                         int nranks, nsgpu_comm *comm, uint64_t pool_cap, uint64_t log_cap, nsgpu_p2p **out) {
   if (!out) return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: null");
   *out = nullptr;
   EnginePlan P;
-  if (int rcp = plan_engine(sc, owner, rank, nranks, pool_cap, P)) return rcp;
+  if (int rcp = plan_engine(sc, ext, owner, rank, nranks, pool_cap, P)) return rcp;
   const uint32_t N = sc->n_nodes, D = sc->n_devices, A = sc->n_apps;
   const uint32_t qcap = P.qcap;
   const std::vector<uint32_t> &napps = P.napps, &node_list = P.node_list;
@@ -747,7 +883,14 @@ static int create_engine(const nsgpu_p2p_scenario *sc, const uint32_t *owner, in
   } else {
     TRY(dupload(h, &M.app_dst_slot, sc->app_dst_slot, A));
   }
-  TRY(dupload(h, &M.app_pkt_size, sc->app_pkt_size, A));
+  if (P.has_trace_client) {  // (the trace clients' offsets and entries lie behind the sizes: tc_entries)
+    std::vector<uint32_t> ps(sc->app_pkt_size, sc->app_pkt_size + A);
+    ps.insert(ps.end(), P.tc_img.begin(), P.tc_img.end());
+    TRY(dupload(h, &M.app_pkt_size, ps.data(), ps.size()));
+    h->has_trace_client = true;
+  } else {
+    TRY(dupload(h, &M.app_pkt_size, sc->app_pkt_size, A));
+  }
   TRY(dupload(h, &M.app_max_bytes, sc->app_max_bytes, A));
   TRY(dupload(h, &M.app_ttl, sc->app_ttl, A));
   TRY(dupload(h, &M.app_start, sc->app_start_ns, A));
@@ -821,7 +964,7 @@ static int create_engine(const nsgpu_p2p_scenario *sc, const uint32_t *owner, in
   TRY(dalloc(h, &M.app_send_gen, A));
   TRY(dalloc(h, &M.app_ss_gen, A));
   TRY(dalloc(h, &M.app_residual, A));
-  TRY(dalloc(h, &M.app_tot, A));
+  TRY(dalloc(h, &M.app_tot, (P.has_trace_client ? 3 : 1) * (size_t)A));  // (+ m_currentEntry, the Sends run)
   if (P.frag) {
     // behind the identifications: each node's FragNode index, the FragHdr, a FragNode for every node that is the
     // destination of a fragmenting flow (nsgpu_p2p_dev.h "IPv4 fragmentation"); kept as the reset image too
@@ -1062,24 +1205,38 @@ static int create_engine(const nsgpu_p2p_scenario *sc, const uint32_t *owner, in
 
 extern "C" int nsgpu_p2p_create(const nsgpu_p2p_scenario *sc, uint64_t pool_cap, uint64_t log_cap,
                                 nsgpu_p2p **out) {
-  return create_engine(sc, nullptr, 0, 1, nullptr, pool_cap, log_cap, out);
+  return create_engine(sc, nullptr, nullptr, 0, 1, nullptr, pool_cap, log_cap, out);
+}
+extern "C" int nsgpu_p2p_create_ex(const nsgpu_p2p_scenario *sc, const nsgpu_p2p_scenario_ext *ext, uint64_t pool_cap,
+                                   uint64_t log_cap, nsgpu_p2p **out) {
+  return create_engine(sc, ext, nullptr, 0, 1, nullptr, pool_cap, log_cap, out);
 }
 
 extern "C" int nsgpu_p2p_create_dist(const nsgpu_p2p_scenario *sc, const uint32_t *node_owner, int rank,
                                      int nranks, nsgpu_comm *comm, uint64_t pool_cap, uint64_t log_cap,
                                      nsgpu_p2p **out) {
+  return nsgpu_p2p_create_dist_ex(sc, nullptr, node_owner, rank, nranks, comm, pool_cap, log_cap, out);
+}
+extern "C" int nsgpu_p2p_create_dist_ex(const nsgpu_p2p_scenario *sc, const nsgpu_p2p_scenario_ext *ext,
+                                        const uint32_t *node_owner, int rank, int nranks, nsgpu_comm *comm,
+                                        uint64_t pool_cap, uint64_t log_cap, nsgpu_p2p **out) {
   if (!node_owner) return set_error(NSGPU_EINVAL, "nsgpu_p2p_create_dist: null owner map");
   if (comm && (comm->nranks != nranks || comm->rank != rank))
     return set_error(NSGPU_EINVAL, "nsgpu_p2p_create_dist: communicator is rank %d of %d", comm->rank, comm->nranks);
-  return create_engine(sc, node_owner, rank, nranks, comm, pool_cap, log_cap, out);
+  return create_engine(sc, ext, node_owner, rank, nranks, comm, pool_cap, log_cap, out);
 }
 
 extern "C" int nsgpu_p2p_dist_plan(const nsgpu_p2p_scenario *sc, const uint32_t *node_owner, int rank, int nranks,
                                    uint64_t pool_cap, nsgpu_p2p_plan *out) {
+  return nsgpu_p2p_dist_plan_ex(sc, nullptr, node_owner, rank, nranks, pool_cap, out);
+}
+extern "C" int nsgpu_p2p_dist_plan_ex(const nsgpu_p2p_scenario *sc, const nsgpu_p2p_scenario_ext *ext,
+                                      const uint32_t *node_owner, int rank, int nranks, uint64_t pool_cap,
+                                      nsgpu_p2p_plan *out) {
   if (!sc || !out) return set_error(NSGPU_EINVAL, "nsgpu_p2p_dist_plan: null");
   static_assert(K_NKINDS <= 16, "nsgpu_p2p_plan holds 16 kinds");
   EnginePlan P;
-  if (int rc = plan_engine(sc, node_owner, rank, nranks, pool_cap, P)) return rc;
+  if (int rc = plan_engine(sc, ext, node_owner, rank, nranks, pool_cap, P)) return rc;
   memset(out, 0, sizeof(*out));
   out->wide = P.wide;
   out->maxc = P.maxc;
@@ -1122,7 +1279,7 @@ extern "C" int nsgpu_p2p_reset(nsgpu_p2p *h, void *stream) {
   NSGPU_HIP(hipMemsetAsync(M.app_send_gen, 0, A * sizeof(uint32_t), s));
   NSGPU_HIP(hipMemsetAsync(M.app_ss_gen, 0, A * sizeof(uint32_t), s));
   NSGPU_HIP(hipMemsetAsync(M.app_residual, 0, A * sizeof(uint32_t), s));
-  NSGPU_HIP(hipMemsetAsync(M.app_tot, 0, A * sizeof(uint32_t), s));
+  NSGPU_HIP(hipMemsetAsync(M.app_tot, 0, (h->has_trace_client ? 3 : 1) * (size_t)A * sizeof(uint32_t), s));
   // (the identifications, the FragNode indices and header, empty FragNodes; a monitored engine: the tables' bases
   // and sizes, empty flow records and tracked-packet tables)
   if (M.frag || M.flowmon) {
@@ -1571,6 +1728,9 @@ static int build_graph(nsgpu_p2p *h, bool df = false, bool tail = false) {
 
 // A run that set the engine's error word: capacity exceeded (the simulation is truncated).
 static int engine_error(uint32_t err) {
+  if (err & ERR_TRACE_SEQ)
+    return set_error(NSGPU_ERANGE, "nsgpu_p2p: a UdpTraceClient's m_sent would pass 2^24 (code %u: the packet descriptor "
+                     "carries the SeqTsHeader's sequence number in 24 bits; it is never wrapped silently)", err);
   if (err & ERR_FLOWMON_ID)
     return set_error(NSGPU_ERANGE, "nsgpu_p2p: a monitored node's IPv4 identification reached the size of its "
                      "tracked-packet table (flowmon; code %u: at most 65536 datagrams a node, the 16-bit identification "
@@ -1756,6 +1916,9 @@ extern "C" int nsgpu_p2p_setup_uid(nsgpu_p2p *h, uint32_t *uid) {
   // (... and so does an engine with a receive error model: no test covers the combination)
   if (h->M.errm)
     return set_error(NSGPU_ESTATE, "nsgpu_p2p_setup_uid: a scenario with a receive error model cannot be attached to a "
+                     "host-closure runtime");
+  if (h->has_trace_client)
+    return set_error(NSGPU_ESTATE, "nsgpu_p2p_setup_uid: a scenario with a UdpTraceClient cannot be attached to a "
                      "host-closure runtime");
   *uid = h->C0.uid;
   return NSGPU_OK;
@@ -2117,6 +2280,72 @@ extern "C" int nsgpu_p2p_udp_servers(nsgpu_p2p *h, nsgpu_udp_server_record *out,
     if (h->app_kind[a] == NSGPU_APP_UDP_SERVER)
       out[a] = nsgpu_udp_server_record{lc[a].received, lc[a].lost, lc[a].last_max_seq, 0};
   return NSGPU_OK;
+}
+
+// UdpTraceClient's m_sent, m_currentEntry and Send events run, per application (zeros for every other kind).
+extern "C" int nsgpu_p2p_udp_trace_clients(nsgpu_p2p *h, nsgpu_udp_trace_client_record *out, void *stream) {
+  if (!h || !out) return set_error(NSGPU_EINVAL, "nsgpu_p2p_udp_trace_clients: null");
+  hipStream_t s = (hipStream_t)stream;
+  const uint32_t A = h->M.n_apps;
+  memset(out, 0, A * sizeof(*out));
+  if (!h->has_trace_client) return NSGPU_OK;
+  std::vector<uint32_t> w(3 * (size_t)A);
+  NSGPU_HIP(hipMemcpyAsync(w.data(), h->M.app_tot, w.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  NSGPU_HIP(hipStreamSynchronize(s));
+  for (uint32_t a = 0; a < A; a++)
+    if (h->app_kind[a] == NSGPU_APP_UDP_TRACE_CLIENT)
+      out[a] = nsgpu_udp_trace_client_record{w[a], w[A + a], w[2 * (size_t)A + a], 0};
+  return NSGPU_OK;
+}
+
+// What UdpTraceClient::LoadDefaultTrace (udp-trace-client.cc:211-232) leaves in m_entries: the ten built-in frames
+// (:41-53) with a B frame's timeToSend 0 and every other frame's the delta to the frame before it that is no B frame.
+namespace {
+const nsgpu_udp_trace_entry k_default_trace[] = {{0, 534},  {40, 1542}, {0, 134},  {0, 390}, {200, 765},
+                                                 {0, 407},  {0, 504},   {120, 903}, {0, 421}, {0, 587}};
+void load_default_trace(std::vector<nsgpu_udp_trace_entry> &v) {
+  v.assign(std::begin(k_default_trace), std::end(k_default_trace));
+}
+int trace_out(const std::vector<nsgpu_udp_trace_entry> &v, nsgpu_udp_trace_entry *out, uint64_t cap, uint64_t *n) {
+  *n = v.size();
+  for (uint64_t i = 0; i < v.size() && i < cap; i++) out[i] = v[i];
+  return NSGPU_OK;
+}
+}  // namespace
+extern "C" int nsgpu_udp_trace_default(nsgpu_udp_trace_entry *out, uint64_t cap, uint64_t *n) {
+  if (!n || (cap && !out)) return set_error(NSGPU_EINVAL, "nsgpu_udp_trace_default: null");
+  std::vector<nsgpu_udp_trace_entry> v;
+  load_default_trace(v);
+  return trace_out(v, out, cap, n);
+}
+// UdpTraceClient::LoadTrace (:176-209) with its own extraction idiom, types and loop condition: a file that ends in
+// whitespace is good () after its last line, so one more round runs; its first extraction meets the end of the file
+// while skipping whitespace and every one fails before it stores anything, so the variables keep the last line's values
+// — the last entry once more, with timeToSend time - prevTime = 0 (or a B frame's 0).  time - prevTime is unsigned and
+// may wrap.  (The reference leaves its variables uninitialised, which shows only for an empty file; here they are 0.)
+extern "C" int nsgpu_udp_trace_load(const char *path, nsgpu_udp_trace_entry *out, uint64_t cap, uint64_t *n) {
+  if (!path || !n || (cap && !out)) return set_error(NSGPU_EINVAL, "nsgpu_udp_trace_load: null");
+  std::vector<nsgpu_udp_trace_entry> v;
+  uint32_t time = 0, index = 0, prevTime = 0;
+  uint16_t size = 0;
+  char frameType = 0;
+  std::ifstream ifTraceFile;
+  ifTraceFile.open(path, std::ifstream::in);
+  if (!ifTraceFile.good()) load_default_trace(v);
+  while (ifTraceFile.good()) {
+    ifTraceFile >> index >> frameType >> time >> size;
+    nsgpu_udp_trace_entry entry;
+    if (frameType == 'B') {
+      entry.time_to_send_ms = 0;
+    } else {
+      entry.time_to_send_ms = time - prevTime;
+      prevTime = time;
+    }
+    entry.packet_size = size;
+    v.push_back(entry);
+  }
+  ifTraceFile.close();
+  return trace_out(v, out, cap, n);
 }
 
 // The fragmentation counters of a frag scenario (zeros without frag): the senders' from the device records, the

@@ -1132,7 +1132,8 @@ __device__ __forceinline__ void stop_application(const P2PDev &M, uint32_t a, ui
     M.app_flags[a] |= AF_RX_CLEARED;
     return;
   }
-  if (PORTS && k == NSGPU_APP_UDP_CLIENT) {  // UdpClient::StopApplication: Simulator::Cancel (m_sendEvent)
+  // UdpClient::StopApplication, UdpTraceClient::StopApplication (udp-trace-client.cc:258-263): Simulator::Cancel (m_sendEvent)
+  if (PORTS && (k == NSGPU_APP_UDP_CLIENT || k == NSGPU_APP_UDP_TRACE_CLIENT)) {
     M.app_flags[a] &= ~4u;
     return;
   }
@@ -1221,6 +1222,105 @@ __device__ __forceinline__ uint32_t route_at(const P2PDev &M, uint32_t n, uint32
 // ... towards the packet's destination.
 __device__ __forceinline__ uint32_t route_of(const P2PDev &M, uint32_t n, const Pkt &p) {
   return route_at(M, n, pkt_dst_slot(M, p));
+}
+
+// ---------------- UdpTraceClient (NSGPU_APP_UDP_TRACE_CLIENT: ports mode, the extended handlers) ----------------
+// udp-trace-client.cc.  One Send event (:311-335) emits a burst: starting at m_currentEntry, every entry up to the next
+// one whose timeToSend is not 0, each as packetSize / MaxPacketSize datagrams of MaxPacketSize and one of the remainder
+// (also when that is 0: SendPacket (0) is the 12-byte SeqTsHeader alone, :265-283).  The sender's node part (tc_send)
+// walks the burst once for the node and application state — one route lookup, then per datagram what a UdpClient's
+// send does — and hands the device step one descriptor that stands for the whole burst: {flow, the first datagram's
+// identification, TC_BURST | the first entry, TTL | the first sequence number << 8}.  The device step walks the
+// entries again by the same rule (tc_step) and runs the single-packet step once per datagram, so no event, uid or
+// child is made beyond a single send's.
+// The entries lie behind app_pkt_size — [n_apps] MaxPacketSize and the others' sizes, then [n_apps + 1] offsets, then
+// the entries as (timeToSend ms, packetSize) pairs — and m_currentEntry and the Send events run behind app_tot
+// ([n_apps] m_sent, [n_apps] m_currentEntry, [n_apps] sends); both only in an engine with a trace client.  P2PDev
+// takes no further pointer (see hub_slot).
+constexpr uint32_t TC_BURST = 0x80000000u;   // Act::p.size of a burst descriptor: the flag | the burst's first entry
+constexpr uint32_t TC_SEQ_LIMIT = 1u << 24;  // the descriptor's sequence field
+constexpr uint32_t ERR_TRACE_SEQ = 32768u;   // the engine's error bit: a trace client's m_sent would pass 2^24
+__device__ __forceinline__ bool is_burst_send(uint32_t op, uint32_t size) { return op == ACT_SEND && (size & TC_BURST); }
+__host__ __device__ __forceinline__ const uint32_t *tc_offsets(const uint32_t *app_pkt_size, uint32_t n_apps) {
+  return app_pkt_size + n_apps;
+}
+__host__ __device__ __forceinline__ const uint32_t *tc_entries(const uint32_t *app_pkt_size, uint32_t n_apps) {
+  return app_pkt_size + 2 * (size_t)n_apps + 1;
+}
+// SendPacket (size) (:265-309): the datagram's IPv4 length — Create<Packet> (size - 12) or (0), the SeqTsHeader, UDP, IPv4.
+__host__ __device__ __forceinline__ uint32_t tc_ip_size(uint32_t size) { return (size > 12u ? size : 12u) + 8u + 20u; }
+// What the sender's node part needs of a Send: the output device (0xffffffff: no route, nothing left the socket), the
+// burst's first entry, identification and sequence number, its SendPacket calls, the next Send's delay.
+struct TcSend {
+  uint32_t out, e0, ipid0, seq0, n, pad;
+  int64_t delay;
+};
+// UdpTraceClient::Send, the node and application side.  Inlined into the node part, which is itself out of line where
+// the handlers split it (node_part_cold): a function of its own between that one and fm_first_tx / route_compressed
+// made the call chain one frame deeper, 16 B of scratch a lane in every extended handler.
+__device__ __forceinline__ TcSend tc_send(const P2PDev &M, uint32_t a, uint64_t now, uint32_t uid) {
+  const P2PDev *G = mdev_of(M.C);
+  const uint32_t A = M.n_apps, mps = M.app_pkt_size[a];
+  const uint32_t base = tc_offsets(M.app_pkt_size, A)[a], cnt = tc_offsets(M.app_pkt_size, A)[a + 1] - base;
+  const uint32_t *T = tc_entries(M.app_pkt_size, A) + 2 * (size_t)base;
+  const uint32_t an = M.app_node[a];
+  const uint32_t e0 = M.app_tot[A + a], seq0 = M.app_tot[a];
+  const uint32_t ttl = M.app_ttl[a];
+  const uint32_t idm = M.frag ? 0xffffu : 0xffffffffu;
+  // m_socket->Send (p): -1 with no route (udp-socket-impl.cc:595-601), for every datagram of the burst alike
+  const uint32_t out = route_at(M, an, M.app_dst_slot[a]);
+  const uint32_t ipid0 = M.node_ipid[an];
+  uint32_t e = e0, n = 0;
+  uint64_t bytes = 0;
+  do {  // :319-333
+    const uint32_t ps = T[2 * e + 1], nfull = ps / mps;
+    for (uint32_t i = 0; i <= nfull; i++) {  // SendPacket (m_maxPacketSize) x nfull, SendPacket (packetSize % m_maxPacketSize)
+      const uint32_t ipsz = tc_ip_size(i < nfull ? mps : ps % mps);
+      if (out != 0xffffffffu) {
+        bytes += ipsz - 28u;
+        if (M.flowmon)  // m_sendOutgoingTrace (ipv4-l3-protocol.cc:618), per datagram with its own size
+          fm_first_tx(G, Pkt{a, (ipid0 + n) & idm, ipsz, ttl | ((seq0 + n) << 8)}, now, uid);
+      }
+      n++;
+    }
+    e = e + 1 == cnt ? 0u : e + 1;  // m_currentEntry++; m_currentEntry %= m_entries.size ()
+  } while (T[2 * e] == 0);
+  M.app_tot[A + a] = e;
+  M.app_tot[2 * A + a]++;
+  if (out != 0xffffffffu) {  // ++m_sent only when Send returned >= 0; BuildHeader: m_identification++ per datagram
+    if (seq0 + n > TC_SEQ_LIMIT) atomicOr(M.error, ERR_TRACE_SEQ);
+    M.app_tot[a] = seq0 + n;
+    M.node_ipid[an] = ipid0 + n;
+    M.appc[a].tx_packets += n;
+    M.appc[a].tx_bytes += bytes;
+  }
+  // Simulator::Schedule (MilliSeconds (entry->timeToSend), &UdpTraceClient::Send, this) (:334)
+  return TcSend{out, e0, ipid0, seq0, n, 0, (int64_t)T[2 * e] * 1000000ll};
+}
+// The device step's walk over a burst: the datagram at (entry e, index i in the entry's frame), the k-th of the burst,
+// and the position after it; more: another datagram follows.  Out of line: the handlers hold a call, not the walk.
+struct TcStep {
+  Pkt p;
+  uint32_t e, i, more;
+};
+__device__ __noinline__ TcStep tc_step(const P2PDev *G, uint32_t a, uint32_t e, uint32_t i, uint32_t k, uint32_t ipid0,
+                                       uint32_t ttlw) {
+  const P2PDev &M = mdev_ref(G);
+  const uint32_t A = M.n_apps, mps = M.app_pkt_size[a];
+  const uint32_t base = tc_offsets(M.app_pkt_size, A)[a], cnt = tc_offsets(M.app_pkt_size, A)[a + 1] - base;
+  const uint32_t *T = tc_entries(M.app_pkt_size, A) + 2 * (size_t)base;
+  const uint32_t ps = T[2 * e + 1], nfull = ps / mps;
+  const uint32_t idm = M.frag ? 0xffffu : 0xffffffffu;
+  TcStep s;
+  s.p = Pkt{a, (ipid0 + k) & idm, tc_ip_size(i < nfull ? mps : ps % mps), ttlw + (k << 8)};
+  if (i < nfull) {
+    s.e = e, s.i = i + 1, s.more = 1;
+  } else {
+    s.e = e + 1 == cnt ? 0u : e + 1;
+    s.i = 0;
+    s.more = T[2 * s.e] == 0 ? 1u : 0u;
+  }
+  return s;
 }
 
 // Icmpv4L4Protocol::SendMessage (icmpv4-l4-protocol.cc:85-129): RouteOutput towards the error's
@@ -1411,6 +1511,15 @@ __device__ __forceinline__ NodeOut node_part_full(const P2PDev &M, Emit &E, uint
         M.app_flags[a] |= 4u;
         post = Post{true, M.app_interval[a], K_SEND | (g << 8), a};
       }
+    } else if (PORTS && M.app_kind[a] == NSGPU_APP_UDP_TRACE_CLIENT) {  // UdpTraceClient::Send (udp-trace-client.cc:311-335)
+      M.app_flags[a] = f & ~4u;
+      const TcSend t = tc_send(M, a, E.now, E.uid);
+      if (t.out == 0xffffffffu) hs.no_route += t.n;  // (every SendPacket's Send failed: m_sent stays)
+      else act = Act{ACT_SEND, t.out, Pkt{a, t.ipid0, TC_BURST | t.e0, M.app_ttl[a] | (t.seq0 << 8)}};
+      const uint32_t g = (M.app_send_gen[a] + 1) & 0xffffffu;
+      M.app_send_gen[a] = g;
+      M.app_flags[a] |= 4u;
+      post = Post{true, t.delay, K_SEND | (g << 8), a};
     } else {
       M.app_flags[a] = f & ~4u;
       const uint32_t sz = M.app_pkt_size[a];
@@ -1452,7 +1561,8 @@ __device__ __forceinline__ NodeOut node_part_full(const P2PDev &M, Emit &E, uint
           E.child(0, E.ctx, K_SEND | (g << 8), a, Pkt{0, 0, 0, 0});
         } else if (PORTS && M.app_kind[a] == NSGPU_APP_UDP_SERVER) {  // Bind (Any, port); SetRecvCallback (HandleRead)
           M.app_flags[a] = (M.app_flags[a] | AF_BOUND | AF_UDP_SERVER) & ~AF_RX_CLEARED;
-        } else if (PORTS && M.app_kind[a] == NSGPU_APP_UDP_CLIENT) {
+        } else if (PORTS && (M.app_kind[a] == NSGPU_APP_UDP_CLIENT || M.app_kind[a] == NSGPU_APP_UDP_TRACE_CLIENT)) {
+          // UdpTraceClient::StartApplication (udp-trace-client.cc:234-256) does the same.
           // UdpClient::StartApplication: Bind, Connect, SetRecvCallback (null), Schedule (Seconds (0), Send) — its
           // ephemeral-port socket is no endpoint any flow of this subset addresses (bit 1 stays clear)
           const uint32_t g = (M.app_send_gen[a] + 1) & 0xffffffu;
@@ -1558,7 +1668,7 @@ struct ColdOut {
   int64_t pdelay;
   uint32_t pkind, pa;
   uint32_t xdrop, n, trseq;
-  uint32_t stat;  // ttl_drops | no_route << 4 | unreach << 8 | icmp << 12 | stop << 16 | cancelled << 17
+  uint32_t stat;  // ttl_drops | no_route << 4 | unreach << 8 | icmp << 12 | stop << 16 | cancelled << 17 (| no_route >> 4 << 18)
 };
 static_assert(sizeof(ColdOut) <= 64, "ColdOut is returned in registers");
 enum : uint32_t { CF_TLOC = 1, CF_DEMOTE = 2, CF_RX_ATOMIC = 4, CF_RESUMED = 8 };
@@ -1592,8 +1702,10 @@ __device__ __noinline__ ColdOut node_part_cold(const P2PDev *G, uint64_t now, ui
   HStat hs{0, 0, 0, 0, 0, false};
   const NodeOut o = node_part_full<PORTS>(M, E, kind_word, a, pkt, sink, hs, (flags & CF_RX_ATOMIC) != 0,
                                           (flags & CF_RESUMED) != 0);
+  // (PORTS: a trace client's burst without a route counts one no_route a datagram, beyond four bits: the rest above bit 18)
+  const uint32_t nr = PORTS ? ((hs.no_route & 15u) << 4) | ((hs.no_route >> 4) << 18) : hs.no_route << 4;
   return ColdOut{o.act.op, o.act.dev, o.act.p, o.post.delay, o.post.valid ? o.post.kind : 0u, o.post.a, o.xdrop, E.n,
-                 E.trseq, hs.ttl_drops | (hs.no_route << 4) | (hs.unreach << 8) | (hs.icmp << 12) |
+                 E.trseq, hs.ttl_drops | nr | (hs.unreach << 8) | (hs.icmp << 12) |
                               ((hs.stop ? 1u : 0u) << 16) | ((o.cancelled ? 1u : 0u) << 17)};
 }
 // The node part as the handlers inline it: a TransmitComplete, and a Receive that is forwarded (route found, TTL
@@ -1655,6 +1767,7 @@ __device__ __forceinline__ NodeOut node_part(const P2PDev &M, Emit &E, uint32_t 
   E.trseq = o.trseq;
   hs.ttl_drops += o.stat & 15u;
   hs.no_route += (o.stat >> 4) & 15u;
+  if constexpr (PORTS) hs.no_route += (o.stat >> 18) << 4;
   hs.unreach += (o.stat >> 8) & 15u;
   hs.icmp += (o.stat >> 12) & 15u;
   if (o.stat & (1u << 16)) hs.stop = true;

@@ -1148,15 +1148,24 @@ __device__ __forceinline__ void device_step(const P2PDev &M, Emit &E, const Act 
   if constexpr (!EXT) {
     device_act_cached(M, E, act, D);
   } else {
-    const bool fr = M.frag && is_fragmenting_send(act.op, act.p.size);
+    // ... and a UdpTraceClient's Send runs it once per datagram of the burst, in order (udp-trace-client.cc:319-333: the
+    // SendPacket calls of one event; nsgpu_p2p_dev.h "UdpTraceClient"): each m_txTrace, then Enqueue or Drop
+    const bool bu = is_burst_send(act.op, act.p.size);
+    const bool fr = !bu && M.frag && is_fragmenting_send(act.op, act.p.size);
     Act f = act;
     uint32_t off = 0, nf = 0;
+    uint32_t be = act.p.size & ~TC_BURST, bi = 0;
     bool more = false;
     do {
       if (fr) {
         f.p = fragment_at(act.p, off, &more);
         off += FRAG_PART;
         nf++;
+      } else if (bu) {
+        const TcStep t = tc_step(mdev_of(M.C), act.p.app, be, bi, nf++, act.p.ipid, act.p.ttl);
+        f.p = t.p;
+        be = t.e, bi = t.i;
+        more = t.more != 0;
       }
       device_act_cached<true>(M, E, f, D);
     } while (more);
@@ -2086,6 +2095,8 @@ __device__ __forceinline__ void hub_node(const P2PDev &M, Ctl &C, uint32_t c, ui
         // (... and so does a fragment timeout's error: the Drop record that follows its Send is XDROP_FRAG's, which
         // only xdrop_record decodes)
         if (PORTS && M.frag && (is_fragmenting_send(op[u], hp->p.size) || (hp->xdrop & XDROP_FRAG))) pd[u] |= 0x80000000u;
+        // (... and a trace client's burst: several queue steps of one event)
+        if (PORTS && is_burst_send(op[u], hp->p.size)) pd[u] |= 0x80000000u;
       }
 #pragma unroll
     for (int u = 0; u < HSO; u++)

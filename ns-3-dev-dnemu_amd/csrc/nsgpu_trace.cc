@@ -290,12 +290,13 @@ bool record_ok(const nsgpu_trace_codec &c, const nsgpu_trace_record &r) {
   return r.size >= (l3_record(r.kind) ? 0 : PPP) && ip_len >= 28u;
 }
 
-// A record of a UdpClient's flow: its payload starts with a SeqTsHeader (sequence number, send time) whose bytes
-// and Packet::Print wording no test here pins, so the codec refuses it instead of writing zeros.
+// A record of a UdpClient's or a UdpTraceClient's flow: its payload starts with a SeqTsHeader (sequence number, send
+// time) whose bytes and Packet::Print wording no test here pins, so the codec refuses it instead of writing zeros.
 bool seqts_record(const nsgpu_trace_codec &c, const nsgpu_trace_record &r) {
-  return c.app_kind[r.app & NSGPU_PKT_APP] == NSGPU_APP_UDP_CLIENT;
+  const uint32_t k = c.app_kind[r.app & NSGPU_PKT_APP];
+  return k == NSGPU_APP_UDP_CLIENT || k == NSGPU_APP_UDP_TRACE_CLIENT;
 }
-const char *const kSeqTs = "a UdpClient datagram: the codec does not write SeqTsHeader payloads";
+const char *const kSeqTs = "a UdpClient datagram (or a UdpTraceClient's): the codec does not write SeqTsHeader payloads";
 // A record of an IPv4 fragment (frag scenarios: offset or MF above the identification, nsgpu_types.h): Packet::Print's
 // wording for fragmented items and the fragments' bytes are pinned by no fixture here, so it is refused as well.
 // An ICMP error about a fragment is refused too: the error's descriptor embeds the offending header's
@@ -383,7 +384,7 @@ int nsgpu_trace_codec_create(const nsgpu_p2p_scenario *sc, const nsgpu_trace_add
   }
   for (uint32_t a = 0; a < A; a++)
     if (c->app_node[a] >= N || ((c->app_kind[a] == NSGPU_APP_ONOFF || c->app_kind[a] == NSGPU_APP_ECHO_CLIENT ||
-                                  c->app_kind[a] == NSGPU_APP_UDP_CLIENT) &&
+                                  c->app_kind[a] == NSGPU_APP_UDP_CLIENT || c->app_kind[a] == NSGPU_APP_UDP_TRACE_CLIENT) &&
                                 c->app_dst[a] >= N)) {
       delete c;
       return set_error(NSGPU_EINVAL, "nsgpu_trace_codec_create: application %u names a node out of range", a);
@@ -403,7 +404,8 @@ int nsgpu_trace_codec_create(const nsgpu_p2p_scenario *sc, const nsgpu_trace_add
   std::vector<std::pair<int64_t, uint32_t>> order;
   for (uint32_t a = 0; a < A; a++)
     if (c->app_kind[a] == NSGPU_APP_ONOFF || c->app_kind[a] == NSGPU_APP_ECHO_CLIENT ||
-        c->app_kind[a] == NSGPU_APP_UDP_CLIENT)  // (a UdpClient's socket takes an ephemeral port like the others)
+        c->app_kind[a] == NSGPU_APP_UDP_CLIENT ||  // (a UdpClient's socket takes an ephemeral port like the others,
+        c->app_kind[a] == NSGPU_APP_UDP_TRACE_CLIENT)  // and so does a UdpTraceClient's)
       order.push_back({sc->app_start_ns[a], a});
   std::sort(order.begin(), order.end());
   std::vector<uint32_t> port(N, 49152);

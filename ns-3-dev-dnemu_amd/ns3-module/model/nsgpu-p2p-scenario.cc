@@ -24,6 +24,7 @@
 #include "ns3/udp-echo-server.h"
 #include "ns3/udp-client.h"
 #include "ns3/udp-server.h"
+#include "ns3/udp-trace-client.h"
 #include "ns3/inet-socket-address.h"
 #include "ns3/address.h"
 #include "ns3/uinteger.h"
@@ -60,7 +61,8 @@ NsgpuP2pScenario::NsgpuP2pScenario ()
     m_stop (-1),
     m_firstLink (true),
     m_engine (0),
-    m_codec (0)
+    m_codec (0),
+    m_hasTrace (false)
 {
 }
 
@@ -147,6 +149,66 @@ NsgpuP2pScenario::AddUdpServer (uint32_t node, Time start, Time stop, uint16_t p
   App a = {NSGPU_APP_UDP_SERVER, node, 0, 0, 0, 0, start.GetTimeStep (), stop.GetTimeStep (), 0, 0.0, 0.0, 0, 0, 0, 0,
            port, packetWindowSize};
   return AddApp (a);
+}
+
+uint32_t
+NsgpuP2pScenario::AddUdpTraceClient (uint32_t node, uint32_t dstNode, Time start, Time stop,
+                                     const std::vector<nsgpu_udp_trace_entry> &entries, uint32_t maxPacketSize,
+                                     uint32_t ttl, uint16_t remotePort)
+{
+  App a = {NSGPU_APP_UDP_TRACE_CLIENT, node, dstNode, maxPacketSize, 0, ttl, start.GetTimeStep (), stop.GetTimeStep (),
+           0, 0.0, 0.0, 0, 0, 0, remotePort, 0, 0};
+  a.entries = entries;
+  return AddApp (a);
+}
+
+std::vector<nsgpu_udp_trace_entry>
+NsgpuP2pScenario::LoadTraceFile (std::string filename)
+{
+  // UdpTraceClient::SetTraceFile (udp-trace-client.cc:143-154): "" -> LoadDefaultTrace, else LoadTrace (filename)
+  uint64_t n = 0;
+  if (filename == "")
+    {
+      NSGPU_TRY (nsgpu_udp_trace_default (0, 0, &n));
+    }
+  else
+    {
+      NSGPU_TRY (nsgpu_udp_trace_load (filename.c_str (), 0, 0, &n));
+    }
+  std::vector<nsgpu_udp_trace_entry> e (std::max (n, (uint64_t) 1));
+  if (filename == "")
+    {
+      NSGPU_TRY (nsgpu_udp_trace_default (&e[0], n, &n));
+    }
+  else
+    {
+      NSGPU_TRY (nsgpu_udp_trace_load (filename.c_str (), &e[0], n, &n));
+    }
+  e.resize (n);
+  return e;
+}
+
+void
+NsgpuP2pScenario::DeclareTrace (Ptr<Application> app, std::string filename)
+{
+  m_declaredTrace.push_back (std::make_pair (app, filename));
+}
+
+void
+NsgpuP2pScenario::GetUdpTraceClient (uint32_t app, uint32_t &sent, uint32_t &currentEntry, uint32_t &sends) const
+{
+  if (m_engine == 0 || app >= m_app.size () || m_app[app].kind != NSGPU_APP_UDP_TRACE_CLIENT)
+    {
+      NS_FATAL_ERROR ("NsgpuP2pScenario::GetUdpTraceClient: application " << app << " is not a UdpTraceClient of an engine");
+    }
+  std::vector<nsgpu_udp_trace_client_record> rec (m_app.size ());
+  if (nsgpu_p2p_udp_trace_clients (m_engine, &rec[0], 0) != NSGPU_OK)
+    {
+      NS_FATAL_ERROR ("libnsgpu: " << nsgpu_last_error ());
+    }
+  sent = rec[app].sent;
+  currentEntry = rec[app].current_entry;
+  sends = rec[app].sends;
 }
 
 void
@@ -676,6 +738,34 @@ NsgpuP2pScenario::FromNodeList (Ptr<HipSimulatorImpl> impl)
           remote = Ipv4Address::ConvertFrom (ra.Get ()).Get ();
           x.remotePort = UintAttribute (o, "RemotePort");
         }
+      else if (DynamicCast<UdpTraceClient> (o) != 0)
+        {
+          // m_entries is private and TraceFilename has no getter: the program names the trace (DeclareTrace)
+          size_t k = 0;
+          while (k < m_declaredTrace.size () && m_declaredTrace[k].first != o)
+            {
+              k++;
+            }
+          if (k == m_declaredTrace.size ())
+            {
+              NS_FATAL_ERROR ("NsgpuP2pScenario::FromNodeList: UdpTraceClient on node " << n << ": its trace is not "
+                              "declared — the application's entries cannot be read back (m_entries is private, "
+                              "TraceFilename has no getter); call DeclareTrace (app, filename) before FromNodeList "
+                              "(\"\": the default trace)");
+            }
+          x.kind = NSGPU_APP_UDP_TRACE_CLIENT;
+          x.entries = LoadTraceFile (m_declaredTrace[k].second);
+          x.size = UintAttribute (o, "MaxPacketSize");
+          AddressValue ra;
+          o->GetAttribute ("RemoteAddress", ra);
+          if (!Ipv4Address::IsMatchingType (ra.Get ()))
+            {
+              NS_FATAL_ERROR ("NsgpuP2pScenario::FromNodeList: UdpTraceClient on node " << n << ": RemoteAddress is "
+                              "not an Ipv4Address (IPv6 remotes are outside the subset)");
+            }
+          remote = Ipv4Address::ConvertFrom (ra.Get ()).Get ();
+          x.remotePort = UintAttribute (o, "RemotePort");
+        }
       else if (DynamicCast<UdpServer> (o) != 0)
         {
           x.kind = NSGPU_APP_UDP_SERVER;
@@ -685,10 +775,11 @@ NsgpuP2pScenario::FromNodeList (Ptr<HipSimulatorImpl> impl)
       else
         {
           NS_FATAL_ERROR ("NsgpuP2pScenario::FromNodeList: node " << n << " application " << a
-                          << " is not OnOff / PacketSink / UdpEcho / UdpClient / UdpServer (not in the GPU-resident "
+                          << " is not OnOff / PacketSink / UdpEcho / UdpClient / UdpServer / UdpTraceClient (not in the GPU-resident "
                           "subset)");
         }
-      if (x.kind == NSGPU_APP_ONOFF || x.kind == NSGPU_APP_ECHO_CLIENT || x.kind == NSGPU_APP_UDP_CLIENT)
+      if (x.kind == NSGPU_APP_ONOFF || x.kind == NSGPU_APP_ECHO_CLIENT || x.kind == NSGPU_APP_UDP_CLIENT ||
+          x.kind == NSGPU_APP_UDP_TRACE_CLIENT)
         {
           if (nodeOfAddr.find (remote) == nodeOfAddr.end ())
             {
@@ -715,7 +806,7 @@ NsgpuP2pScenario::PopulateRoutingTables (void)
   for (size_t i = 0; i < m_app.size (); i++)
     {
       if (m_app[i].kind == NSGPU_APP_ONOFF || m_app[i].kind == NSGPU_APP_ECHO_CLIENT ||
-          m_app[i].kind == NSGPU_APP_UDP_CLIENT)
+          m_app[i].kind == NSGPU_APP_UDP_CLIENT || m_app[i].kind == NSGPU_APP_UDP_TRACE_CLIENT)
         {
           m_dstSlot[m_app[i].dst] = 0;  // mark; numbered below in node order
           if (m_icmp || m_app[i].kind == NSGPU_APP_ECHO_CLIENT)
@@ -774,7 +865,8 @@ NsgpuP2pScenario::Fill (void)
   for (size_t i = 0; i < A; i++)
     {
       const App &a = m_app[i];
-      const bool sender = a.kind == NSGPU_APP_ONOFF || a.kind == NSGPU_APP_ECHO_CLIENT || a.kind == NSGPU_APP_UDP_CLIENT;
+      const bool sender = a.kind == NSGPU_APP_ONOFF || a.kind == NSGPU_APP_ECHO_CLIENT ||
+                          a.kind == NSGPU_APP_UDP_CLIENT || a.kind == NSGPU_APP_UDP_TRACE_CLIENT;
       m_cPort[i] = a.port, m_cWindow[i] = a.window;
       m_cKind[i] = a.kind, m_cNode[i] = a.node, m_cDst[i] = a.dst, m_cSize[i] = a.size, m_cMaxb[i] = a.maxBytes;
       m_cTtl[i] = a.ttl, m_cCount[i] = a.count, m_cIvl[i] = a.interval, m_cRaddr[i] = a.remoteAddr;
@@ -828,6 +920,22 @@ NsgpuP2pScenario::Fill (void)
       sc.rng_seed = m_rngSeed, sc.rng_run = m_rngRun;
     }
   sc.flowmon = m_flowStats ? 1u : 0u;
+  // the UdpTraceClients' entries travel beside the struct (nsgpu_p2p_scenario_ext)
+  m_hasTrace = false;
+  m_cTraceOff.assign (A + 1, 0), m_cTraceEnt.clear ();
+  for (size_t i = 0; i < A; i++)
+    {
+      if (m_app[i].kind == NSGPU_APP_UDP_TRACE_CLIENT)
+        {
+          m_hasTrace = true;
+          m_cTraceEnt.insert (m_cTraceEnt.end (), m_app[i].entries.begin (), m_app[i].entries.end ());
+        }
+      m_cTraceOff[i + 1] = m_cTraceEnt.size ();
+    }
+  m_cTraceEnt.push_back (nsgpu_udp_trace_entry ());  // (never empty: its address is taken)
+  m_ext = nsgpu_p2p_scenario_ext ();
+  m_ext.size = sizeof (m_ext);
+  m_ext.trace_off = &m_cTraceOff[0], m_ext.trace_entries = &m_cTraceEnt[0];
   sc.n_setup = m_setup.size ();
   sc.setup_kind = m_cSk.empty () ? 0 : &m_cSk[0];
   sc.setup_index = m_cSi.empty () ? 0 : &m_cSi[0];
@@ -837,7 +945,7 @@ nsgpu_p2p *
 NsgpuP2pScenario::CreateEngine (uint64_t poolCap, uint64_t logCap)
 {
   Fill ();
-  if (nsgpu_p2p_create (&m_sc, poolCap, logCap, &m_engine) != NSGPU_OK ||
+  if (nsgpu_p2p_create_ex (&m_sc, m_hasTrace ? &m_ext : 0, poolCap, logCap, &m_engine) != NSGPU_OK ||
       nsgpu_p2p_reset (m_engine, 0) != NSGPU_OK)
     {
       NS_FATAL_ERROR ("libnsgpu: " << nsgpu_last_error ());

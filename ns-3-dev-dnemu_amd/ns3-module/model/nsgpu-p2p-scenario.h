@@ -22,6 +22,7 @@
 
 #include "ns3/nstime.h"
 #include "ns3/ptr.h"
+#include "ns3/application.h"
 #include "nsgpu.h"
 #include "hip-simulator-impl.h"
 #include <stdint.h>
@@ -53,6 +54,22 @@ public:
   uint32_t AddUdpServer (uint32_t node, Time start, Time stop, uint16_t port = 100, uint16_t packetWindowSize = 32);
   /* UdpServer::GetReceived () / GetLost () of application `app` (a UdpServer) as the engine counts them now */
   void GetUdpServer (uint32_t app, uint32_t &received, uint32_t &lost) const;
+  /* UdpTraceClientHelper (address of dstNode, remotePort, filename).Install (udp-trace-client.cc): `entries` as
+   * LoadTrace / LoadDefaultTrace leave them (LoadTraceFile; DefaultTrace), maxPacketSize in [1, 1472].  One Send event
+   * emits every entry up to the next one whose timeToSend is not 0, a frame above maxPacketSize cut into datagrams; at
+   * most NSGPU_UDP_TRACE_MAX_BURST datagrams a Send.  GetUdpTraceClient: m_sent, m_currentEntry and the Send events
+   * run, as the engine counts them now. */
+  uint32_t AddUdpTraceClient (uint32_t node, uint32_t dstNode, Time start, Time stop,
+                              const std::vector<nsgpu_udp_trace_entry> &entries, uint32_t maxPacketSize, uint32_t ttl,
+                              uint16_t remotePort = 100);
+  static std::vector<nsgpu_udp_trace_entry> LoadTraceFile (std::string filename);  /* "": the default trace */
+  static std::vector<nsgpu_udp_trace_entry> DefaultTrace (void) { return LoadTraceFile (""); }
+  void GetUdpTraceClient (uint32_t app, uint32_t &sent, uint32_t &currentEntry, uint32_t &sends) const;
+  /* FromNodeList mirrors a UdpTraceClient only when the program declared its trace here before: the application's
+   * m_entries are private and its TraceFilename attribute has no getter, so the file (or "": the default trace) cannot
+   * be read back from the object.  An undeclared UdpTraceClient ends FromNodeList in a fatal error.  A file is loaded
+   * here as the application loaded it; SetRemote's clearing of the entries and SetTraceFile during Run are not modelled. */
+  void DeclareTrace (Ptr<Application> app, std::string filename);
   uint32_t AddOnOff (uint32_t node, uint32_t dstNode, Time start, Time stop, uint64_t rateBps, uint32_t packetSize,
                      double onSeconds, double offSeconds, uint32_t maxBytes, uint32_t ttl);
   void Stop (Time at);
@@ -109,7 +126,8 @@ public:
    * (OnOffApplication DataRate / PacketSize / Remote / OnTime / OffTime (ConstantVariable) / MaxBytes,
    * PacketSink Local (Any, port), UdpEchoServer Port, UdpEchoClient RemoteAddress / RemotePort / MaxPackets /
    * Interval / PacketSize, UdpClient RemoteAddress / RemotePort / MaxPackets / Interval / PacketSize, UdpServer Port /
-   * PacketWindowSize; StartTime / StopTime).  The UDP ports are always given to the engine: a datagram reaches the
+   * PacketWindowSize, UdpTraceClient RemoteAddress / RemotePort / MaxPacketSize with the trace DeclareTrace named;
+   * StartTime / StopTime).  The UDP ports are always given to the engine: a datagram reaches the
    * application bound to its destination port, a node may host several bound applications on distinct ports.  The setup list follows `impl`'s journal: per node, its first
    * zero-delay call is Node::Start, the next ones its devices' NetDevice::Start then its applications'
    * Application::Start (the helpers add devices before applications); the Stop event; every other call
@@ -153,6 +171,7 @@ private:
     uint32_t remotePort;
     uint32_t port;         // bound port of a PacketSink / UdpEchoServer / UdpServer
     uint32_t window;       // UdpServer PacketWindowSize
+    std::vector<nsgpu_udp_trace_entry> entries;  // UdpTraceClient m_entries
   };
   struct Em
   {
@@ -176,6 +195,7 @@ private:
   std::vector<Ptr<NetDevice> > m_devObj;                // FromNodeList: the ns-3 device of each engine device
   std::vector<Em> m_em;                                 // per device (empty: no device has a receive error model)
   std::vector<std::pair<Ptr<NetDevice>, uint32_t> > m_errorStream;  // SetErrorStream
+  std::vector<std::pair<Ptr<Application>, std::string> > m_declaredTrace;  // DeclareTrace
   uint32_t m_nDst;
   bool m_icmp;
   bool m_frag;
@@ -188,6 +208,10 @@ private:
   nsgpu_trace_codec *m_codec;
   // the C view (Fill)
   nsgpu_p2p_scenario m_sc;
+  nsgpu_p2p_scenario_ext m_ext;  // the UdpTraceClients' entries (m_hasTrace: given to the _ex entry points)
+  bool m_hasTrace;
+  std::vector<uint64_t> m_cTraceOff;
+  std::vector<nsgpu_udp_trace_entry> m_cTraceEnt;
   std::vector<uint32_t> m_cDevNode, m_cDevPeer, m_cDevQmax, m_cKind, m_cNode, m_cDst, m_cSlot, m_cSrc, m_cSize,
     m_cMaxb, m_cTtl, m_cCount, m_cSk, m_cSi, m_cRaddr, m_cRport, m_cPort, m_cWindow, m_cEmKind, m_cEmEnabled,
     m_cEmUnit, m_cEmStream, m_cEmList;

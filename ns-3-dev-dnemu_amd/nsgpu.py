@@ -162,6 +162,9 @@ SIGNATURES = {
     "nsgpu_p2p_pending": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "nsgpu_p2p_get_wide": (C.c_int, [_vp, _vp]),
     "nsgpu_p2p_udp_servers": (C.c_int, [_vp, _vp, _vp]),
+    "nsgpu_p2p_udp_trace_clients": (C.c_int, [_vp, _vp, _vp]),
+    "nsgpu_udp_trace_load": (C.c_int, [C.c_char_p, _vp, _u64, _vp]),
+    "nsgpu_udp_trace_default": (C.c_int, [_vp, _u64, _vp]),
     "nsgpu_p2p_frag_stats": (C.c_int, [_vp, _vp, _vp]),
     "nsgpu_loss_counter_run": (C.c_int, [C.c_uint32, _vp, C.c_uint64, _vp, C.c_int, _vp]),
     "nsgpu_p2p_error_models": (C.c_int, [_vp, _vp, _vp]),
@@ -173,6 +176,7 @@ SIGNATURES = {
     "nsgpu_p2p_inject_send": (C.c_int, [_vp, _u32, _u64, _u32, _u32, _vp, _vp, _vp]),
     "nsgpu_p2p_counters": (C.c_int, [_vp, _vp, _vp, _vp]),
     "nsgpu_p2p_create": (C.c_int, [_vp, _u64, _u64, C.POINTER(C.c_void_p)]),
+    "nsgpu_p2p_create_ex": (C.c_int, [_vp, _vp, _u64, _u64, C.POINTER(C.c_void_p)]),
     "nsgpu_p2p_reset": (C.c_int, [_vp, _vp]),
     "nsgpu_p2p_run": (C.c_int, [_vp, _vp]),
     "nsgpu_p2p_results": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp]),
@@ -192,6 +196,8 @@ SIGNATURES = {
     "nsgpu_comm_destroy": (C.c_int, [_vp]),
     "nsgpu_p2p_create_dist": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _u64, _u64, C.POINTER(C.c_void_p)]),
     "nsgpu_p2p_dist_plan": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _u64, _vp]),
+    "nsgpu_p2p_create_dist_ex": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _u64, _u64, C.POINTER(C.c_void_p)]),
+    "nsgpu_p2p_dist_plan_ex": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _u64, _vp]),
     "nsgpu_wifil_listen": (C.c_int, [_vp, _u32, C.c_int]),
     "nsgpu_wifil_send_plan": (C.c_int, [_vp, _u32, _u32, _vp, _vp, _vp, _u64, C.POINTER(C.c_uint64)]),
     "nsgpu_wifil_next_end": (C.c_int, [_vp, _vp]),

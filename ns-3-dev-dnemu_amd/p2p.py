@@ -27,7 +27,9 @@ TRACE_RECORD_DTYPE = np.dtype([("ts", "<u8"), ("uid", "<u4"), ("seq", "<u2"), ("
 
 APP_ONOFF, APP_SINK, APP_ECHO_CLIENT, APP_ECHO_SERVER = 0, 1, 2, 3
 APP_UDP_CLIENT, APP_UDP_SERVER = 4, 5  # (Scenario (ports=True) only)
-SENDERS = (APP_ONOFF, APP_ECHO_CLIENT, APP_UDP_CLIENT)  # applications that originate datagrams towards app["dst"]
+APP_UDP_TRACE_CLIENT = 6  # (ports=True only; its trace entries travel in a ScenarioExt)
+# applications that originate datagrams towards app["dst"]
+SENDERS = (APP_ONOFF, APP_ECHO_CLIENT, APP_UDP_CLIENT, APP_UDP_TRACE_CLIENT)
 BOUND = (APP_SINK, APP_ECHO_SERVER, APP_UDP_SERVER)  # applications whose socket is bound to (Any, app["port"])
 SETUP_NODE, SETUP_DEVICE, SETUP_APP, SETUP_STOP, SETUP_UID, SETUP_NOOP = 0, 1, 2, 3, 4, 5
 NO_ROUTE = 0xFFFFFFFF
@@ -55,6 +57,11 @@ class ScenarioStruct(C.Structure):
     ]
 
 
+class ScenarioExt(C.Structure):
+    """nsgpu_p2p_scenario_ext (include/nsgpu_types.h): the UdpTraceClients' entries, for the _ex entry points."""
+    _fields_ = [("size", C.c_uint32), ("pad_", C.c_uint32), ("trace_off", C.c_void_p), ("trace_entries", C.c_void_p)]
+
+
 class P2PStats(C.Structure):
     _fields_ = [("dispatched", C.c_uint64), ("cancelled", C.c_uint64), ("digest", C.c_uint64),
                 ("final_ts", C.c_uint64), ("next_uid", C.c_uint32), ("windows", C.c_uint32),
@@ -69,6 +76,10 @@ APP_COUNTERS_DTYPE = np.dtype([("tx_packets", "<u4"), ("rx_packets", "<u4"), ("t
                                ("rx_bytes", "<u8")])
 # nsgpu_udp_server_record: UdpServer::GetReceived / GetLost, the loss counter's m_lastMaxSeqNum
 UDP_SERVER_DTYPE = np.dtype([("received", "<u4"), ("lost", "<u4"), ("last_max_seq", "<u4"), ("pad_", "<u4")])
+# nsgpu_udp_trace_entry (UdpTraceClient::TraceEntry without the frame type), nsgpu_udp_trace_client_record
+UDP_TRACE_ENTRY_DTYPE = np.dtype([("time_to_send_ms", "<u4"), ("packet_size", "<u4")])
+UDP_TRACE_CLIENT_DTYPE = np.dtype([("sent", "<u4"), ("current_entry", "<u4"), ("sends", "<u4"), ("pad_", "<u4")])
+UDP_TRACE_MAX_BURST = 256  # NSGPU_UDP_TRACE_MAX_BURST: datagrams of one Send
 # nsgpu_frag_stats: the IPv4 fragmentation counters of a run (Scenario (frag=True))
 FRAG_STATS_FIELDS = ("fragmented", "fragments_sent", "reassembled", "timeouts", "cancelled_timers", "max_list")
 FRAG_CAP = 128  # entries of a node's reassembly list (a run that would pass it fails)
@@ -188,6 +199,14 @@ class Scenario:
         return self._app(kind=APP_UDP_CLIENT, node=node, start=start_ns, stop=stop_ns, dst=dst, size=size,
                          count=count, interval=interval_ns, ttl=ttl, remote_addr=remote_addr,
                          remote_port=remote_port)
+
+    # UdpTraceClientHelper (address, port, filename).Install: MaxPacketSize; entries = [(timeToSend ms, packetSize)]
+    # as LoadTrace / LoadDefaultTrace leave them (load_trace_file; None: DEFAULT_TRACE)
+    def add_udp_trace_client(self, node, dst, start_ns, stop_ns, entries=None, max_packet_size=1024, remote_port=100,
+                             ttl=64, remote_addr=None):
+        ent = [(int(t), int(z)) for t, z in (DEFAULT_TRACE if entries is None else entries)]
+        return self._app(kind=APP_UDP_TRACE_CLIENT, node=node, start=start_ns, stop=stop_ns, dst=dst,
+                         size=max_packet_size, ttl=ttl, remote_addr=remote_addr, remote_port=remote_port, entries=ent)
 
     def add_udp_server(self, node, start_ns, stop_ns, port=100, window=32):  # UdpServerHelper (port).Install
         return self._app(kind=APP_UDP_SERVER, node=node, start=start_ns, stop=stop_ns, port=port, ttl=0,
@@ -382,6 +401,51 @@ class Scenario:
         s.flowmon = 1 if getattr(self, "flowmon", False) else 0
         s._keep = arrays  # keep the arrays alive with the struct
         return s
+
+    def c_ext(self):
+        """The nsgpu_p2p_scenario_ext of a scenario with a UdpTraceClient (None without one: the plain entry points)."""
+        if not any(a["kind"] == APP_UDP_TRACE_CLIENT for a in self.apps):
+            return None
+        off = np.zeros(len(self.apps) + 1, np.uint64)
+        ent = []
+        for i, a in enumerate(self.apps):
+            if a["kind"] == APP_UDP_TRACE_CLIENT:
+                ent.extend(a["entries"])
+            off[i + 1] = len(ent)
+        for t, z in ent:
+            if not (0 <= t < 1 << 32 and 0 <= z < 1 << 32):
+                raise ValueError("trace entry outside uint32")
+        arr = np.array(ent or [(0, 0)], dtype=np.uint64).astype(np.uint32).view(UDP_TRACE_ENTRY_DTYPE).reshape(-1)
+        x = ScenarioExt()
+        x.size = C.sizeof(ScenarioExt)
+        x.trace_off, x.trace_entries = off.ctypes.data, arr.ctypes.data
+        x._keep = (off, arr)
+        return x
+
+
+def _trace_entries(call):
+    n = C.c_uint64(0)
+    nsgpu.check(call(None, 0, C.byref(n)))
+    out = np.zeros(max(n.value, 1), UDP_TRACE_ENTRY_DTYPE)
+    nsgpu.check(call(out.ctypes.data, n.value, C.byref(n)))
+    return [(int(e["time_to_send_ms"]), int(e["packet_size"])) for e in out[:n.value]]
+
+
+def load_trace_file(path):
+    """UdpTraceClient::LoadTrace (path) through the library's loader (nsgpu_udp_trace_load): [(timeToSend ms,
+    packetSize)] with the reference's quirks (a file that ends in whitespace yields its last entry twice; an unreadable
+    file gives the default trace)."""
+    return _trace_entries(lambda o, c, n: nsgpu.lib().nsgpu_udp_trace_load(str(path).encode(), o, c, n))
+
+
+# UdpTraceClient::LoadDefaultTrace's entries: (timeToSend ms, packetSize), B frames with 0
+DEFAULT_TRACE = ((0, 534), (40, 1542), (0, 134), (0, 390), (200, 765), (0, 407), (0, 504), (120, 903), (0, 421),
+                 (0, 587))
+
+
+def default_trace():
+    """The library's copy of the default trace (nsgpu_udp_trace_default)."""
+    return _trace_entries(lambda o, c, n: nsgpu.lib().nsgpu_udp_trace_default(o, c, n))
 
 
 def ip(dotted):
@@ -619,10 +683,15 @@ class Engine:
 
     def __init__(self, scenario, log_cap=0, pool_cap=0, stream=None):
         self.s = scenario.c_struct()
+        self.x = scenario.c_ext()
         self.stream = stream
         self.log_cap = log_cap
         h = C.c_void_p()
-        nsgpu.check(nsgpu.lib().nsgpu_p2p_create(C.byref(self.s), pool_cap, log_cap, C.byref(h)))
+        if self.x is None:
+            nsgpu.check(nsgpu.lib().nsgpu_p2p_create(C.byref(self.s), pool_cap, log_cap, C.byref(h)))
+        else:
+            nsgpu.check(nsgpu.lib().nsgpu_p2p_create_ex(C.byref(self.s), C.byref(self.x), pool_cap, log_cap,
+                                                         C.byref(h)))
         self.h = h.value
 
     def reset(self):
@@ -683,6 +752,13 @@ class Engine:
         """UdpServer received / lost / last_max_seq per application (nsgpu_p2p_udp_servers; zeros for other kinds)."""
         out = np.zeros(self.s.n_apps, UDP_SERVER_DTYPE)
         nsgpu.check(nsgpu.lib().nsgpu_p2p_udp_servers(self.h, out.ctypes.data, self.stream))
+        return out
+
+    def trace_clients(self):
+        """UdpTraceClient m_sent / m_currentEntry / Send events run per application (nsgpu_p2p_udp_trace_clients:
+        UDP_TRACE_CLIENT_DTYPE; zeros for other kinds)."""
+        out = np.zeros(self.s.n_apps, UDP_TRACE_CLIENT_DTYPE)
+        nsgpu.check(nsgpu.lib().nsgpu_p2p_udp_trace_clients(self.h, out.ctypes.data, self.stream))
         return out
 
     def frag_stats(self):
@@ -838,14 +914,19 @@ def dist_plan(scenario, owner, rank, nranks, pool_cap=0):
     collectives — X0 / X1 / X2 bytes, X2 records per peer, window capacities, lookaheads, window 0's bound —
     as a dict (arrays as lists).  owner None: the single engine's plan."""
     s = scenario.c_struct()
+    x = scenario.c_ext()
     own = None
     if owner is not None:
         own = np.ascontiguousarray(owner, dtype=np.uint32)
         if len(own) != s.n_nodes:
             raise ValueError("owner: one rank per node")
     pl = Plan()
-    nsgpu.check(nsgpu.lib().nsgpu_p2p_dist_plan(C.byref(s), own.ctypes.data if own is not None else None, rank,
-                                                 nranks, pool_cap, C.byref(pl)))
+    if x is None:
+        nsgpu.check(nsgpu.lib().nsgpu_p2p_dist_plan(C.byref(s), own.ctypes.data if own is not None else None, rank,
+                                                     nranks, pool_cap, C.byref(pl)))
+    else:
+        nsgpu.check(nsgpu.lib().nsgpu_p2p_dist_plan_ex(C.byref(s), C.byref(x), own.ctypes.data if own is not None
+                                                        else None, rank, nranks, pool_cap, C.byref(pl)))
     out = {}
     for f, _t in Plan._fields_:
         v = getattr(pl, f)
@@ -879,9 +960,14 @@ class DistEngine(Engine):
         self.log_cap = log_cap
         self.comm = comm
         h = C.c_void_p()
-        nsgpu.check(nsgpu.lib().nsgpu_p2p_create_dist(C.byref(self.s), self.owner.ctypes.data, rank, nranks,
-                                                       comm.h if comm is not None else None, pool_cap, log_cap,
-                                                       C.byref(h)))
+        self.x = scenario.c_ext()
+        ch = comm.h if comm is not None else None
+        if self.x is None:
+            nsgpu.check(nsgpu.lib().nsgpu_p2p_create_dist(C.byref(self.s), self.owner.ctypes.data, rank, nranks, ch,
+                                                           pool_cap, log_cap, C.byref(h)))
+        else:
+            nsgpu.check(nsgpu.lib().nsgpu_p2p_create_dist_ex(C.byref(self.s), C.byref(self.x), self.owner.ctypes.data,
+                                                              rank, nranks, ch, pool_cap, log_cap, C.byref(h)))
         self.h = h.value
 
 
@@ -920,6 +1006,16 @@ class LoopbackGroup:
     def udp_servers(self):
         """Every application's UdpServer record from the rank owning its node (merge_results' rule)."""
         per = [m.udp_servers() for m in self.members]
+        app_node = self.members[0].s._keep["app_node"]
+        out = per[0].copy()
+        for r, rec in enumerate(per):
+            m = self.owner[app_node] == r
+            out[m] = rec[m]
+        return out
+
+    def trace_clients(self):
+        """Every application's UdpTraceClient record from the rank owning its node (merge_results' rule)."""
+        per = [m.trace_clients() for m in self.members]
         app_node = self.members[0].s._keep["app_node"]
         out = per[0].copy()
         for r, rec in enumerate(per):

@@ -220,10 +220,11 @@ class Codec:
         """(src, dst, sport, dport) of a datagram of flow app_word."""
         a = app_word & ~PKT_REPLY
         A = self.sc.apps[a]
-        if A["kind"] == p2p.APP_UDP_CLIENT:
+        if A["kind"] in (p2p.APP_UDP_CLIENT, p2p.APP_UDP_TRACE_CLIENT):
             # its payload starts with a SeqTsHeader (sequence number, send time) whose bytes and Packet::Print
             # wording nothing here pins: refused, not written as zeros
-            raise ValueError("trace codec: a UdpClient datagram (flow %d): SeqTsHeader payloads are not written" % a)
+            raise ValueError("trace codec: a %s datagram (flow %d): SeqTsHeader payloads are not written"
+                             % ("UdpClient" if A["kind"] == p2p.APP_UDP_CLIENT else "UdpTraceClient", a))
         req_src = self._out_addr(A["node"], A["dst"])
         req_dst = A["remote_addr"] if A["remote_addr"] is not None else self.first_addr.get(A["dst"], 0)
         if app_word & PKT_REPLY:  # UdpEchoServer::HandleRead -> SendTo (packet, 0, from)
