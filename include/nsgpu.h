@@ -642,6 +642,38 @@ int nsgpu_error_model_thresholds(uint32_t unit, double rate, double *out);
  * is NSGPU_EINVAL. */
 int nsgpu_rng_stream_run(uint32_t seed, uint32_t run, uint32_t stream_index, uint64_t n, double *out, int on_device,
                          void *stream);
+/* Random OnOff times (nsgpu_p2p_scenario_ext.app_on_var / app_off_var, nsgpu_types.h): a scenario with a Uniform or
+ * Exponential OnTime / OffTime is created through the _ex entry points.  Refused at create, each with its own message:
+ * a variable on an application that is not an OnOff; Uniform with min < 0, max < min or a non-finite parameter;
+ * Exponential with mean <= 0, a non-finite mean or one whose 23 * mean seconds overflow the timestamp, a bound < 0, a
+ * bound in (0, mean / 8) (the device redraws at most 1,024 times a value and fails the run with NSGPU_ERANGE beyond:
+ * error code 65536); two variables naming one RngStream; a variable and an enabled Rate error model naming one;
+ * NSGPU_RV_OTHER; an unknown kind.  Such an engine cannot join a host-closure runtime (nsgpu_p2p_setup_uid,
+ * nsgpu_sim_attach_p2p / _adopt_p2p) and refuses nsgpu_p2p_inject_send.
+ * nsgpu_p2p_onoff_draws: per application the GetValue calls on its OnTime and OffTime variables and their ambiguous
+ * attempts, n_apps records (n_apps must be the engine's; zeros without a random variable; a partitioned engine returns
+ * its own nodes' applications: the owner's values count).
+ * nsgpu_p2p_onoff_ambiguous: the log of ambiguous Exponential attempts (csrc/nsgpu_ranvar.h): *n = the records there
+ * are (at most NSGPU_RV_AMBIGUOUS_CAP), of which at most `cap` are written (out may be NULL with cap 0), *overflow =
+ * the attempts that found the log full.  *n == 0 and *overflow == 0: every timestamp of the run is the reference's on
+ * any host whose libm log errs by less than 1 ulp. */
+int nsgpu_p2p_onoff_draws(nsgpu_p2p *h, nsgpu_onoff_draw_record *out, uint32_t n_apps, void *stream);
+int nsgpu_p2p_onoff_ambiguous(nsgpu_p2p *h, nsgpu_ambiguous_draw *out, uint64_t cap, uint64_t *n, uint64_t *overflow,
+                              void *stream);
+/* A variable on its own: n values of *v, whose RngStream is the v->stream-th of a program with RngSeed `seed` and
+ * RngRun `run`: seconds[i] = GetValue (), ns[i] = Seconds (that), ambiguous[i] = 1 when an attempt of the draw was
+ * ambiguous, ns_other[i] = the other candidate's timestamp then (ns[i] otherwise).  Any output may be NULL.
+ * on_device = 0: on the host; 1: the same function in a one-thread kernel on `stream` (the function the engine's
+ * handlers call).  NSGPU_ERANGE: a bounded Exponential was rejected 1,024 times in one draw. */
+int nsgpu_ranvar_run(const nsgpu_ranvar *v, uint32_t seed, uint32_t run, uint64_t n, double *seconds, int64_t *ns,
+                     int64_t *ns_other, uint8_t *ambiguous, int on_device, void *stream);
+/* The device's log on the host: hi[i] + lo[i] = log (u[i]) for doubles u[i] in [2^-33, 1), hi the nearest double,
+ * the sum within 2^-40 ulp (hi) of the logarithm (double-double, + - * / only). */
+int nsgpu_ranvar_log(const double *u, uint64_t n, double *hi, double *lo);
+/* One ExponentialVariable attempt from the integer k behind u = k / 4294967088 (host): r = -mean * hi, Seconds (r),
+ * Seconds (-mean * hi's neighbour), whether r <= bound (or bound == 0), whether the attempt is ambiguous. */
+int nsgpu_ranvar_exponential(double mean, double bound, uint32_t k, double *r, int64_t *ns, int64_t *ns_other,
+                             int *accept, int *ambiguous);
 /* Launch mode of nsgpu_p2p_run: 0 = hipGraph replays (default), 1 = the same kernels launched one by
  * one (also selected by the environment variable NSGPU_P2P_EAGER; used under rocprofv3). */
 int nsgpu_p2p_set_eager(nsgpu_p2p *h, int eager);

@@ -93,7 +93,7 @@ typedef struct nsgpu_loss_trace {
 
 /* ---------------- point-to-point scenario (GPU-resident p2p / DropTail / IPv4 / UDP subset) ----------------
  * A topology of PointToPointNetDevices joined by PointToPointChannels, IPv4 forwarding by static
- * next-hop tables, OnOff (UDP, constant on/off times) sources and PacketSink sinks.  All arrays are
+ * next-hop tables, OnOff (UDP; constant on/off times, or random ones: nsgpu_ranvar below) sources and PacketSink sinks.  All arrays are
  * host pointers; devices and applications are listed in ns-3 creation order (Node::AddDevice /
  * Node::AddApplication), which fixes the setup-time uids (node-list.cc:124-131, node.cc:111-145). */
 enum nsgpu_app_kind { NSGPU_APP_ONOFF = 0, NSGPU_APP_SINK = 1, NSGPU_APP_ECHO_CLIENT = 2, NSGPU_APP_ECHO_SERVER = 3,
@@ -244,11 +244,49 @@ typedef struct nsgpu_udp_trace_entry {
   uint32_t time_to_send_ms;  /* TraceEntry::timeToSend: the delta to the previous non-B frame (0 for a B frame) */
   uint32_t packet_size;      /* TraceEntry::packetSize (a uint16 in the reference: above 65535 is refused) */
 } nsgpu_udp_trace_entry;
+/* ---------------- random OnOff times (onoff-application.cc:221-237, random-variable.cc) ----------------
+ * OnOffApplication draws Seconds (m_offTime.GetValue ()) when it schedules StartSending (ScheduleStartEvent: from
+ * StartApplication and StopSending) and Seconds (m_onTime.GetValue ()) when it schedules StopSending (ScheduleStopEvent:
+ * from StartSending), whether or not the event is cancelled later.  A variable owns its RngStream: `stream` is the
+ * index of the RngStream the program constructs for it (0-based, as dev_em_stream), seeded by the scenario's rng_seed
+ * / rng_run.  Every kind of RandomVariable that is not listed is NSGPU_RV_OTHER, named so that it can be refused.
+ *   NSGPU_RV_CONSTANT      p0 = the value (in app_on_var / app_off_var: the application's app_on_s / app_off_s is
+ *                          used instead, and the entry's parameters are ignored); draws nothing
+ *   NSGPU_RV_UNIFORM       p0 = min, p1 = max: min + U01 * (max - min)
+ *   NSGPU_RV_EXPONENTIAL   p0 = mean, p1 = bound (0: none): -mean * log (U01), redrawn while above the bound
+ * The Exponential's log is evaluated in double-double on the device; a draw whose timestamp could differ from the
+ * reference's under a libm log with an error below 1 ulp is recorded as ambiguous (csrc/nsgpu_ranvar.h). */
+enum { NSGPU_RV_CONSTANT = 0, NSGPU_RV_UNIFORM = 1, NSGPU_RV_EXPONENTIAL = 2,
+       NSGPU_RV_OTHER = 3 /* Pareto, Weibull, Normal, LogNormal, Gamma, Erlang, Triangular, Zipf, Zeta, Empirical,
+                             Deterministic, Sequential: named so that it can be refused */ };
+typedef struct nsgpu_ranvar {
+  uint32_t kind, stream;
+  double p0, p1;
+} nsgpu_ranvar;
+#define NSGPU_RV_AMBIGUOUS_CAP 1024u /* records of an engine's ambiguous-draw log; further ones are only counted */
+/* What nsgpu_p2p_onoff_draws returns per application (zeros for an application without a random variable). */
+typedef struct nsgpu_onoff_draw_record {
+  uint32_t on_draws, off_draws;  /* GetValue calls on the OnTime / OffTime variable (a Constant counts none) */
+  uint32_t ambiguous;            /* ambiguous attempts of both */
+  uint32_t pad_;
+} nsgpu_onoff_draw_record;
+/* One ambiguous attempt (nsgpu_p2p_onoff_ambiguous). */
+typedef struct nsgpu_ambiguous_draw {
+  uint32_t app, which;    /* which: 0 = OnTime, 1 = OffTime */
+  uint32_t ordinal;       /* the GetValue call's 0-based ordinal on that variable */
+  uint32_t k;             /* the integer behind u: u = k / 4294967088 */
+  int64_t ns, ns_other;   /* Seconds (-mean * hi), which the device took; Seconds (-mean * hi's neighbour) */
+} nsgpu_ambiguous_draw;
+
 typedef struct nsgpu_p2p_scenario_ext {
   uint32_t size;             /* sizeof (nsgpu_p2p_scenario_ext) as the caller compiled it */
   uint32_t pad_;
   const uint64_t *trace_off; /* CSR, n_apps + 1 offsets into trace_entries (empty for every other kind) */
   const nsgpu_udp_trace_entry *trace_entries;
+  /* ---- random OnOff times (appended: a caller compiled against the shorter record gives a smaller `size`) ----
+   * n_apps entries each, or NULL: every OnTime / OffTime is the Constant app_on_s / app_off_s. */
+  const nsgpu_ranvar *app_on_var;
+  const nsgpu_ranvar *app_off_var;
 } nsgpu_p2p_scenario_ext;
 /* What nsgpu_p2p_udp_trace_clients returns per application (zeros for every other kind). */
 typedef struct nsgpu_udp_trace_client_record {

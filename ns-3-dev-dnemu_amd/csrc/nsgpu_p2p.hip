@@ -101,6 +101,10 @@ struct nsgpu_p2p {
   const DevRec *dev_init = nullptr;  // device records after reset (tx state idle), and behind them the receive error
   size_t dev_bytes = 0;              // models' reset image (nsgpu_p2p_dev.h "receive error models"); its bytes
   uint32_t em_models = 0;            // enabled receive error models
+  // an engine with a random OnOff time: the reset image of app_last_start's allocation (the times, and behind them the
+  // variables' records and the empty ambiguous log), its bytes
+  const uint64_t *rv_init = nullptr;
+  size_t rv_bytes = 0;
   const nsgpu_loss_counter *loss_init = nullptr;  // ports mode: the UdpServers' loss counters after reset
   uint32_t n_apps = 0;
   // an engine with a UdpTraceClient: app_tot holds 3 * n_apps words (m_sent, m_currentEntry, the Send events run)
@@ -202,6 +206,10 @@ struct EnginePlan {
   std::vector<EmRec> em_recs;
   std::vector<double> em_tabs;
   std::vector<uint32_t> em_list;
+  std::vector<uint32_t> em_streams;  // the RngStreams the enabled Rate models name
+  // random OnOff times (nsgpu_p2p_scenario_ext.app_on_var / app_off_var): two reset records an application (OnTime,
+  // OffTime; nsgpu_p2p_dev.h "random OnOff times"), empty without a random variable
+  std::vector<RvRec> rv_recs;
   // per-flow statistics (scenario flowmon): each node's tracked-packet table size (plan_flowmon)
   bool flowmon = false;
   std::vector<uint32_t> fm_cap;
@@ -265,6 +273,7 @@ static int plan_error_models(const nsgpu_p2p_scenario *sc, EnginePlan &P) {
           return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: devices %u and %u name the same RngStream %u (one Rate error "
                            "model object shared by two devices is not modelled)", st.second, d, st.first);
       streams.emplace_back(sc->dev_em_stream[d], d);
+      P.em_streams.push_back(sc->dev_em_stream[d]);
       nsgpu_rng_stream_init(&r.g, sc->rng_seed, sc->rng_run, sc->dev_em_stream[d]);
       if (unit != NSGPU_EU_PKT) {
         uint64_t bits;
@@ -302,6 +311,77 @@ static int plan_error_models(const nsgpu_p2p_scenario *sc, EnginePlan &P) {
   return NSGPU_OK;
 }
 
+// The OnOff applications' OnTime / OffTime variables (nsgpu_p2p_scenario_ext.app_on_var / app_off_var), validated; the
+// reset records.  A caller compiled against the shorter record, a NULL array and a Constant entry all mean app_on_s /
+// app_off_s; without a random variable P.rv_recs stays empty and the engine is today's.
+static bool rv_finite(double x) { return x - x == 0.0; }
+static int plan_ranvars(const nsgpu_p2p_scenario *sc, const nsgpu_p2p_scenario_ext *ext, EnginePlan &P) {
+  const uint32_t A = sc->n_apps;
+  if (!ext || ext->size < offsetof(nsgpu_p2p_scenario_ext, app_off_var) + sizeof(void *)) return NSGPU_OK;
+  const nsgpu_ranvar *var[2] = {ext->app_on_var, ext->app_off_var};
+  if (!var[0] && !var[1]) return NSGPU_OK;
+  static const char *const name[2] = {"OnTime", "OffTime"};
+  std::vector<RvRec> recs(2 * (size_t)A);
+  std::vector<std::pair<uint32_t, uint32_t>> streams;  // (stream, 2 a + which)
+  bool any = false;
+  for (uint32_t a = 0; a < A; a++)
+    for (int w = 0; w < 2; w++) {
+      RvRec r{};
+      r.v.kind = NSGPU_RV_CONSTANT;
+      const double *cs = w == 0 ? sc->app_on_s : sc->app_off_s;
+      r.v.p0 = cs ? cs[a] : 0.0;
+      const nsgpu_ranvar *v = var[w] ? var[w] + a : nullptr;
+      if (v && v->kind != NSGPU_RV_CONSTANT) {
+        if (v->kind == NSGPU_RV_OTHER)
+          return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: app %u: %s: only Constant, Uniform and Exponential variables "
+                           "are modelled (pow, sqrt and exp would each need what log got)", a, name[w]);
+        if (v->kind != NSGPU_RV_UNIFORM && v->kind != NSGPU_RV_EXPONENTIAL)
+          return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: app %u: %s: unknown random variable kind %u", a, name[w], v->kind);
+        if (sc->app_kind[a] != NSGPU_APP_ONOFF)
+          return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: app %u: %s: a random variable on an application that is not "
+                           "an OnOff", a, name[w]);
+        if (v->kind == NSGPU_RV_UNIFORM) {
+          if (!rv_finite(v->p0) || !rv_finite(v->p1))
+            return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: app %u: %s: Uniform with a non-finite parameter", a, name[w]);
+          if (v->p0 < 0) return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: app %u: %s: Uniform with min < 0", a, name[w]);
+          if (v->p1 < v->p0) return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: app %u: %s: Uniform with max < min", a, name[w]);
+          if (v->p1 >= 9.2e9)  // (2^63 ns)
+            return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: app %u: %s: Uniform whose max overflows the timestamp", a, name[w]);
+        } else {
+          if (!rv_finite(v->p0))
+            return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: app %u: %s: Exponential with a non-finite mean", a, name[w]);
+          if (!(v->p0 > 0)) return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: app %u: %s: Exponential with mean <= 0", a, name[w]);
+          // -log (U01) is at most 32 ln 2 = 22.2
+          if (23.0 * v->p0 >= 9.2e9)
+            return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: app %u: %s: Exponential whose mean overflows the timestamp "
+                             "(23 * mean seconds)", a, name[w]);
+          if (!(v->p1 >= 0))  // (a NaN too)
+            return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: app %u: %s: Exponential with bound < 0", a, name[w]);
+          if (v->p1 > 0 && v->p1 < v->p0 / 8)
+            return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: app %u: %s: Exponential with a bound below mean / 8 (the "
+                             "device redraws at most %u times)", a, name[w], NSGPU_RV_MAX_ATTEMPTS);
+        }
+        for (const auto &st : streams)
+          if (st.first == v->stream)
+            return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: app %u %s and app %u %s name the same RngStream %u (a "
+                             "variable owns its stream)", st.second / 2, name[st.second & 1], a, name[w], v->stream);
+        for (const uint32_t es : P.em_streams)
+          if (es == v->stream)
+            return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: app %u: %s names RngStream %u, which a Rate error model "
+                             "names too", a, name[w], v->stream);
+        streams.emplace_back(v->stream, 2 * a + (uint32_t)w);
+        r.v = *v;
+        if (!nsgpu_rng_stream_init(&r.g, sc->rng_seed, sc->rng_run, v->stream))
+          return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: rng_seed %u is not a seed RngStream::CheckSeed accepts (below "
+                           "4294944443)", sc->rng_seed);
+        any = true;
+      }
+      recs[2 * (size_t)a + w] = r;
+    }
+  if (any) P.rv_recs.swap(recs);
+  return NSGPU_OK;
+}
+
 // One UdpTraceClient's entries, validated, and the walk of its cycle (udp-trace-client.cc:311-335) from entry 0 until
 // m_currentEntry repeats at a Send's start: the smallest and largest UDP payload it puts on a wire, the largest burst,
 // the shortest delay between two Sends, and per cycle the datagrams and the time.
@@ -315,7 +395,7 @@ static int plan_trace_client(const nsgpu_p2p_scenario *sc, const nsgpu_p2p_scena
                              TraceWalk &W) {
   if (!ports)
     return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: app %u: UdpTraceClient needs UDP ports (app_port)", a);
-  if (!ext || ext->size < sizeof(nsgpu_p2p_scenario_ext) || !ext->trace_off)
+  if (!ext || ext->size < offsetof(nsgpu_p2p_scenario_ext, trace_entries) + sizeof(void *) || !ext->trace_off)
     return set_error(NSGPU_EINVAL, "nsgpu_p2p_create: UdpTraceClient %u: no trace entries (an nsgpu_p2p_scenario_ext "
                      "through the _ex entry points carries them)", a);
   const uint64_t lo = ext->trace_off[a], hi = ext->trace_off[a + 1];
@@ -465,6 +545,7 @@ static int plan_engine(const nsgpu_p2p_scenario *sc, const nsgpu_p2p_scenario_ex
     qcap = std::max(qcap, sc->dev_qmax[d]);
   }
   if (int rce = plan_error_models(sc, P)) return rce;
+  if (int rcv = plan_ranvars(sc, ext, P)) return rcv;
   if (owner) {
     if (nranks < 1 || nranks > MAXR || rank < 0 || rank >= nranks ||
         (uint64_t)nranks * CAPX_MAX + TB + 2 * WCAP >= (uint64_t)GRID_POOL_DIST * TB)  // (k2_pa: slot, remote, chunk blocks)
@@ -1004,7 +1085,18 @@ static int create_engine(const nsgpu_p2p_scenario *sc, const nsgpu_p2p_scenario_
   } else {
     TRY(dalloc(h, &M.node_ipid, N));
   }
-  TRY(dalloc(h, &M.app_last_start, A));
+  if (!P.rv_recs.empty()) {
+    // behind the last-start times: the RvHdr, the variables' records, the ambiguous log (nsgpu_p2p_dev.h "random OnOff
+    // times"); kept as the reset image too
+    h->rv_bytes = rv_bytes(A);
+    std::vector<uint64_t> img(h->rv_bytes / 8, 0);
+    memcpy(rv_recs(img.data(), A), P.rv_recs.data(), P.rv_recs.size() * sizeof(RvRec));
+    TRY(dupload(h, &h->rv_init, img.data(), img.size()));
+    TRY(dalloc(h, &M.app_last_start, img.size()));
+    M.ranvar = 1;
+  } else {
+    TRY(dalloc(h, &M.app_last_start, A));
+  }
   if (P.ports) {  // (the UdpServers' loss counters lie behind the counters: loss_counters)
     static_assert(sizeof(nsgpu_loss_counter) == 2 * sizeof(nsgpu_app_counters), "loss_counters");
     TRY(dalloc(h, &M.appc, 3 * (size_t)A));
@@ -1289,7 +1381,8 @@ extern "C" int nsgpu_p2p_reset(nsgpu_p2p *h, void *stream) {
     NSGPU_HIP(hipMemsetAsync(M.node_ipid, 0, M.n_nodes * sizeof(uint32_t), s));
   }
   if (M.trace) NSGPU_HIP(hipMemsetAsync(M.trace_n, 0, sizeof(unsigned long long), s));
-  NSGPU_HIP(hipMemsetAsync(M.app_last_start, 0, A * sizeof(uint64_t), s));
+  if (h->rv_init) NSGPU_HIP(hipMemcpyAsync(M.app_last_start, h->rv_init, h->rv_bytes, hipMemcpyDeviceToDevice, s));
+  else NSGPU_HIP(hipMemsetAsync(M.app_last_start, 0, A * sizeof(uint64_t), s));
   NSGPU_HIP(hipMemsetAsync(M.appc, 0, A * sizeof(nsgpu_app_counters), s));
   if (h->loss_init)
     NSGPU_HIP(hipMemcpyAsync(loss_counters(M.appc, A), h->loss_init, A * sizeof(nsgpu_loss_counter),
@@ -1346,7 +1439,7 @@ bool launch_kernel(nsgpu_p2p *h, int k, hipStream_t s, bool df, hipEvent_t ev0 =
       // (a scenario with ports, frag, a receive error model or per-flow statistics: the extended handlers — the
       // endpoint lookup, UdpClient, UdpServer, IPv4 fragmentation and reassembly, the error models, the flow monitor —
       // nsgpu_p2p_ports.hip)
-      if (h->loss_init || h->M.frag || h->M.errm || h->M.flowmon) launch_handle_ports(h->M, wide, false, df, K2_GRID, s, ev0, ev1);
+      if (h->loss_init || h->M.frag || h->M.errm || h->M.flowmon || h->M.ranvar) launch_handle_ports(h->M, wide, false, df, K2_GRID, s, ev0, ev1);
       else if (df) NSGPU_KLAUNCH((k2_handle<true, false, true>), dim3(K2_GRID), dim3(HB), s, ev0, ev1, h->M);
       else if (wide) NSGPU_KLAUNCH(k2_handle<true>, dim3(K2_GRID), dim3(HB), s, ev0, ev1, h->M);
       else NSGPU_KLAUNCH(k2_handle<false>, dim3(K2_GRID), dim3(HB), s, ev0, ev1, h->M);
@@ -1644,7 +1737,7 @@ static int launch_windows_dist(nsgpu_p2p *h, hipStream_t s, int nwin = NWIN) {
   for (int w = 0; w < nwin && !rc; w++) {
     dist_pa(M, s);
     rc = x_allgather(h, M.x0_send, M.x0_recv, X0B, s);
-    dist_handle(M, s, h->loss_init != nullptr || M.frag != 0 || M.errm != 0);
+    dist_handle(M, s, h->loss_init != nullptr || M.frag != 0 || M.errm != 0 || M.ranvar != 0);
     dist_rank(M, s);
     if (!rc) rc = x_allgather(h, M.x1_send, M.x1_recv, X1B, s);
     dist_rank_fin(M, s);
@@ -1728,6 +1821,9 @@ static int build_graph(nsgpu_p2p *h, bool df = false, bool tail = false) {
 
 // A run that set the engine's error word: capacity exceeded (the simulation is truncated).
 static int engine_error(uint32_t err) {
+  if (err & ERR_RANVAR_ATTEMPTS)
+    return set_error(NSGPU_ERANGE, "nsgpu_p2p: a bounded ExponentialVariable was rejected %u times in one GetValue "
+                     "(code %u)", NSGPU_RV_MAX_ATTEMPTS, err);
   if (err & ERR_TRACE_SEQ)
     return set_error(NSGPU_ERANGE, "nsgpu_p2p: a UdpTraceClient's m_sent would pass 2^24 (code %u: the packet descriptor "
                      "carries the SeqTsHeader's sequence number in 24 bits; it is never wrapped silently)", err);
@@ -1920,6 +2016,9 @@ extern "C" int nsgpu_p2p_setup_uid(nsgpu_p2p *h, uint32_t *uid) {
   if (h->has_trace_client)
     return set_error(NSGPU_ESTATE, "nsgpu_p2p_setup_uid: a scenario with a UdpTraceClient cannot be attached to a "
                      "host-closure runtime");
+  if (h->M.ranvar)
+    return set_error(NSGPU_ESTATE, "nsgpu_p2p_setup_uid: a scenario with a random OnOff time cannot be attached to a "
+                     "host-closure runtime");
   *uid = h->C0.uid;
   return NSGPU_OK;
 }
@@ -1987,6 +2086,8 @@ extern "C" int nsgpu_p2p_inject_send(nsgpu_p2p *h, uint32_t app, uint64_t now, u
     return set_error(NSGPU_ESTATE, "nsgpu_p2p_inject_send: not available in a scenario with IPv4 fragmentation (frag)");
   if (h->M.errm)
     return set_error(NSGPU_ESTATE, "nsgpu_p2p_inject_send: not available in a scenario with a receive error model");
+  if (h->M.ranvar)
+    return set_error(NSGPU_ESTATE, "nsgpu_p2p_inject_send: not available in a scenario with a random OnOff time");
   // (... nor on a monitored engine: the injected datagram would pass no ReportFirstTx)
   if (h->M.flowmon)
     return set_error(NSGPU_ESTATE, "nsgpu_p2p_inject_send: not available in a scenario with per-flow statistics (flowmon)");
@@ -2433,6 +2534,45 @@ extern "C" int nsgpu_p2p_flow_stats(nsgpu_p2p *h, int64_t max_delay_ns, nsgpu_fl
   return NSGPU_OK;
 }
 
+// The random OnOff times' draw counts per application (zeros without a random variable).  A partitioned engine's
+// variables advance on the rank that owns the application's node; another rank's stay at zero here.
+extern "C" int nsgpu_p2p_onoff_draws(nsgpu_p2p *h, nsgpu_onoff_draw_record *out, uint32_t n_apps, void *stream) {
+  if (!h || (n_apps && !out)) return set_error(NSGPU_EINVAL, "nsgpu_p2p_onoff_draws: null");
+  if (n_apps != h->M.n_apps) return set_error(NSGPU_EINVAL, "nsgpu_p2p_onoff_draws: the engine has %u applications", h->M.n_apps);
+  hipStream_t s = (hipStream_t)stream;
+  const P2PDev &M = h->M;
+  memset(out, 0, (size_t)n_apps * sizeof(*out));
+  if (!M.ranvar) return NSGPU_OK;
+  std::vector<RvRec> rr(2 * (size_t)n_apps);
+  NSGPU_HIP(hipMemcpyAsync(rr.data(), rv_recs(M.app_last_start, n_apps), rr.size() * sizeof(RvRec), hipMemcpyDeviceToHost, s));
+  NSGPU_HIP(hipStreamSynchronize(s));
+  for (uint32_t a = 0; a < n_apps; a++)
+    out[a] = nsgpu_onoff_draw_record{rr[2 * a].draws, rr[2 * a + 1].draws, rr[2 * a].ambiguous + rr[2 * a + 1].ambiguous, 0};
+  return NSGPU_OK;
+}
+// The log of ambiguous attempts: *n records (at most cap are written to out; out may be NULL with cap 0 to ask for
+// the count) and the attempts beyond the log's NSGPU_RV_AMBIGUOUS_CAP records.
+extern "C" int nsgpu_p2p_onoff_ambiguous(nsgpu_p2p *h, nsgpu_ambiguous_draw *out, uint64_t cap, uint64_t *n,
+                                         uint64_t *overflow, void *stream) {
+  if (!h || !n || !overflow || (cap && !out)) return set_error(NSGPU_EINVAL, "nsgpu_p2p_onoff_ambiguous: null");
+  *n = *overflow = 0;
+  const P2PDev &M = h->M;
+  if (!M.ranvar) return NSGPU_OK;
+  hipStream_t s = (hipStream_t)stream;
+  RvHdr H;
+  NSGPU_HIP(hipMemcpyAsync(&H, rv_hdr(M.app_last_start, M.n_apps), sizeof(H), hipMemcpyDeviceToHost, s));
+  NSGPU_HIP(hipStreamSynchronize(s));
+  const uint32_t cnt = std::min(H.log_n, NSGPU_RV_AMBIGUOUS_CAP);
+  *n = cnt;
+  *overflow = H.log_over;
+  const uint64_t m = std::min<uint64_t>(cnt, cap);
+  if (m) {
+    NSGPU_HIP(hipMemcpyAsync(out, rv_log(M.app_last_start, M.n_apps), m * sizeof(*out), hipMemcpyDeviceToHost, s));
+    NSGPU_HIP(hipStreamSynchronize(s));
+  }
+  return NSGPU_OK;
+}
+
 extern "C" int nsgpu_p2p_results(nsgpu_p2p *h, nsgpu_p2p_stats *stats, nsgpu_dev_counters *devc,
                                  nsgpu_app_counters *appc, uint64_t *log_ts, uint32_t *log_uid, uint32_t *log_ctx,
                                  uint64_t log_n, uint32_t *error, void *stream) {
@@ -2491,7 +2631,7 @@ static void launch_windows_group(nsgpu_p2p_group *g, hipStream_t s, int nwin = N
   for (int w = 0; w < nwin; w++) {
     for (auto *h : g->m) dist_pa(h->M, s);
     hipLaunchKernelGGL(k_copies, dim3(n * n), dim3(256), 0, s, (const CopyDesc *)g->d_x[0]);
-    for (auto *h : g->m) dist_handle(h->M, s, h->loss_init != nullptr || h->M.frag != 0 || h->M.errm != 0);
+    for (auto *h : g->m) dist_handle(h->M, s, h->loss_init != nullptr || h->M.frag != 0 || h->M.errm != 0 || h->M.ranvar != 0);
     for (auto *h : g->m) dist_rank(h->M, s);
     hipLaunchKernelGGL(k_copies, dim3(n * n), dim3(256), 0, s, (const CopyDesc *)g->d_x[1]);
     for (auto *h : g->m) dist_rank_fin(h->M, s);

@@ -25,6 +25,7 @@
 #include "nsgpu_internal.h"
 #include "nsgpu_loss_counter.h"
 #include "nsgpu_p2p_span.h"
+#include "nsgpu_ranvar.h"
 #include "nsgpu_rng_stream.h"
 #include "nsgpu_wave.h"
 
@@ -327,7 +328,8 @@ struct P2PDev {
   uint8_t *x1_send, *x1_recv;   // X1: X1B bytes per rank (header, the rank's records in dispatch order: SEnt)
   uint8_t *x1_own;              // this rank's window lists, not exchanged: X1Ent x WCAP, then X1Loc x XLCAP
   uint8_t *x2_send, *x2_recv;   // X2: x2b bytes per peer
-  uint32_t capx, pad_x;         // X2 records per peer per window (the run's largest cut between two ranks)
+  uint32_t capx, ranvar;        // X2 records per peer per window (the run's largest cut between two ranks); ranvar:
+                                // some OnOff has a random OnTime / OffTime (the extended handlers; was padding)
   uint64_t x2b;                 // X2 bytes per peer
   uint32_t *gacc;               // k_gtile's accumulators: 2 x NACC packed 64-bit words
   // run control / outputs
@@ -1105,17 +1107,96 @@ __device__ __forceinline__ void cancel_events(const P2PDev &M, uint32_t a, uint6
   M.app_flags[a] = f & ~(4u | 8u);  // Cancel (m_sendEvent); Cancel (m_startStopEvent)
 }
 
+// ---------------- random OnOff times (nsgpu_p2p_scenario_ext.app_on_var / app_off_var) ----------------
+// OnOffApplication::ScheduleStartEvent / ScheduleStopEvent (onoff-application.cc:221-237) take Seconds
+// (m_offTime.GetValue ()) / Seconds (m_onTime.GetValue ()): the draw happens when the event is scheduled, whether or not
+// it is cancelled later; ScheduleNextTx's StopApplication at MaxBytes draws nothing.  A variable (random-variable.cc:
+// 251-258 Uniform, :574-589 Exponential; nsgpu_ranvar.h) owns its RngStream, and the helper's attribute copy gives every
+// application its own two.  Their state — stream, parameters, draw and ambiguous counts — is per application and
+// advances in the application's own event order: it belongs to the serial pass of the application's node, like
+// app_ss_gen (no atomics; on a partitioned engine the owner of the node).  The records lie behind app_last_start in its
+// allocation (P2PDev takes no further pointer, see hub_slot): the RvHdr, two RvRecs an application (OnTime, OffTime),
+// then the log of ambiguous attempts, whose slots are claimed with one atomic (appends are rare).  All of it is part of
+// the reset image.
+constexpr uint32_t ERR_RANVAR_ATTEMPTS = 65536u;  // the engine's error bit: a bounded Exponential was rejected 1,024 times
+struct RvRec {
+  nsgpu_rng_stream g;
+  uint32_t draws, ambiguous;  // GetValue calls; ambiguous attempts
+  nsgpu_ranvar v;
+  uint64_t pad;
+};
+static_assert(sizeof(RvRec) == 64, "RvRec");
+struct RvHdr {
+  uint32_t log_n, log_over;  // log records written (at most NSGPU_RV_AMBIGUOUS_CAP); attempts beyond them
+  uint32_t pad[2];
+};
+__host__ __device__ __forceinline__ RvHdr *rv_hdr(uint64_t *app_last_start, uint32_t n_apps) {
+  return reinterpret_cast<RvHdr *>(app_last_start + n_apps);
+}
+__host__ __device__ __forceinline__ RvRec *rv_recs(uint64_t *app_last_start, uint32_t n_apps) {
+  return reinterpret_cast<RvRec *>(rv_hdr(app_last_start, n_apps) + 1);
+}
+__host__ __device__ __forceinline__ nsgpu_ambiguous_draw *rv_log(uint64_t *app_last_start, uint32_t n_apps) {
+  return reinterpret_cast<nsgpu_ambiguous_draw *>(rv_recs(app_last_start, n_apps) + 2 * (size_t)n_apps);
+}
+__host__ __device__ __forceinline__ size_t rv_bytes(uint32_t n_apps) {  // the whole allocation
+  return (size_t)n_apps * sizeof(uint64_t) + sizeof(RvHdr) + 2 * (size_t)n_apps * sizeof(RvRec) +
+         (size_t)NSGPU_RV_AMBIGUOUS_CAP * sizeof(nsgpu_ambiguous_draw);
+}
+static_assert(sizeof(nsgpu_ambiguous_draw) == 32 && sizeof(RvHdr) == 16, "the log's records stay 8-byte aligned");
+// Seconds (GetValue ()) of application a's OnTime (which = 0) or OffTime (1) variable.  Out of line: the handlers of a
+// scenario without a random variable never reach it.
+__device__ __noinline__ int64_t rv_draw(const P2PDev *G, uint32_t a, uint32_t which) {
+  const P2PDev &M = mdev_ref(G);
+  RvRec *r = rv_recs(M.app_last_start, M.n_apps) + (2 * (size_t)a + which);
+  if (r->v.kind == NSGPU_RV_CONSTANT) return seconds_to_ts(r->v.p0);
+  const uint32_t ordinal = r->draws++;
+  RvHdr *H = rv_hdr(M.app_last_start, M.n_apps);
+  nsgpu_ambiguous_draw *L = rv_log(M.app_last_start, M.n_apps);
+  double sec;
+  const bool ok = nsgpu_ranvar_value(r->v, &r->g, &sec, [&](uint32_t k, int64_t ns, int64_t ns2) {
+    r->ambiguous++;
+    const uint32_t i = atomicAdd(&H->log_n, 1u);
+    if (i < NSGPU_RV_AMBIGUOUS_CAP) {
+      L[i] = nsgpu_ambiguous_draw{a, which, ordinal, k, ns, ns2};
+    } else {  // (log_n is clamped when it is read)
+      atomicAdd(&H->log_over, 1u);
+    }
+  });
+  if (!ok) atomicOr(M.error, ERR_RANVAR_ATTEMPTS);
+  return seconds_to_ts(sec);
+}
+// EXT: the extended handlers (k2_handle<.., PORTS = true>); the default instantiations read the constants as before.
+// RV_HANDLERS: and of the extended handlers only the copy compiled in nsgpu_p2p_ranvar.hip (NSGPU_P2P_RANVAR) calls
+// rv_draw.  The draw is register-heavy (a double-double logarithm, three Seconds () conversions in 128-bit integers:
+// 70 VGPRs, 97 SGPRs), and a callee's registers shape its callers' allocation: compiled into nsgpu_p2p_ports.hip's
+// handlers it cost every one of them 24 B of scratch a lane, SGPRs spilled to VGPR lanes in the holders' loop and
+// 2 to 4 % of an existing ports workload's speed (profiles/r17/kernel_resources.md).  In a code object of its own only
+// the scenarios with a random variable pay.
+#ifdef NSGPU_P2P_RANVAR
+constexpr bool RV_HANDLERS = true;
+#else
+constexpr bool RV_HANDLERS = false;
+#endif
+template <bool EXT = false>
 __device__ __forceinline__ void schedule_start_event(const P2PDev &M, Emit &E, uint32_t a) {
   const uint32_t g = (M.app_ss_gen[a] + 1) & 0xffffffu;
   M.app_ss_gen[a] = g;
   M.app_flags[a] |= 8u;
-  E.child(seconds_to_ts(M.app_off_s[a]), E.ctx, K_START_SENDING | (g << 8), a, Pkt{0, 0, 0, 0});
+  int64_t d;
+  if (EXT && RV_HANDLERS && M.ranvar) d = rv_draw(mdev_of(M.C), a, 1);  // Seconds (m_offTime.GetValue ())
+  else d = seconds_to_ts(M.app_off_s[a]);
+  E.child(d, E.ctx, K_START_SENDING | (g << 8), a, Pkt{0, 0, 0, 0});
 }
+template <bool EXT = false>
 __device__ __forceinline__ void schedule_stop_event(const P2PDev &M, Emit &E, uint32_t a) {
   const uint32_t g = (M.app_ss_gen[a] + 1) & 0xffffffu;
   M.app_ss_gen[a] = g;
   M.app_flags[a] |= 8u;
-  E.child(seconds_to_ts(M.app_on_s[a]), E.ctx, K_STOP_SENDING | (g << 8), a, Pkt{0, 0, 0, 0});
+  int64_t d;
+  if (EXT && RV_HANDLERS && M.ranvar) d = rv_draw(mdev_of(M.C), a, 0);  // Seconds (m_onTime.GetValue ())
+  else d = seconds_to_ts(M.app_on_s[a]);
+  E.child(d, E.ctx, K_STOP_SENDING | (g << 8), a, Pkt{0, 0, 0, 0});
 }
 template <bool PORTS = false>
 __device__ __forceinline__ void stop_application(const P2PDev &M, uint32_t a, uint64_t now) {
@@ -1571,7 +1652,7 @@ __device__ __forceinline__ NodeOut node_part_full(const P2PDev &M, Emit &E, uint
           E.child(0, E.ctx, K_SEND | (g << 8), a, Pkt{0, 0, 0, 0});
         } else {
           cancel_events(M, a, E.now);
-          schedule_start_event(M, E, a);
+          schedule_start_event<PORTS>(M, E, a);
         }
         break;
       case K_APP_STOP:
@@ -1588,7 +1669,7 @@ __device__ __forceinline__ NodeOut node_part_full(const P2PDev &M, Emit &E, uint
         post = schedule_next_tx(M, a, E.now);
         if (post.valid) E.child(post.delay, E.ctx, post.kind, post.a, Pkt{0, 0, 0, 0});
         post.valid = false;
-        schedule_stop_event(M, E, a);
+        schedule_stop_event<PORTS>(M, E, a);
         break;
       }
       case K_STOP_SENDING: {  // onoff-application.cc:208-216
@@ -1599,7 +1680,7 @@ __device__ __forceinline__ NodeOut node_part_full(const P2PDev &M, Emit &E, uint
         }
         M.app_flags[a] = f & ~8u;
         cancel_events(M, a, E.now);
-        schedule_start_event(M, E, a);
+        schedule_start_event<PORTS>(M, E, a);
         break;
       }
       case K_FWD_UP:  // DoForwardUp -> UdpSocketImpl::ForwardUp -> PacketSink::HandleRead (a = sink app)

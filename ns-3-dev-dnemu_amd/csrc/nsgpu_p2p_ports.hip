@@ -1,7 +1,8 @@
 // nsgpu_p2p_ports.hip — the p2p subset's extended handler kernels, for scenarios with UDP ports, IPv4 fragmentation
 // or receive error models (k2_handle<.., PORTS = true>: the per-flow endpoint lookup, UdpClient, UdpServer; fragments
 // sent by the device step, reassembly and its timeout; ReceiveListErrorModel and RateErrorModel; nsgpu_p2p_dev.h "UDP
-// ports", "IPv4 fragmentation", "receive error models"), and PacketLossCounter and RngStream on their own.
+// ports", "IPv4 fragmentation", "receive error models"), and PacketLossCounter, RngStream and the random variables
+// (nsgpu_ranvar.h) on their own.  A scenario with a random OnOff time runs nsgpu_p2p_ranvar.hip's copy of them.
 // A translation unit of its own, and so a code object of its own: nsgpu_p2p.hip's holds exactly the kernels it held
 // before ports existed, so the engines of scenarios without ports run the same code at the same layout.  The window
 // header is compiled here for k2_handle alone (NSGPU_P2P_HANDLERS_ONLY): its other kernels stay nsgpu_p2p.hip's.
@@ -10,8 +11,12 @@
 namespace nsgpu {
 #include "nsgpu_p2p_win.h"
 
+// (nsgpu_p2p_ranvar.hip: the same handlers with the random OnOff times' draw compiled in)
+void launch_handle_ranvar(const P2PDev &M, bool wide, bool xl, bool df, int grid, hipStream_t s, hipEvent_t ev0,
+                          hipEvent_t ev1);
 void launch_handle_ports(const P2PDev &M, bool wide, bool xl, bool df, int grid, hipStream_t s, hipEvent_t ev0,
                          hipEvent_t ev1) {
+  if (M.ranvar) return launch_handle_ranvar(M, wide, xl, df, grid, s, ev0, ev1);
   const dim3 g(grid), b(HB);
   if (df) hipExtLaunchKernelGGL((k2_handle<true, false, true, true>), g, b, 0, s, ev0, ev1, 0, M);
   else if (wide && xl) hipExtLaunchKernelGGL((k2_handle<true, true, false, true>), g, b, 0, s, ev0, ev1, 0, M);
@@ -123,5 +128,94 @@ extern "C" int nsgpu_rng_stream_run(uint32_t seed, uint32_t run, uint32_t stream
   if (e == hipSuccess) e = hipStreamSynchronize(s);
   (void)hipFree(d);
   if (e != hipSuccess) return set_error(NSGPU_EHIP, "nsgpu_rng_stream_run: %s", hipGetErrorString(e));
+  return NSGPU_OK;
+}
+
+// RandomVariable::GetValue over n draws of variable v, whose stream is the v->stream-th of a program with RngSeed
+// `seed` and RngRun `run`: seconds[i] the value, ns[i] = Seconds (value), ns_other[i] the other candidate's timestamp
+// (the last ambiguous attempt's; ns[i] for an unambiguous draw), ambiguous[i] whether any attempt of the draw was
+// ambiguous (nsgpu_ranvar.h).  on_device = 0 runs nsgpu_ranvar_value on the host, 1 in a one-thread kernel (the
+// function the handlers call).  Any output may be NULL.
+struct RvRunOut {
+  double *seconds;
+  int64_t *ns, *ns_other;
+  uint8_t *ambiguous;
+};
+NSGPU_HD static inline bool rv_run(nsgpu_ranvar v, nsgpu_rng_stream g, uint64_t n, const RvRunOut &o) {
+  bool ok = true;
+  for (uint64_t i = 0; i < n; i++) {
+    double sec;
+    bool amb = false;
+    int64_t other = 0;
+    ok = nsgpu_ranvar_value(v, &g, &sec, [&](uint32_t, int64_t, int64_t ns2) {
+           amb = true;
+           other = ns2;
+         }) && ok;
+    const int64_t ts = seconds_to_ts(sec);
+    if (o.seconds) o.seconds[i] = sec;
+    if (o.ns) o.ns[i] = ts;
+    if (o.ns_other) o.ns_other[i] = amb ? other : ts;
+    if (o.ambiguous) o.ambiguous[i] = amb ? 1 : 0;
+  }
+  return ok;
+}
+__global__ void k_ranvar(nsgpu_ranvar v, nsgpu_rng_stream g, uint64_t n, RvRunOut o, uint32_t *bad) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  *bad = rv_run(v, g, n, o) ? 0u : 1u;
+}
+extern "C" int nsgpu_ranvar_run(const nsgpu_ranvar *v, uint32_t seed, uint32_t run, uint64_t n, double *seconds,
+                                int64_t *ns, int64_t *ns_other, uint8_t *ambiguous, int on_device, void *stream) {
+  if (!v) return set_error(NSGPU_EINVAL, "nsgpu_ranvar_run: null");
+  if (v->kind > NSGPU_RV_EXPONENTIAL)
+    return set_error(NSGPU_EINVAL, "nsgpu_ranvar_run: only Constant, Uniform and Exponential variables are modelled");
+  nsgpu_rng_stream g;
+  if (!nsgpu_rng_stream_init(&g, seed, run, v->stream))
+    return set_error(NSGPU_EINVAL, "nsgpu_ranvar_run: seed %u is not a seed RngStream::CheckSeed accepts (below "
+                     "4294944443)", seed);
+  const char *const erange = "nsgpu_ranvar_run: a bounded ExponentialVariable was rejected %u times in one GetValue";
+  if (!on_device) {
+    if (!rv_run(*v, g, n, RvRunOut{seconds, ns, ns_other, ambiguous})) return set_error(NSGPU_ERANGE, erange, NSGPU_RV_MAX_ATTEMPTS);
+    return NSGPU_OK;
+  }
+  if (!n) return NSGPU_OK;
+  hipStream_t s = (hipStream_t)stream;
+  uint8_t *d = nullptr;  // [n] seconds, [n] ns, [n] ns_other, the flag word, [n] ambiguous
+  NSGPU_HIP(hipMalloc((void **)&d, 25 * n + 8));
+  const RvRunOut o{reinterpret_cast<double *>(d), reinterpret_cast<int64_t *>(d + 8 * n),
+                   reinterpret_cast<int64_t *>(d + 16 * n), d + 24 * n + 8};
+  uint32_t *dbad = reinterpret_cast<uint32_t *>(d + 24 * n);
+  uint32_t bad = 0;
+  hipLaunchKernelGGL(k_ranvar, dim3(1), dim3(64), 0, s, *v, g, n, o, dbad);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess && seconds) e = hipMemcpyAsync(seconds, o.seconds, 8 * n, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess && ns) e = hipMemcpyAsync(ns, o.ns, 8 * n, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess && ns_other) e = hipMemcpyAsync(ns_other, o.ns_other, 8 * n, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess && ambiguous) e = hipMemcpyAsync(ambiguous, o.ambiguous, n, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(&bad, dbad, 4, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  (void)hipFree(d);
+  if (e != hipSuccess) return set_error(NSGPU_EHIP, "nsgpu_ranvar_run: %s", hipGetErrorString(e));
+  if (bad) return set_error(NSGPU_ERANGE, erange, NSGPU_RV_MAX_ATTEMPTS);
+  return NSGPU_OK;
+}
+// log (u) by nsgpu_rv_log on the host, for the accuracy tests: hi[i] + lo[i] for u[i] in [2^-33, 1).
+extern "C" int nsgpu_ranvar_log(const double *u, uint64_t n, double *hi, double *lo) {
+  if (n && (!u || !hi || !lo)) return set_error(NSGPU_EINVAL, "nsgpu_ranvar_log: null");
+  for (uint64_t i = 0; i < n; i++) {
+    if (!(u[i] >= 1.0 / 8589934592.0 && u[i] < 1.0)) return set_error(NSGPU_EINVAL, "nsgpu_ranvar_log: u[%llu] outside [2^-33, 1)", (unsigned long long)i);
+    const nsgpu_dd l = nsgpu_rv_log(u[i]);
+    hi[i] = l.hi;
+    lo[i] = l.lo;
+  }
+  return NSGPU_OK;
+}
+// One ExponentialVariable attempt from k by nsgpu_rv_exponential on the host, for the constructed-ambiguity tests:
+// r, Seconds (r), Seconds (r'), accepted, ambiguous.
+extern "C" int nsgpu_ranvar_exponential(double mean, double bound, uint32_t k, double *r, int64_t *ns, int64_t *ns_other,
+                                        int *accept, int *ambiguous) {
+  if (!r || !ns || !ns_other || !accept || !ambiguous) return set_error(NSGPU_EINVAL, "nsgpu_ranvar_exponential: null");
+  if (k == 0 || k > NSGPU_RNG_M1) return set_error(NSGPU_EINVAL, "nsgpu_ranvar_exponential: k outside [1, 4294967087]");
+  const nsgpu_rv_attempt t = nsgpu_rv_exponential(mean, bound, k);
+  *r = t.r, *ns = t.ns, *ns_other = t.ns2, *accept = t.accept, *ambiguous = t.ambiguous;
   return NSGPU_OK;
 }

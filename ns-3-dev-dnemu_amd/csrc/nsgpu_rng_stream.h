@@ -19,7 +19,8 @@
 
 // U01 (:221-244).  `p1 / m1` truncated and the `if (p1 < 0.0) p1 += m1` after it are the mathematical residue in
 // [0, m): a quotient that rounds across an integer leaves a remainder the correction brings back.
-NSGPU_HD static inline double nsgpu_rng_u01(nsgpu_rng_stream *g) {
+// nsgpu_rng_next: the step, returning the integer k in [1, m1] behind the value; U01 = k * norm.
+NSGPU_HD static inline uint32_t nsgpu_rng_next(nsgpu_rng_stream *g) {
   long long p1 = NSGPU_RNG_A12 * (long long)g->s[1] - NSGPU_RNG_A13N * (long long)g->s[0];
   p1 %= (long long)NSGPU_RNG_M1;
   if (p1 < 0) p1 += (long long)NSGPU_RNG_M1;
@@ -32,9 +33,12 @@ NSGPU_HD static inline double nsgpu_rng_u01(nsgpu_rng_stream *g) {
   g->s[3] = g->s[4];
   g->s[4] = g->s[5];
   g->s[5] = (uint32_t)p2;
+  return (uint32_t)(p1 > p2 ? p1 - p2 : p1 - p2 + (long long)NSGPU_RNG_M1);
+}
+NSGPU_HD static inline double nsgpu_rng_u01(nsgpu_rng_stream *g) {
   // norm = 1.0 / (m1 + 1.0); (p1 > p2) ? (p1 - p2) * norm : (p1 - p2 + m1) * norm — the operands are exact
   const double norm = 1.0 / 4294967088.0;
-  return (double)(p1 > p2 ? p1 - p2 : p1 - p2 + (long long)NSGPU_RNG_M1) * norm;
+  return (double)nsgpu_rng_next(g) * norm;
 }
 
 // ---- host: the k-th stream's initial state ----

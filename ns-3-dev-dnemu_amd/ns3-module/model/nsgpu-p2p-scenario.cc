@@ -62,7 +62,8 @@ NsgpuP2pScenario::NsgpuP2pScenario ()
     m_firstLink (true),
     m_engine (0),
     m_codec (0),
-    m_hasTrace (false)
+    m_hasTrace (false),
+    m_hasVar (false)
 {
 }
 
@@ -229,11 +230,174 @@ NsgpuP2pScenario::GetUdpServer (uint32_t app, uint32_t &received, uint32_t &lost
 
 uint32_t
 NsgpuP2pScenario::AddOnOff (uint32_t node, uint32_t dstNode, Time start, Time stop, uint64_t rateBps,
-                            uint32_t packetSize, double onSeconds, double offSeconds, uint32_t maxBytes, uint32_t ttl)
+                            uint32_t packetSize, double onSeconds, double offSeconds, uint32_t maxBytes, uint32_t ttl,
+                            const nsgpu_ranvar *onVar, const nsgpu_ranvar *offVar)
 {
   App a = {NSGPU_APP_ONOFF, node, dstNode, packetSize, maxBytes, ttl, start.GetTimeStep (), stop.GetTimeStep (),
            rateBps, onSeconds, offSeconds, 0, 0, 0, 9};
+  a.onVar = onVar ? *onVar : nsgpu_ranvar ();
+  a.offVar = offVar ? *offVar : nsgpu_ranvar ();
+  if (a.onVar.kind == NSGPU_RV_CONSTANT && onVar)
+    {
+      a.on = onVar->p0;
+    }
+  if (a.offVar.kind == NSGPU_RV_CONSTANT && offVar)
+    {
+      a.off = offVar->p0;
+    }
   return AddApp (a);
+}
+
+nsgpu_ranvar
+NsgpuP2pScenario::UniformVar (double min, double max, uint32_t stream)
+{
+  nsgpu_ranvar v = {NSGPU_RV_UNIFORM, stream, min, max};
+  return v;
+}
+
+nsgpu_ranvar
+NsgpuP2pScenario::ExponentialVar (double mean, double bound, uint32_t stream)
+{
+  nsgpu_ranvar v = {NSGPU_RV_EXPONENTIAL, stream, mean, bound};
+  return v;
+}
+
+void
+NsgpuP2pScenario::GetOnOffDraws (uint32_t app, uint32_t &onDraws, uint32_t &offDraws, uint32_t &ambiguous) const
+{
+  if (m_engine == 0 || app >= m_app.size () || m_app[app].kind != NSGPU_APP_ONOFF)
+    {
+      NS_FATAL_ERROR ("NsgpuP2pScenario::GetOnOffDraws: application " << app << " is not an OnOff of an engine");
+    }
+  std::vector<nsgpu_onoff_draw_record> rec (m_app.size ());
+  if (nsgpu_p2p_onoff_draws (m_engine, &rec[0], m_app.size (), 0) != NSGPU_OK)
+    {
+      NS_FATAL_ERROR ("libnsgpu: " << nsgpu_last_error ());
+    }
+  onDraws = rec[app].on_draws;
+  offDraws = rec[app].off_draws;
+  ambiguous = rec[app].ambiguous;
+}
+
+std::vector<nsgpu_ambiguous_draw>
+NsgpuP2pScenario::GetAmbiguousDraws (uint64_t &overflow) const
+{
+  if (m_engine == 0)
+    {
+      NS_FATAL_ERROR ("NsgpuP2pScenario::GetAmbiguousDraws: no engine");
+    }
+  std::vector<nsgpu_ambiguous_draw> rec (NSGPU_RV_AMBIGUOUS_CAP);
+  uint64_t n = 0;
+  if (nsgpu_p2p_onoff_ambiguous (m_engine, &rec[0], rec.size (), &n, &overflow, 0) != NSGPU_OK)
+    {
+      NS_FATAL_ERROR ("libnsgpu: " << nsgpu_last_error ());
+    }
+  rec.resize (n);
+  return rec;
+}
+
+NsgpuP2pScenario::OnOffDecl &
+NsgpuP2pScenario::OnOffDeclOf (Ptr<Application> app)
+{
+  for (size_t k = 0; k < m_declaredOnOff.size (); k++)
+    {
+      if (m_declaredOnOff[k].app == app)
+        {
+          return m_declaredOnOff[k];
+        }
+    }
+  OnOffDecl d;
+  d.app = app;
+  d.streams = d.exponential[0] = d.exponential[1] = false;
+  d.stream[0] = d.stream[1] = 0;
+  d.var[0] = d.var[1] = nsgpu_ranvar ();
+  m_declaredOnOff.push_back (d);
+  return m_declaredOnOff.back ();
+}
+
+void
+NsgpuP2pScenario::DeclareOnOffStreams (Ptr<Application> app, uint32_t onStream, uint32_t offStream)
+{
+  OnOffDecl &d = OnOffDeclOf (app);
+  d.streams = true;
+  d.stream[0] = onStream;
+  d.stream[1] = offStream;
+}
+
+void
+NsgpuP2pScenario::DeclareOnOffExponential (Ptr<Application> app, uint32_t which, double mean, double bound,
+                                           uint32_t stream)
+{
+  if (which > 1)
+    {
+      NS_FATAL_ERROR ("NsgpuP2pScenario::DeclareOnOffExponential: which is 0 (OnTime) or 1 (OffTime)");
+    }
+  OnOffDecl &d = OnOffDeclOf (app);
+  d.exponential[which] = true;
+  d.var[which] = ExponentialVar (mean, bound, stream);
+}
+
+/* An OnOffApplication's OnTime (which = 0) / OffTime (1) attribute as the engine takes it.  ConstantVariable (v) prints
+ * as "Constant:v" and UniformVariable (a, b) as "Uniform:a:b" (random-variable.cc:1931-1945; read back at 17 digits);
+ * the variable's RngStream is the one DeclareOnOffStreams named.  An ExponentialVariable does not print (:1957 sets
+ * badbit): DeclareOnOffExponential plays the role DeclareTrace plays for a trace client. */
+void
+NsgpuP2pScenario::MirrorOnOffTime (const RandomVariable &v, uint32_t which, uint32_t node, Ptr<Application> app,
+                                   double &seconds, nsgpu_ranvar &var) const
+{
+  const char *what = which == 0 ? "OnTime" : "OffTime";
+  const OnOffDecl *decl = 0;
+  for (size_t k = 0; k < m_declaredOnOff.size (); k++)
+    {
+      if (m_declaredOnOff[k].app == app)
+        {
+          decl = &m_declaredOnOff[k];
+        }
+    }
+  var = nsgpu_ranvar ();
+  std::ostringstream os;
+  os.precision (17);
+  os << v;
+  const std::string s = os.fail () ? std::string () : os.str ();
+  if (s.compare (0, 9, "Constant:") == 0)
+    {
+      std::ostringstream c;  // (the value as the attribute prints it by default, as before the other kinds were read)
+      c << v;
+      seconds = std::strtod (c.str ().c_str () + 9, 0);
+      return;
+    }
+  if (s.compare (0, 8, "Uniform:") == 0)
+    {
+      if (decl == 0 || !decl->streams)
+        {
+          NS_FATAL_ERROR ("NsgpuP2pScenario::FromNodeList: node " << node << ": OnOffApplication " << what << " is " << s
+                          << " and its RngStream was not named: call DeclareOnOffStreams (app, onStream, offStream) "
+                          "before FromNodeList (the engine cannot discover the order in which the program constructs "
+                          "its RngStreams)");
+        }
+      char *end = 0;
+      const double lo = std::strtod (s.c_str () + 8, &end);
+      if (end == 0 || *end != ':')
+        {
+          NS_FATAL_ERROR ("NsgpuP2pScenario::FromNodeList: node " << node << ": cannot read " << s);
+        }
+      var = UniformVar (lo, std::strtod (end + 1, 0), decl->stream[which]);
+      return;
+    }
+  if (s.empty () && decl != 0 && decl->exponential[which])
+    {
+      var = decl->var[which];
+      return;
+    }
+  if (!s.empty ())
+    {
+      NS_FATAL_ERROR ("NsgpuP2pScenario::FromNodeList: node " << node << ": OnOffApplication " << what << " is " << s
+                      << ": only ConstantVariable, UniformVariable and ExponentialVariable are modelled");
+    }
+  NS_FATAL_ERROR ("NsgpuP2pScenario::FromNodeList: node " << node << ": OnOffApplication " << what << " is a "
+                  "RandomVariable its attribute does not print (neither Constant, Uniform nor Normal).  If it is an "
+                  "ExponentialVariable, call DeclareOnOffExponential (app, " << which << ", mean, bound, stream) before "
+                  "FromNodeList; every other kind is not modelled");
 }
 
 void
@@ -344,22 +508,6 @@ NsgpuP2pScenario::GetFlowStats (Time maxDelay) const
 }
 
 namespace {
-/* ConstantVariable (v) prints as "Constant:v" (random-variable.cc:1931-1940); anything else draws from a
- * random stream, which the GPU-resident OnOff cannot */
-double
-ConstantSeconds (const RandomVariable &v, const char *what, uint32_t node)
-{
-  std::ostringstream os;
-  os << v;
-  const std::string s = os.str ();
-  if (s.compare (0, 9, "Constant:") != 0)
-    {
-      NS_FATAL_ERROR ("NsgpuP2pScenario::FromNodeList: node " << node << ": OnOffApplication " << what << " is " << s
-                      << ", not a ConstantVariable");
-    }
-  return std::strtod (s.c_str () + 9, 0);
-}
-
 Time
 TimeAttribute (Ptr<Object> o, const char *name)
 {
@@ -600,7 +748,7 @@ NsgpuP2pScenario::FromNodeList (Ptr<HipSimulatorImpl> impl)
                           << em->GetInstanceTypeId ().GetName () << ", which the engine does not model");
         }
     }
-  if (!m_em.empty ())
+  if (!m_em.empty () || !m_declaredOnOff.empty ())
     {
       IntegerValue gv;
       GlobalValue::GetValueByName ("RngSeed", gv);
@@ -680,8 +828,8 @@ NsgpuP2pScenario::FromNodeList (Ptr<HipSimulatorImpl> impl)
           RandomVariableValue on, off;
           o->GetAttribute ("OnTime", on);
           o->GetAttribute ("OffTime", off);
-          x.on = ConstantSeconds (on.Get (), "OnTime", n);
-          x.off = ConstantSeconds (off.Get (), "OffTime", n);
+          MirrorOnOffTime (on.Get (), 0, n, o, x.on, x.onVar);
+          MirrorOnOffTime (off.Get (), 1, n, o, x.off, x.offVar);
           AddressValue peer;
           o->GetAttribute ("Remote", peer);
           if (!InetSocketAddress::IsMatchingType (peer.Get ()))
@@ -936,6 +1084,22 @@ NsgpuP2pScenario::Fill (void)
   m_ext = nsgpu_p2p_scenario_ext ();
   m_ext.size = sizeof (m_ext);
   m_ext.trace_off = &m_cTraceOff[0], m_ext.trace_entries = &m_cTraceEnt[0];
+  // ... and so do the OnOff applications' random OnTime / OffTime variables
+  m_hasVar = false;
+  m_cOnVar.assign (A1, nsgpu_ranvar ()), m_cOffVar.assign (A1, nsgpu_ranvar ());
+  for (size_t i = 0; i < A; i++)
+    {
+      if (m_app[i].kind == NSGPU_APP_ONOFF)
+        {
+          m_cOnVar[i] = m_app[i].onVar, m_cOffVar[i] = m_app[i].offVar;
+          m_hasVar = m_hasVar || m_cOnVar[i].kind != NSGPU_RV_CONSTANT || m_cOffVar[i].kind != NSGPU_RV_CONSTANT;
+        }
+    }
+  if (m_hasVar)
+    {
+      m_ext.app_on_var = &m_cOnVar[0], m_ext.app_off_var = &m_cOffVar[0];
+      sc.rng_seed = m_rngSeed, sc.rng_run = m_rngRun;
+    }
   sc.n_setup = m_setup.size ();
   sc.setup_kind = m_cSk.empty () ? 0 : &m_cSk[0];
   sc.setup_index = m_cSi.empty () ? 0 : &m_cSi[0];
@@ -945,7 +1109,7 @@ nsgpu_p2p *
 NsgpuP2pScenario::CreateEngine (uint64_t poolCap, uint64_t logCap)
 {
   Fill ();
-  if (nsgpu_p2p_create_ex (&m_sc, m_hasTrace ? &m_ext : 0, poolCap, logCap, &m_engine) != NSGPU_OK ||
+  if (nsgpu_p2p_create_ex (&m_sc, (m_hasTrace || m_hasVar) ? &m_ext : 0, poolCap, logCap, &m_engine) != NSGPU_OK ||
       nsgpu_p2p_reset (m_engine, 0) != NSGPU_OK)
     {
       NS_FATAL_ERROR ("libnsgpu: " << nsgpu_last_error ());

@@ -70,8 +70,28 @@ public:
    * be read back from the object.  An undeclared UdpTraceClient ends FromNodeList in a fatal error.  A file is loaded
    * here as the application loaded it; SetRemote's clearing of the entries and SetTraceFile during Run are not modelled. */
   void DeclareTrace (Ptr<Application> app, std::string filename);
+  /* onVar / offVar: a UniformVariable or an ExponentialVariable OnTime / OffTime instead of the ConstantVariable
+   * onSeconds / offSeconds (0, or a variable of kind NSGPU_RV_CONSTANT: the constant).  UniformVar / ExponentialVar
+   * make one; `stream` is the index of the RngStream the program constructs for that variable (0-based, as for
+   * SetRateErrorModel: the engine cannot discover the order, the caller names it), seeded by SetRng's RngSeed / RngRun.
+   * The OnOff application draws Seconds (offVar) when it schedules StartSending and Seconds (onVar) when it schedules
+   * StopSending (onoff-application.cc:221-237).  An Exponential's log is the device's own (double-double); a draw
+   * whose timestamp could differ under the host's libm log is logged as ambiguous, not fatal: GetOnOffDraws and
+   * GetAmbiguousDraws read the counts and the log (an empty log with overflow 0: the run is the reference's). */
   uint32_t AddOnOff (uint32_t node, uint32_t dstNode, Time start, Time stop, uint64_t rateBps, uint32_t packetSize,
-                     double onSeconds, double offSeconds, uint32_t maxBytes, uint32_t ttl);
+                     double onSeconds, double offSeconds, uint32_t maxBytes, uint32_t ttl,
+                     const nsgpu_ranvar *onVar = 0, const nsgpu_ranvar *offVar = 0);
+  static nsgpu_ranvar UniformVar (double min, double max, uint32_t stream);
+  static nsgpu_ranvar ExponentialVar (double mean, double bound, uint32_t stream);
+  void GetOnOffDraws (uint32_t app, uint32_t &onDraws, uint32_t &offDraws, uint32_t &ambiguous) const;
+  std::vector<nsgpu_ambiguous_draw> GetAmbiguousDraws (uint64_t &overflow) const;
+  /* FromNodeList mirrors an OnOffApplication with a UniformVariable OnTime / OffTime (the attribute prints
+   * "Uniform:min:max") only when the streams of its two variables were named here before; an ExponentialVariable
+   * cannot be told from the attribute at all (random-variable.cc:1931-1957 prints Constant, Uniform and Normal only,
+   * and the Impl classes are private to that file), so the program declares it whole: which = 0 the OnTime, 1 the
+   * OffTime; bound 0: none.  An undeclared non-constant variable ends FromNodeList in a fatal error. */
+  void DeclareOnOffStreams (Ptr<Application> app, uint32_t onStream, uint32_t offStream);
+  void DeclareOnOffExponential (Ptr<Application> app, uint32_t which, double mean, double bound, uint32_t stream);
   void Stop (Time at);
   /* Ipv4AddressHelper (network, mask).Assign on the two devices of a link (host .1 on a, .2 on b) and
    * Ipv4L3Protocol::AddInterface's interface numbering (the loopback is interface 0) */
@@ -123,7 +143,8 @@ public:
    * Node::AddDevice order — PointToPointNetDevice DataRate / InterframeGap / TxQueue (DropTailQueue in
    * PACKETS mode: MaxPackets), its PointToPointChannel's Delay and peer; the LoopbackNetDevice — its Ipv4
    * interfaces (address, interface index), DefaultTtl, and its applications in Node::AddApplication order
-   * (OnOffApplication DataRate / PacketSize / Remote / OnTime / OffTime (ConstantVariable) / MaxBytes,
+   * (OnOffApplication DataRate / PacketSize / Remote / OnTime / OffTime (ConstantVariable; UniformVariable with
+   * DeclareOnOffStreams, ExponentialVariable with DeclareOnOffExponential) / MaxBytes,
    * PacketSink Local (Any, port), UdpEchoServer Port, UdpEchoClient RemoteAddress / RemotePort / MaxPackets /
    * Interval / PacketSize, UdpClient RemoteAddress / RemotePort / MaxPackets / Interval / PacketSize, UdpServer Port /
    * PacketWindowSize, UdpTraceClient RemoteAddress / RemotePort / MaxPacketSize with the trace DeclareTrace named;
@@ -134,7 +155,7 @@ public:
    * keeps its uid on the host (NSGPU_SETUP_UID).  A device's ReceiveErrorModel attribute is mirrored: a
    * ReceiveListErrorModel (GetList, IsEnabled), a RateErrorModel (GetRate, GetUnit, IsEnabled) whose stream
    * SetErrorStream named, RngSeed / RngRun from the GlobalValues.  Anything outside the GPU-resident subset (another
-   * device type, a random OnTime, two applications bound to one port of a node, a ListErrorModel or any other
+   * device type, an undeclared or unmodelled random OnTime, two applications bound to one port of a node, a ListErrorModel or any other
    * ErrorModel subclass, a RateErrorModel without a named stream, ...) is a fatal error. */
   void FromNodeList (Ptr<HipSimulatorImpl> impl);
   /* The journal entries the engine dispatches from now on (FromNodeList) */
@@ -172,7 +193,18 @@ private:
     uint32_t port;         // bound port of a PacketSink / UdpEchoServer / UdpServer
     uint32_t window;       // UdpServer PacketWindowSize
     std::vector<nsgpu_udp_trace_entry> entries;  // UdpTraceClient m_entries
+    nsgpu_ranvar onVar, offVar;  // OnOff: the OnTime / OffTime variables (kind NSGPU_RV_CONSTANT: on / off above)
   };
+  struct OnOffDecl  // DeclareOnOffStreams / DeclareOnOffExponential
+  {
+    Ptr<Application> app;
+    bool streams, exponential[2];
+    uint32_t stream[2];
+    nsgpu_ranvar var[2];
+  };
+  OnOffDecl &OnOffDeclOf (Ptr<Application> app);
+  void MirrorOnOffTime (const RandomVariable &v, uint32_t which, uint32_t node, Ptr<Application> app, double &seconds,
+                        nsgpu_ranvar &var) const;
   struct Em
   {
     uint32_t kind, enabled, unit, stream;  // NSGPU_EM_*, IsEnabled (), NSGPU_EU_*, the RngStream's index
@@ -196,6 +228,7 @@ private:
   std::vector<Em> m_em;                                 // per device (empty: no device has a receive error model)
   std::vector<std::pair<Ptr<NetDevice>, uint32_t> > m_errorStream;  // SetErrorStream
   std::vector<std::pair<Ptr<Application>, std::string> > m_declaredTrace;  // DeclareTrace
+  std::vector<OnOffDecl> m_declaredOnOff;
   uint32_t m_nDst;
   bool m_icmp;
   bool m_frag;
@@ -208,8 +241,9 @@ private:
   nsgpu_trace_codec *m_codec;
   // the C view (Fill)
   nsgpu_p2p_scenario m_sc;
-  nsgpu_p2p_scenario_ext m_ext;  // the UdpTraceClients' entries (m_hasTrace: given to the _ex entry points)
-  bool m_hasTrace;
+  nsgpu_p2p_scenario_ext m_ext;  // the UdpTraceClients' entries and the OnOff variables (m_hasTrace || m_hasVar:
+  bool m_hasTrace, m_hasVar;     // given to the _ex entry points)
+  std::vector<nsgpu_ranvar> m_cOnVar, m_cOffVar;
   std::vector<uint64_t> m_cTraceOff;
   std::vector<nsgpu_udp_trace_entry> m_cTraceEnt;
   std::vector<uint32_t> m_cDevNode, m_cDevPeer, m_cDevQmax, m_cKind, m_cNode, m_cDst, m_cSlot, m_cSrc, m_cSize,

@@ -170,6 +170,11 @@ SIGNATURES = {
     "nsgpu_p2p_error_models": (C.c_int, [_vp, _vp, _vp]),
     "nsgpu_p2p_flow_stats": (C.c_int, [_vp, C.c_int64, _vp, _vp]),
     "nsgpu_rng_stream_run": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, _vp, C.c_int, _vp]),
+    "nsgpu_p2p_onoff_draws": (C.c_int, [_vp, _vp, C.c_uint32, _vp]),
+    "nsgpu_p2p_onoff_ambiguous": (C.c_int, [_vp, _vp, _u64, _vp, _vp, _vp]),
+    "nsgpu_ranvar_run": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint64, _vp, _vp, _vp, _vp, C.c_int, _vp]),
+    "nsgpu_ranvar_log": (C.c_int, [_vp, C.c_uint64, _vp, _vp]),
+    "nsgpu_ranvar_exponential": (C.c_int, [C.c_double, C.c_double, C.c_uint32, _vp, _vp, _vp, _vp, _vp]),
     "nsgpu_error_model_thresholds": (C.c_int, [C.c_uint32, C.c_double, _vp]),
     "nsgpu_p2p_setup_uid": (C.c_int, [_vp, _vp]),
     "nsgpu_p2p_advance": (C.c_int, [_vp, _u64, _u32, _vp, _vp, _vp, _vp]),

@@ -58,8 +58,54 @@ class ScenarioStruct(C.Structure):
 
 
 class ScenarioExt(C.Structure):
-    """nsgpu_p2p_scenario_ext (include/nsgpu_types.h): the UdpTraceClients' entries, for the _ex entry points."""
+    """nsgpu_p2p_scenario_ext (include/nsgpu_types.h) as it was before the random OnOff times were appended: the
+    UdpTraceClients' entries, for the _ex entry points.  The record is size-prefixed, so this shorter form stays valid
+    and a scenario without a random variable still travels in it."""
     _fields_ = [("size", C.c_uint32), ("pad_", C.c_uint32), ("trace_off", C.c_void_p), ("trace_entries", C.c_void_p)]
+
+
+class ScenarioExtV2(C.Structure):
+    """nsgpu_p2p_scenario_ext in full: ScenarioExt and the OnOff applications' OnTime / OffTime variables."""
+    _fields_ = ScenarioExt._fields_ + [("app_on_var", C.c_void_p), ("app_off_var", C.c_void_p)]
+
+
+# random OnOff times: NSGPU_RV_*, nsgpu_ranvar, nsgpu_onoff_draw_record, nsgpu_ambiguous_draw
+RV_CONSTANT, RV_UNIFORM, RV_EXPONENTIAL, RV_OTHER = 0, 1, 2, 3
+RANVAR_DTYPE = np.dtype([("kind", "<u4"), ("stream", "<u4"), ("p0", "<f8"), ("p1", "<f8")])
+ONOFF_DRAWS_DTYPE = np.dtype([("on_draws", "<u4"), ("off_draws", "<u4"), ("ambiguous", "<u4"), ("pad_", "<u4")])
+AMBIGUOUS_DRAW_DTYPE = np.dtype([("app", "<u4"), ("which", "<u4"), ("ordinal", "<u4"), ("k", "<u4"), ("ns", "<i8"),
+                                 ("ns_other", "<i8")])
+RV_AMBIGUOUS_CAP = 1024  # NSGPU_RV_AMBIGUOUS_CAP: records of an engine's ambiguous-draw log
+RNG_NORM = 1.0 / 4294967088.0  # RngStream::U01: u = k * norm
+
+
+class RanVar:
+    """A RandomVariable of an OnOffApplication's OnTime / OffTime (nsgpu_ranvar): kind, the index of the RngStream the
+    program constructs for it (0-based, like a Rate error model's stream) and two parameters."""
+
+    def __init__(self, kind, stream, p0, p1=0.0):
+        self.kind, self.stream, self.p0, self.p1 = int(kind), int(stream), float(p0), float(p1)
+
+    def record(self):
+        return (self.kind, self.stream, self.p0, self.p1)
+
+    def __repr__(self):
+        return f"RanVar(kind={self.kind}, stream={self.stream}, p0={self.p0!r}, p1={self.p1!r})"
+
+
+def Constant(value):
+    """ConstantVariable (value): draws nothing (the on_s / off_s of add_onoff)."""
+    return RanVar(RV_CONSTANT, 0, value)
+
+
+def Uniform(min, max, stream):
+    """UniformVariable (min, max): min + U01 * (max - min), one U01 a value."""
+    return RanVar(RV_UNIFORM, stream, min, max)
+
+
+def Exponential(mean, stream, bound=0):
+    """ExponentialVariable (mean, bound): -mean * log (U01), redrawn while above a non-zero bound."""
+    return RanVar(RV_EXPONENTIAL, stream, mean, bound)
 
 
 class P2PStats(C.Structure):
@@ -170,7 +216,7 @@ class Scenario:
 
     def _app(self, **kw):
         a = dict(dst=0, rate=0, size=0, on=0.0, off=0.0, maxb=0, ttl=64, count=0, interval=0, port=0,
-                 remote_addr=None, remote_port=0, window=0)
+                 remote_addr=None, remote_port=0, window=0, on_var=None, off_var=None)
         a.update(kw)
         self.apps.append(a)
         self.setup.append((SETUP_APP, len(self.apps) - 1))  # Node::AddApplication
@@ -180,9 +226,19 @@ class Scenario:
         return self._app(kind=APP_SINK, node=node, start=start_ns, stop=stop_ns, port=port, ttl=0)
 
     def add_onoff(self, node, dst, start_ns, stop_ns, rate_bps=500000, size=512, on_s=1.0, off_s=1.0,
-                  max_bytes=0, ttl=64, remote_addr=None, remote_port=9):
+                  max_bytes=0, ttl=64, remote_addr=None, remote_port=9, on_var=None, off_var=None):
+        """OnOffHelper.Install.  on_s / off_s: ConstantVariable OnTime / OffTime; on_var / off_var: a Uniform or
+        Exponential (or Constant) variable instead (random OnOff times on the device: DESIGN 4.4g)."""
+        for v in (on_var, off_var):
+            if v is not None and not isinstance(v, RanVar):
+                raise TypeError("on_var / off_var: p2p.Uniform, p2p.Exponential or p2p.Constant")
+        if on_var is not None and on_var.kind == RV_CONSTANT:
+            on_s, on_var = on_var.p0, None
+        if off_var is not None and off_var.kind == RV_CONSTANT:
+            off_s, off_var = off_var.p0, None
         return self._app(kind=APP_ONOFF, node=node, start=start_ns, stop=stop_ns, dst=dst, rate=rate_bps, size=size,
-                         on=on_s, off=off_s, maxb=max_bytes, ttl=ttl, remote_addr=remote_addr, remote_port=remote_port)
+                         on=on_s, off=off_s, maxb=max_bytes, ttl=ttl, remote_addr=remote_addr, remote_port=remote_port,
+                         on_var=on_var, off_var=off_var)
 
     def add_echo_server(self, node, start_ns, stop_ns, port=9):  # UdpEchoServerHelper (port).Install
         return self._app(kind=APP_ECHO_SERVER, node=node, start=start_ns, stop=stop_ns, port=port, ttl=64)
@@ -403,8 +459,11 @@ class Scenario:
         return s
 
     def c_ext(self):
-        """The nsgpu_p2p_scenario_ext of a scenario with a UdpTraceClient (None without one: the plain entry points)."""
-        if not any(a["kind"] == APP_UDP_TRACE_CLIENT for a in self.apps):
+        """The nsgpu_p2p_scenario_ext of a scenario with a UdpTraceClient or a random OnOff time (None without either:
+        the plain entry points)."""
+        has_trace = any(a["kind"] == APP_UDP_TRACE_CLIENT for a in self.apps)
+        has_var = any(a.get("on_var") is not None or a.get("off_var") is not None for a in self.apps)
+        if not has_trace and not has_var:
             return None
         off = np.zeros(len(self.apps) + 1, np.uint64)
         ent = []
@@ -416,10 +475,18 @@ class Scenario:
             if not (0 <= t < 1 << 32 and 0 <= z < 1 << 32):
                 raise ValueError("trace entry outside uint32")
         arr = np.array(ent or [(0, 0)], dtype=np.uint64).astype(np.uint32).view(UDP_TRACE_ENTRY_DTYPE).reshape(-1)
-        x = ScenarioExt()
-        x.size = C.sizeof(ScenarioExt)
+        x = ScenarioExtV2() if has_var else ScenarioExt()
+        x.size = C.sizeof(x)
         x.trace_off, x.trace_entries = off.ctypes.data, arr.ctypes.data
         x._keep = (off, arr)
+        if has_var:
+            const = (RV_CONSTANT, 0, 0.0, 0.0)
+            on = np.array([a["on_var"].record() if a.get("on_var") is not None else const for a in self.apps],
+                          RANVAR_DTYPE)
+            offv = np.array([a["off_var"].record() if a.get("off_var") is not None else const for a in self.apps],
+                            RANVAR_DTYPE)
+            x.app_on_var, x.app_off_var = on.ctypes.data, offv.ctypes.data
+            x._keep += (on, offv)
         return x
 
 
@@ -774,6 +841,24 @@ class Engine:
         nsgpu.check(nsgpu.lib().nsgpu_p2p_error_models(self.h, out.ctypes.data, self.stream))
         return out
 
+    def onoff_draws(self):
+        """Per application, the GetValue calls on its OnTime and OffTime variables and their ambiguous attempts
+        (nsgpu_p2p_onoff_draws: ONOFF_DRAWS_DTYPE; zeros without a random variable)."""
+        out = np.zeros(self.s.n_apps, ONOFF_DRAWS_DTYPE)
+        nsgpu.check(nsgpu.lib().nsgpu_p2p_onoff_draws(self.h, out.ctypes.data, self.s.n_apps, self.stream))
+        return out
+
+    def ambiguous_draws(self):
+        """(records, overflow): the log of ambiguous Exponential attempts (nsgpu_p2p_onoff_ambiguous:
+        AMBIGUOUS_DRAW_DTYPE, unordered) and the attempts that found its RV_AMBIGUOUS_CAP records full.  Empty with
+        overflow 0: every timestamp of the run is the reference's on a host whose libm log errs below 1 ulp;
+        check_ambiguous decides the listed ones for this host."""
+        out = np.zeros(RV_AMBIGUOUS_CAP, AMBIGUOUS_DRAW_DTYPE)
+        n, over = C.c_uint64(), C.c_uint64()
+        nsgpu.check(nsgpu.lib().nsgpu_p2p_onoff_ambiguous(self.h, out.ctypes.data, RV_AMBIGUOUS_CAP, C.byref(n),
+                                                          C.byref(over), self.stream))
+        return out[:n.value], int(over.value)
+
     def flow_stats(self, max_delay_ns=MAX_PER_HOP_DELAY_NS):
         """FlowMonitor's FlowStats of the flows that sent anything (nsgpu_p2p_flow_stats: FLOW_STATS_DTYPE), ordered
         by flow_id: FlowIds are 1-based in the order of the flows' first transmissions, as Ipv4FlowClassifier numbers
@@ -1029,6 +1114,21 @@ class LoopbackGroup:
         per = [m.frag_stats() for m in self.members]
         return {k: (max if k == "max_list" else sum)(p[k] for p in per) for k in FRAG_STATS_FIELDS}
 
+    def onoff_draws(self):
+        """Every application's draw counts from the rank owning its node (the variables' state lives there)."""
+        per = [m.onoff_draws() for m in self.members]
+        app_node = self.members[0].s._keep["app_node"]
+        out = per[0].copy()
+        for r, rec in enumerate(per):
+            m = self.owner[app_node] == r
+            out[m] = rec[m]
+        return out
+
+    def ambiguous_draws(self):
+        """Every partition's ambiguous attempts (each rank logs its own nodes' applications) and the overflows' sum."""
+        per = [m.ambiguous_draws() for m in self.members]
+        return np.concatenate([p[0] for p in per]), sum(p[1] for p in per)
+
     def error_models(self):
         """Every device's error-model record from the rank owning its node (the model's state lives there)."""
         per = [m.error_models() for m in self.members]
@@ -1070,6 +1170,69 @@ def rng_stream(seed, run, stream, n, on_device=False, hip_stream=None):
     out = np.zeros(n, np.float64)
     nsgpu.check(nsgpu.lib().nsgpu_rng_stream_run(seed, run, stream, n, out.ctypes.data, int(on_device), hip_stream))
     return out
+
+
+def ranvar_run(var, seed, run, n, on_device=False, hip_stream=None):
+    """n values of RanVar `var`, whose stream is the var.stream-th RngStream of a program with RngSeed `seed` and RngRun
+    `run` (nsgpu_ranvar_run): (seconds, ns, ns_other, ambiguous) — GetValue (), Seconds (that), the other candidate's
+    timestamp of an ambiguous draw (ns otherwise) and the flag — on the host, or in a one-thread kernel by the function
+    the handlers call."""
+    v = np.array([var.record()], RANVAR_DTYPE)
+    sec, ns, other = np.zeros(n, np.float64), np.zeros(n, np.int64), np.zeros(n, np.int64)
+    amb = np.zeros(n, np.uint8)
+    nsgpu.check(nsgpu.lib().nsgpu_ranvar_run(v.ctypes.data, seed, run, n, sec.ctypes.data, ns.ctypes.data,
+                                             other.ctypes.data, amb.ctypes.data, int(on_device), hip_stream))
+    return sec, ns, other, amb.astype(bool)
+
+
+def ranvar_log(u):
+    """The device's double-double log on the host (nsgpu_ranvar_log): (hi, lo) arrays for doubles u in [2^-33, 1)."""
+    u = np.ascontiguousarray(u, np.float64)
+    hi, lo = np.zeros(u.size, np.float64), np.zeros(u.size, np.float64)
+    nsgpu.check(nsgpu.lib().nsgpu_ranvar_log(u.ctypes.data, u.size, hi.ctypes.data, lo.ctypes.data))
+    return hi, lo
+
+
+def ranvar_exponential(mean, bound, k):
+    """One ExponentialVariable attempt from the integer k behind u (nsgpu_ranvar_exponential, host): a dict with r,
+    ns, ns_other, accept, ambiguous."""
+    r, ns, other = C.c_double(), C.c_int64(), C.c_int64()
+    acc, amb = C.c_int(), C.c_int()
+    nsgpu.check(nsgpu.lib().nsgpu_ranvar_exponential(float(mean), float(bound), int(k), C.byref(r), C.byref(ns),
+                                                     C.byref(other), C.byref(acc), C.byref(amb)))
+    return dict(r=r.value, ns=ns.value, ns_other=other.value, accept=bool(acc.value), ambiguous=bool(amb.value))
+
+
+def seconds_to_ns(s):
+    """Seconds (double).GetTimeStep () at ns resolution on the host, in exact integer arithmetic: int64x64_t (s) is
+    floor (s) and floor (frac * (2^64 - 1 as a double = 2^64)) as a 64.64 fixed-point value, times 10^9, high word
+    (int64x64-128.cc; csrc/nsgpu_device.h seconds_to_ts).  s >= 0."""
+    import math
+    hi = math.floor(s)
+    lo = int((s - hi) * 18446744073709551615.0)
+    return int(hi) * 10**9 + ((lo * 10**9) >> 64)
+
+
+def check_ambiguous(records, scenario):
+    """The listed ambiguous attempts (Engine.ambiguous_draws) decided for THIS host: each is recomputed with the host's
+    math.log, which is what the reference calls, and the ones whose host timestamp differs from the one the device
+    took — or, for a bounded variable, whose host accept / reject decision differs from the device's — are returned.
+    Empty, with no overflow, means the run is the reference's on this host."""
+    import math
+    bad = []
+    for rec in records:
+        a = scenario.apps[int(rec["app"])]
+        v = a["on_var"] if int(rec["which"]) == 0 else a["off_var"]
+        u = float(int(rec["k"])) * RNG_NORM
+        mean, bound = v.p0, v.p1
+        rh = -mean * math.log(u)
+        differs = seconds_to_ns(rh) != int(rec["ns"])
+        if bound != 0:
+            dev = ranvar_exponential(mean, bound, int(rec["k"]))
+            differs = differs or (rh <= bound) != dev["accept"]
+        if differs:
+            bad.append(rec)
+    return np.array(bad, AMBIGUOUS_DRAW_DTYPE)
 
 
 def error_model_thresholds(unit, rate):
