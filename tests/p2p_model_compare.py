@@ -1,6 +1,6 @@
 """An engine's (or a group's) results against a Python model's run, bit for bit: what tests/test_gpu_frag.py,
-tests/test_gpu_errmodel.py and tests/test_gpu_p2p_fuzz.py assert.  Everything compared is integer state, so there are
-no tolerances."""
+tests/test_gpu_errmodel.py, tests/test_gpu_p2p_fuzz.py and tests/test_gpu_p2p_sources_fuzz.py assert.  Everything
+compared is integer state, so there are no tolerances."""
 import numpy as np
 
 import trace
@@ -24,7 +24,7 @@ def first_log_difference(log, want):
     return i, tuple(tuple(int(x[i]) for x in lg) if i < len(lg[0]) else None for lg in (log, want))
 
 
-def _compare(m, st, devc, appc, log, servers, frag, em, tr, label, context):
+def _compare(m, st, devc, appc, log, servers, frag, em, tr, label, context, clients=None, draws=None):
     note = " | " + label if label else ""
     diff = first_log_difference(log, m["log"])
     if diff is not None:
@@ -43,6 +43,12 @@ def _compare(m, st, devc, appc, log, servers, frag, em, tr, label, context):
     assert frag == m["frag"], "fragmentation counters" + note
     if em is not None:
         assert np.array_equal(em, m["em"]), "error models' records" + note
+    if clients is not None:
+        for f in ("sent", "current_entry", "sends"):
+            assert np.array_equal(clients[f], m["clients"][f]), "trace clients' " + f + note
+    if draws is not None:
+        for f in ("on_draws", "off_draws", "ambiguous"):
+            assert np.array_equal(draws[f], m["draws"][f]), "OnOff " + f + note
     if tr is not None:
         tr, want = trace.sort_records(tr), trace.sort_records(m["trace"])
         assert len(tr) == len(want), "trace length" + note
@@ -56,6 +62,8 @@ def assert_equals_frag_model(m, st, devc, appc, log, servers, frag, tr=None, lab
     _compare(m, st, devc, appc, log, servers, frag, None, tr, label, context)
 
 
-def assert_equals_model(m, st, devc, appc, log, servers, frag, em, tr=None, label="", context=None):
-    """m: a run of tests/p2p_errmodel_pyref.py: the above and the error models' records."""
-    _compare(m, st, devc, appc, log, servers, frag, em, tr, label, context)
+def assert_equals_model(m, st, devc, appc, log, servers, frag, em, tr=None, label="", context=None, clients=None,
+                        draws=None):
+    """m: a run of tests/p2p_errmodel_pyref.py: the above and the error models' records.  clients / draws: an engine's
+    trace_clients () / onoff_draws () against a run of tests/p2p_full_pyref.py."""
+    _compare(m, st, devc, appc, log, servers, frag, em, tr, label, context, clients, draws)
