@@ -1926,13 +1926,37 @@ __device__ uint64_t g_gt[GT_BLK_MAX][8];
   } while (0)
 // What the lanes of each of k2_handle's holder blocks ran in the sampled window: g_blkk[block] = {Receives, gen-0
 // TransmitCompletes, local records, Sends, events of other kinds, the busiest lane's events, holder lanes}
-constexpr int BLKK_MAX = 64, BLKK_N = 8;
+// ... and where a lane's local record took its time: [8..12] = the block's slowest lane's shader-clock cycles
+// (s_memtime) from the parent event's slot_done (HN_T(0)) to local_record's return (1), lq_push's (2), the record's
+// pop at the loop's top (3), its own slot_done (4) and the loop's next top (5); a fused record (handle_node2) has
+// marks 0, 1 and 4 only.  The last record a lane made counts.  [13] = the slowest lane's cycles in handle_node2
+// (the scale of the others against the block's stamped duration).
+constexpr int BLKK_MAX = 64, BLKK_N = 16;
 __device__ uint32_t g_blkk[BLKK_MAX][BLKK_N];
-#define BLK_KINDS_T0(C)             \
+#define BLK_KINDS_T0(C)              \
   uint32_t bk_[5] = {0, 0, 0, 0, 0}; \
+  uint64_t hn_[6] = {0, 0, 0, 0, 0, 0}; \
+  bool hn_open_ = false;             \
+  const uint64_t hn_t0_ = __builtin_amdgcn_s_memtime(); \
   const uint64_t bkw_ = (C).windows
 #define BLK_KINDS_EV(kind, local) \
   bk_[(local) ? 2 : (kind) == K_RECEIVE ? 0 : (kind) == K_TX_COMPLETE ? 1 : (kind) == K_SEND ? 3 : 4]++
+#define HN_T(i) hn_[i] = __builtin_amdgcn_s_memtime()
+#define HN_BEGIN()                                \
+  do {                                            \
+    for (int k_ = 1; k_ < 6; k_++) hn_[k_] = 0;   \
+    hn_open_ = false;                             \
+    HN_T(0);                                      \
+  } while (0)
+// (the loop's top after a queued record ran: mark 5, once)
+#define HN_TOP()      \
+  do {                \
+    if (hn_open_) {   \
+      HN_T(5);        \
+      hn_open_ = false; \
+    }                 \
+  } while (0)
+#define HN_RAN() hn_open_ = true
 #define BLK_KINDS_REC(holder)                                                                    \
   do {                                                                                           \
     if (bkw_ == g_blk_win && blockIdx.x < (uint32_t)BLKK_MAX && (holder)) {                      \
@@ -1940,6 +1964,13 @@ __device__ uint32_t g_blkk[BLKK_MAX][BLKK_N];
         if (bk_[k_]) atomicAdd(&g_blkk[blockIdx.x][k_], bk_[k_]);                                \
       atomicMax(&g_blkk[blockIdx.x][5], bk_[0] + bk_[1] + bk_[2] + bk_[3] + bk_[4]);             \
       atomicAdd(&g_blkk[blockIdx.x][6], 1u);                                                     \
+      for (int k_ = 1; k_ < 6; k_++) {                                                           \
+        int p_ = k_ - 1;                                                                         \
+        while (p_ > 0 && hn_[p_] == 0) p_--;                                                     \
+        if (hn_[k_] > hn_[p_] && hn_[p_] != 0)                                                   \
+          atomicMax(&g_blkk[blockIdx.x][7 + k_], (uint32_t)(hn_[k_] - hn_[p_]));                 \
+      }                                                                                          \
+      atomicMax(&g_blkk[blockIdx.x][13], (uint32_t)(__builtin_amdgcn_s_memtime() - hn_t0_));     \
     }                                                                                            \
   } while (0)
 #else
@@ -1949,6 +1980,10 @@ __device__ uint32_t g_blkk[BLKK_MAX][BLKK_N];
 #define BLK_KINDS_T0(C) (void)0
 #define BLK_KINDS_EV(kind, local) (void)0
 #define BLK_KINDS_REC(holder)      (void)0
+#define HN_T(i) (void)0
+#define HN_BEGIN() (void)0
+#define HN_TOP() (void)0
+#define HN_RAN() (void)0
 #endif
 
 // ================================ window pipeline ================================

@@ -968,6 +968,8 @@ __device__ __forceinline__ uint64_t lk_word2(const LKey &k) {
 __device__ __forceinline__ uint32_t local_record(const P2PDev &M, const Emit &E, uint32_t par, uint64_t tmin,
                                                  uint32_t region, uint32_t *cnt, bool atomic, uint64_t par_key) {
   const uint32_t cap = region < (uint32_t)NHB ? (uint32_t)LR : (uint32_t)LRH;
+  // (one wave-level add for the holder lanes that arrive together, wave_alloc32, measured no gain over the
+  // per-lane LDS atomic: DESIGN.md 4.4, r18)
   const uint32_t k = atomic ? atomicAdd(cnt, 1u) : (*cnt)++;
   if (k >= cap) {
     atomicOr(M.error, 32u);
@@ -1286,6 +1288,7 @@ __device__ __forceinline__ void handle_node2(const P2PDev &M, Ctl &C, uint32_t i
           }
           pending = 0;
         }
+        HN_TOP();
         if (!hg && !hl) break;
         if (!started || rel > cur_rel) {
           ts0_it = it;
@@ -1304,6 +1307,7 @@ __device__ __forceinline__ void handle_node2(const P2PDev &M, Ctl &C, uint32_t i
           kw = K_TX_COMPLETE;
           E.uid = s, E.tloc = true;
           E.demote = false;
+          HN_T(3);
         } else {
           s = my[it];
           key = mk[it];
@@ -1341,9 +1345,35 @@ __device__ __forceinline__ void handle_node2(const P2PDev &M, Ctl &C, uint32_t i
           for (uint32_t j = 0; j < E.n; j++) ni += (E.ch_kind[E.slot0 + j] & 0xffu) == K_FWD_UP;
         slot_done(M, s, key, E.n, ni, xa);
         pending += ni;
+        if (WIDE && E.tloc) {
+          HN_T(4);
+          HN_RAN();
+        }
         if (WIDE && E.lj >= 0) {
+          HN_BEGIN();
           const uint32_t r2 = local_record(M, E, s, tmin, blockIdx.x, lcnt_sh, true, key);
-          if (r2 != NOSRC) lq_push(M, lq, qh, nq, (uint32_t)(E.lts - tmin), r2, E.lctx, E.la);
+          HN_T(1);
+          if (r2 != NOSRC) {
+            // The record's TransmitComplete run on the spot when it is the node's next event and finds its device's
+            // queue empty: nothing is queued before it (qh == nq), no inline leaf of this ts group waits for the
+            // group's end (pending == 0, this event's own included), the node's next gen-0 event is strictly later
+            // (at equal ts the gen-0 event goes first: its uid is older), and the cached device is the record's with
+            // an empty DropTail queue.  The whole event is then its slot's counts and busy = 0: node_part returns
+            // ACT_KICK at once for K_TX_COMPLETE, device_act_cached's ACT_KICK branch with cnt == 0 starts no
+            // transmission (no child, no trace sink), and the EXT device_step loops only over a Send's parts.  Every
+            // other case goes through the queue as before.
+            const uint32_t lrel = (uint32_t)(E.lts - tmin);
+            if (qh == nq && pending == 0 && (it >= n || (mk[it] >> 32) > (uint64_t)lrel) && D.d == E.la &&
+                D.cnt == 0) {
+              BLK_KINDS_EV(K_TX_COMPLETE, true);
+              slot_done(M, r2, 0, 0, 0, xa);
+              D.busy = 0;
+              HN_T(4);
+            } else {
+              lq_push(M, lq, qh, nq, lrel, r2, E.lctx, E.la);
+              HN_T(2);
+            }
+          }
         }
       }
       D.flush(M);

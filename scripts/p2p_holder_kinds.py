@@ -1,7 +1,11 @@
 """Diagnostic: k2_handle's 64 holder blocks at sampled windows of the default grid (lib/libnsgpu_prof.so): each
 block's end time beside what its lanes ran (Receives, gen-0 TransmitCompletes, local records, Sends, other kinds,
 the busiest lane's events).  The question it answers: are the blocks that end last the ones that ran a Send?
-Usage: python scripts/p2p_holder_kinds.py [n] [first] [step] [count] [--table]
+With --marks also where a lane's local record took its time (handle_node2's HN_T marks, the block's slowest lane):
+from its parent's slot_done to local_record's return, lq_push's, the record's pop, its own slot_done and the loop's
+next top, in us (shader-clock cycles scaled by the block's stamped duration over the holder's cycles); a fused
+record has the first and the fourth only (the fourth: from local_record's return).
+Usage: python scripts/p2p_holder_kinds.py [n] [first] [step] [count] [--table] [--marks]
 Each sample re-runs the engine with the stamps aimed at window w (nsgpu_p2p_phase_read(-w))."""
 import os
 import sys
@@ -15,6 +19,8 @@ import p2p  # noqa: E402
 
 args = [a for a in sys.argv[1:] if not a.startswith("--")]
 table = "--table" in sys.argv
+marks = "--marks" in sys.argv
+MARK_NAMES = ("local_record", "lq_push", "to the pop", "the event", "next top")
 n = int(args[0]) if len(args) > 0 else 128
 first = int(args[1]) if len(args) > 1 else 300
 step = int(args[2]) if len(args) > 2 else 100
@@ -24,7 +30,7 @@ eng = p2p.Engine(p2p.grid(n, n))
 st, _, _, _ = eng.run()
 W = int(st.windows)
 print(f"grid {n} x {n}: {st.dispatched} events, {W} windows, wide {eng.wide()}", flush=True)
-BLK, GT, NHB, NK = 2048, 8192, 64, 8
+BLK, GT, NHB, NK = 2048, 8192, 64, 16
 buf = np.zeros(64 + 3 * BLK * 2 + GT * 8 + NHB * NK // 2, np.uint64)
 rows = []
 for w in list(range(first, W, step))[:count]:
@@ -53,6 +59,14 @@ for w in list(range(first, W, step))[:count]:
         for i in order:
             k = kinds[i]
             print(f"   {i:3d} {end[i]:5.2f} {dur[i]:6.2f} {k[0]:5d} {k[1]:4d} {k[2]:6d} {k[3]:4d} {k[4]:5d} {k[5]:8d} {k[6]:7d}")
+    if marks:
+        full = (kinds[:, 6] >= 60) & (kinds[:, 2] >= kinds[:, 6] - 2) & (kinds[:, 13] > 0)  # every lane ran a pair
+        if full.any():
+            us = dur[full, None] * kinds[full, 8:13] / kinds[full, 13:14]
+            print(f"   {full.sum()} blocks whose lanes each made a local record: holder {dur[full].mean():5.2f} us = "
+                  f"{kinds[full, 13].mean():.0f} cycles; " +
+                  ", ".join(f"{n} {u:.2f} us ({c:.0f} cy)" for n, u, c in zip(MARK_NAMES, us.mean(0), kinds[full, 8:13].mean(0))),
+                  flush=True)
     rows.append((end, dur, kinds.copy(), send))
 if rows:
     end = np.concatenate([r[0] for r in rows])
