@@ -40,6 +40,9 @@ int         nsgpu_version(void);                 /* 100 * major + minor */
 const char *nsgpu_last_error(void);
 int         nsgpu_device_count(int *count);
 int         nsgpu_set_device(int device);
+/* The current device's CU count and the LDS bytes one block may use: what nsgpu_wifi_create plans its
+ * split-queue store from (nsgpu_wifi_get_store reports the plan). */
+int         nsgpu_device_limits(int *compute_units, int *lds_bytes_per_block);
 int         nsgpu_malloc(void **d_ptr, size_t bytes);
 int         nsgpu_free(void *d_ptr);
 int         nsgpu_memcpy_htod(void *d_dst, const void *h_src, size_t bytes, void *stream);

@@ -29,6 +29,14 @@ int nsgpu_set_device(int device) {
   NSGPU_HIP(hipSetDevice(device));
   return NSGPU_OK;
 }
+int nsgpu_device_limits(int *compute_units, int *lds_bytes_per_block) {
+  if (!compute_units || !lds_bytes_per_block) return set_error(NSGPU_EINVAL, "nsgpu_device_limits: null");
+  int dev = 0;
+  NSGPU_HIP(hipGetDevice(&dev));
+  NSGPU_HIP(hipDeviceGetAttribute(compute_units, hipDeviceAttributeMultiprocessorCount, dev));
+  NSGPU_HIP(hipDeviceGetAttribute(lds_bytes_per_block, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
+  return NSGPU_OK;
+}
 int nsgpu_malloc(void **d_ptr, size_t bytes) {
   if (!d_ptr) return set_error(NSGPU_EINVAL, "nsgpu_malloc: null");
   hipError_t e = hipMalloc(d_ptr, bytes ? bytes : 1);

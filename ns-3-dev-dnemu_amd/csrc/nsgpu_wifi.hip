@@ -21,8 +21,11 @@
 //   Receive(T1) before Receive(T2)       iff T1 precedes T2 in the schedule (their fan-outs' uid bases);
 //   Receive(T) before EndReceive(R)      iff T was dispatched before the syncing Receive R: t_T <= ts_R;
 //   EndReceive(R1) before EndReceive(R2) iff R1 precedes R2 (ts, then schedule order).
-// A transmission's arrivals come at t_T + d with d > 0, so the next Receive of phy j is the smallest arrival
-// among the transmissions t_T below it: a 64-transmission window after the first unconsumed one.
+// A transmission's arrivals come at t_T + d with d >= 0 (phys a few centimetres apart — the two radios of one
+// node — are 0 ns apart in the reference's integer nanoseconds), so the next Receive of phy j is the smallest arrival among the
+// transmissions with t_T at or below it, equal arrivals in schedule order: a 64-transmission window after the
+// first unconsumed one.  The rules above hold at d = 0 as they stand: a SendPacket at ts_R has a setup uid, so
+// it was dispatched before the Receive R of that nanosecond, whatever the delay.
 //
 // The uids follow from counts (k_sync_hist, k_tx_base, k_sync_place, k_sync_rank): a Receive's syncing
 // consumes one uid (the EndReceive), a transmission's fan-out consumes one per receiver.  With
@@ -221,16 +224,19 @@ struct RingNi {
   __device__ __forceinline__ bool phys_room() const { return true; }
   __device__ __forceinline__ void on_receive(int64_t) {}
   // AppendEvent, not receiving (interference-helper.cc:192-212): fold the entries up to upper_bound (now)
-  // into m_firstPower, drop them, the new entry first; returns m_firstPower
-  __device__ __forceinline__ double fold_start(int64_t nw, double p) {
+  // into m_firstPower and drop them (fold_drop: returns m_firstPower), then the new entry first (push_front).
+  // The caller asks room () in between: the capacity bounds the list the reference keeps, after the erase.
+  __device__ __forceinline__ double fold_drop(int64_t nw) {
     cursor_advance<true>(ring, head, len, m, nw, cur_n, cur_s);
     head = (head + cur_n) & m;
     len -= cur_n;
     cur_n = 0;
+    return cur_s;
+  }
+  __device__ __forceinline__ void push_front(int64_t nw, double p) {
     head = (head - 1) & m;
     ring[head] = NiEnt{nw, p};
     len++;
-    return cur_s;
   }
   __device__ __forceinline__ void insert_start(int64_t nw, double p) { ni_insert(ring, head, len, m, nw, p); }
   __device__ __forceinline__ void insert_end(int64_t t, double d) { ni_insert(ring, head, len, m, t, d); }
@@ -347,15 +353,17 @@ struct SplitNi {
     }
   }
   __device__ __forceinline__ void on_receive(int64_t nw) { advance<false>(nw); }
-  __device__ __forceinline__ double fold_start(int64_t nw, double p) {
+  __device__ __forceinline__ double fold_drop(int64_t nw) {
     advance<true>(nw);  // (S is empty after it: every start is at or before now)
     ndead = 0;
+    return cur_s;
+  }
+  __device__ __forceinline__ void push_front(int64_t nw, double p) {  // (after fold_drop: S is empty)
     st[sx(0)] = nw;
     sd[sx(0)] = p;
     ns = 1;
     hts = nw;
     hds = p;
-    return cur_s;
   }
   __device__ __forceinline__ void insert_start(int64_t nw, double p) {
     st[sx(ns)] = nw;
@@ -767,7 +775,8 @@ __device__ __forceinline__ void phy_run(const WifiDev &D, const int64_t j, Ni &n
     WPH(6);  // (kind decision, Receive operands)
     ni.on_receive(nw);
     WPH(7);  // the eager cursor
-    if (!ni.room()) {
+    if (!rxing) firstPower = ni.fold_drop(nw);  // fold up to upper_bound (now) into m_firstPower
+    if (!ni.room()) {  // (asked after the fold's erase: ni_cap bounds the list the reference would hold)
       err |= ERR_NICAP;
       break;
     }
@@ -775,7 +784,7 @@ __device__ __forceinline__ void phy_run(const WifiDev &D, const int64_t j, Ni &n
       err |= ERR_LDS;
       break;
     }
-    if (!rxing) firstPower = ni.fold_start(nw, rxPowerW);  // fold up to upper_bound (now) into m_firstPower
+    if (!rxing) ni.push_front(nw, rxPowerW);
     else ni.insert_start(nw, rxPowerW);
     WPH(8);  // fold / start entry
     ni.insert_end(endNew, -rxPowerW);

@@ -70,6 +70,7 @@ SIGNATURES = {
     "nsgpu_last_error": (C.c_char_p, []),
     "nsgpu_device_count": (C.c_int, [C.POINTER(C.c_int)]),
     "nsgpu_set_device": (C.c_int, [C.c_int]),
+    "nsgpu_device_limits": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "nsgpu_malloc": (C.c_int, [C.POINTER(C.c_void_p), C.c_size_t]),
     "nsgpu_free": (C.c_int, [_vp]),
     "nsgpu_memcpy_htod": (C.c_int, [_vp, _vp, C.c_size_t, _vp]),

@@ -15,6 +15,7 @@ import nsgpu
 import nsref
 import wifi
 from test_wifi_oracle import random_scenario, run_oracle, tie_scenario
+from wifi_rx_check import check_engine
 
 pytestmark = pytest.mark.gpu
 
@@ -35,26 +36,9 @@ def grid100_committed():
 
 
 def compare(sc, rx_log=True, store=wifi.STORE_AUTO):
-    st, phys, base, ends, log = run_oracle(sc, rx_log=rx_log)
+    oracle = run_oracle(sc, rx_log=rx_log)
     eng = wifi.Engine(sc, rx_log=rx_log, store=store)
-    g = eng.run()
-    gd, od = g.as_dict(), st.as_dict()
-    assert g.near_threshold == 0 and st.near_threshold == 0
-    assert gd == od, {k: (gd[k], od[k]) for k in gd if gd[k] != od[k]}
-    assert np.array_equal(eng.tx_base(), base)
-    ge = eng.ends()
-    assert len(ge) == len(ends)
-    assert np.array_equal(ge, ends)
-    gp = eng.phys()
-    for f in wifi.PHY_COUNTERS_DTYPE.names:
-        if f == "first_power":
-            np.testing.assert_allclose(gp[f], phys[f], rtol=1e-9, atol=1e-24)
-        else:
-            assert np.array_equal(gp[f], phys[f]), f
-    if rx_log:
-        gl = eng.rx_log_read()
-        for f in ("ts", "uid", "outcome", "flags", "cca_ns"):
-            assert np.array_equal(gl[f], log[f]), (f, np.nonzero(gl[f] != log[f])[0][:10])
+    st = check_engine(eng, oracle, rx_log=rx_log)  # (tests/wifi_rx_check.py: the comparison itself)
     eng.close()
     return st
 

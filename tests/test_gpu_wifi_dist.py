@@ -10,28 +10,9 @@ import p2p
 import wifi
 from test_gpu_wifi import grid100_committed
 from test_wifi_oracle import random_scenario, run_oracle, tie_scenario
+from wifi_rx_check import check_partition  # (the comparison itself)
 
 pytestmark = pytest.mark.gpu
-
-
-def check_partition(eng, st, phys, base, ends, log, sc):
-    g = eng.stats()
-    gd, od = g.as_dict(), st.as_dict()
-    assert gd == od, {k: (gd[k], od[k]) for k in gd if gd[k] != od[k]}
-    assert np.array_equal(eng.tx_base(), base)
-    assert np.array_equal(eng.ends(), ends)
-    b, e = eng.phys_range
-    gp = eng.phys()
-    for f in wifi.PHY_COUNTERS_DTYPE.names:
-        if f == "first_power":
-            np.testing.assert_allclose(gp[f][b:e], phys[f][b:e], rtol=1e-9, atol=1e-24)
-        else:
-            assert np.array_equal(gp[f][b:e], phys[f][b:e]), f
-    if log is not None:
-        gl = eng.rx_log_read().reshape(len(sc.tx), sc.n_phy)
-        ol = log.reshape(len(sc.tx), sc.n_phy)
-        for f in ("ts", "uid", "outcome", "flags", "cca_ns"):
-            assert np.array_equal(gl[f][:, b:e], ol[f][:, b:e]), f
 
 
 def run_group(sc, parts, rx_log=True, store=wifi.STORE_AUTO):

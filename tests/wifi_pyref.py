@@ -14,9 +14,18 @@ import math
 import nsref
 
 
-def run(sc, durations):
+def run(sc, durations, info=None):
     """sc: wifi.Scenario; durations: ns per transmission.  Returns (stats dict, rx log dict
-    {(k, j): (ts, uid, outcome, flags, cca)}, ends list of dicts, tx_base list, phys list of dicts)."""
+    {(k, j): (ts, uid, outcome, flags, cca)}, ends list of dicts, tx_base list, phys list of dicts).
+
+    info: a dict that receives what the run reached (instrumentation only: nothing below reads it back) —
+    pe_max [phy]: most EndReceive events of one phy scheduled and not yet dispatched (the live one + cancelled ones);
+    starts_max [phy]: most Receives of one phy in one nanosecond whose start entries stay in its list together
+    (a Receive outside RX folds the list first: the count starts again at 1);
+    zero_delay: Receives scheduled with a 0 ns delay; tie_rr: Receives of a phy at the ts of its previous Receive;
+    tie_re: Receive / EndReceive pairs of one phy at one ts; sync_at_tx: syncing Receives at a ts at which a
+    transmission starts; rx_at_own_tx: Receives of a phy at the ts of one of its own SendPackets;
+    undispatched: transmissions after the Stop."""
     n = sc.n_phy
     ed_w = math.pow(10.0, sc.ed / 10.0) / 1000.0
     cca_w = math.pow(10.0, sc.cca / 10.0) / 1000.0
@@ -33,6 +42,10 @@ def run(sc, durations):
     st = dict(dispatched=0, tx=0, rx=0, sync=0, drop_rx=0, drop_tx=0, drop_ed=0, cca_evals=0, cca_switches=0,
               end=0, end_cancelled=0, final_ts=0)
     log, ends, tx_base = {}, [], [0] * len(sc.tx)
+    # instrumentation (info): per-phy trackers beside the model's state, never read by it
+    trk = [dict(pe=0, pe_max=0, starts=0, starts_max=0, last_rx=-1, last_end=-1, last_tx=-1) for _ in range(n)]
+    cnt = dict(zero_delay=0, tie_rr=0, tie_re=0, sync_at_tx=0, rx_at_own_tx=0)
+    tx_times = set(int(t) for t in sc.tx["ts"])
 
     def state(p, now):
         if p["end_tx"] > now:
@@ -65,6 +78,7 @@ def run(sc, durations):
             p = phy[s]
             cur = state(p, now)
             assert cur != "tx", "SendPacket while in TX"
+            trk[s]["last_tx"] = now
             if cur == "rx":
                 ends[p["live"]]["flags"] |= 1
                 p["rxing"] = False
@@ -81,12 +95,20 @@ def run(sc, durations):
                 rx = nsref.lib().nsref_calc_rx_power(float(t["dbm"]), d, chain)
                 heapq.heappush(heap, (now + delay, uid, ("rx", k, j, rx)))
                 log[(k, j)] = [now + delay, uid, 255, 0, 0]
+                cnt["zero_delay"] += delay == 0
                 uid += 1
         elif ev[0] == "rx":
             _, k, j, rx = ev
             p = phy[j]
             w = math.pow(10.0, (rx + sc.rx_gain_db) / 10.0) / 1000.0
             end_new = now + durations[k]
+            tk = trk[j]
+            tk["starts"] = tk["starts"] + 1 if (p["rxing"] and tk["last_rx"] == now) else 1
+            tk["starts_max"] = max(tk["starts_max"], tk["starts"])
+            cnt["tie_rr"] += tk["last_rx"] == now
+            cnt["tie_re"] += tk["last_end"] == now
+            cnt["rx_at_own_tx"] += tk["last_tx"] == now
+            tk["last_rx"] = now
             if not p["rxing"]:
                 i = bisect.bisect_right(p["ni_t"], now)
                 for q in range(i):
@@ -111,6 +133,9 @@ def run(sc, durations):
                 ends.append(dict(ts=end_new, sync_ts=now, uid=uid, phy=j, tx=k, flags=0))
                 heapq.heappush(heap, (end_new, uid, ("end", len(ends) - 1)))
                 uid += 1
+                tk["pe"] += 1
+                tk["pe_max"] = max(tk["pe_max"], tk["pe"])
+                cnt["sync_at_tx"] += now in tx_times
             else:
                 outcome, maybe = 3, True
             if maybe:
@@ -140,6 +165,10 @@ def run(sc, durations):
             e = ends[ev[1]]
             e["flags"] |= 2
             p = phy[e["phy"]]
+            tk = trk[e["phy"]]
+            tk["pe"] -= 1
+            cnt["tie_re"] += tk["last_rx"] == now
+            tk["last_end"] = now
             p["end"] += 1
             st["end"] += 1
             if e["flags"] & 1:
@@ -149,4 +178,7 @@ def run(sc, durations):
                 p["rxing"] = False
                 p["live"] = None
     st["next_uid"] = uid
+    if info is not None:
+        info.update(cnt, pe_max=[q["pe_max"] for q in trk], starts_max=[q["starts_max"] for q in trk],
+                    undispatched=len(sc.tx) - st["tx"])
     return st, log, ends, tx_base, phy
