@@ -666,6 +666,12 @@ class Sched:
         e = np.array([tuple(ev)], dtype=EVENT_DTYPE)
         check(lib().nsgpu_sched_remove(self.h, e.ctypes.data))
 
+    def stats(self):
+        """(refills so far, size of the current front, running estimate of one refill in microseconds)."""
+        refills, front, us = C.c_uint64(), C.c_uint64(), C.c_double()
+        check(lib().nsgpu_sched_stats(self.h, C.byref(refills), C.byref(front), C.byref(us)))
+        return refills.value, front.value, us.value
+
     def __del__(self):
         try:
             lib().nsgpu_sched_destroy(self.h)

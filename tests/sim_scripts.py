@@ -114,3 +114,86 @@ def random_script(sim, seed, n_ops=400):
         ids.append(sim.schedule(rng.randrange(0, 30), make(-i - 1)))
     sim.run()
     return log
+
+
+def burst_script(sim, seed, n_ops=3000):
+    """Bursts, 64-bit times and a Stop: the same log as `random_script`, for any backend.
+
+    Delays come from {0, 1, U[0, 50), 2^32 + U[0, 50), 3.6e12} (an hour), so timestamps pass 2^32 early; two handlers
+    schedule 5,000 events each in one dispatch; Cancel and Remove are aimed at the bursts' ids; one handler calls
+    Stop, and a second Run continues after it.
+    """
+    import random
+    rng = random.Random(seed)
+    log = []
+    ids = []
+    burst_ids = []
+    counter = [0]
+
+    def delay():
+        r = rng.random()
+        if r < 0.2:
+            return 0
+        if r < 0.4:
+            return 1
+        if r < 0.8:
+            return rng.randrange(0, 50)
+        if r < 0.97:
+            return (1 << 32) + rng.randrange(0, 50)
+        return 3600000000000
+
+    def leaf(tag):
+        def cb():
+            log.append((sim.now(), sim.context(), tag))
+        return cb
+
+    def make(tag):
+        def cb():
+            log.append((sim.now(), sim.context(), tag))
+            for _ in range(2 if rng.random() < 0.35 else 1):
+                if counter[0] >= n_ops or rng.random() > 0.85:
+                    break
+                counter[0] += 1
+                op = rng.random()
+                t = counter[0]
+                if op < 0.40:
+                    ids.append(sim.schedule(delay(), make(t)))
+                elif op < 0.65:
+                    sim.schedule_with_context(rng.randrange(0, 8), delay(), make(t))
+                elif op < 0.75:
+                    ids.append(sim.schedule_now(make(t)))
+                elif op < 0.80 and ids:
+                    sim.cancel(ids[rng.randrange(len(ids))])
+                elif op < 0.85 and ids:
+                    sim.remove(ids[rng.randrange(len(ids))])
+                elif op < 0.93 and burst_ids:
+                    sim.cancel(burst_ids[rng.randrange(len(burst_ids))])
+                elif burst_ids:
+                    sim.remove(burst_ids[rng.randrange(len(burst_ids))])
+        return cb
+
+    def burst(tag):
+        def cb():
+            log.append((sim.now(), sim.context(), tag))
+            for i in range(5000):
+                t = tag * 10000 + i
+                burst_ids.append(sim.schedule(delay(), make(t) if i % 10 == 0 else leaf(t)))
+        return cb
+
+    def stopper(tag):
+        def cb():
+            log.append((sim.now(), sim.context(), tag))
+            sim.stop()
+        return cb
+
+    for i in range(20):
+        ids.append(sim.schedule(rng.randrange(0, 30), make(-i - 1)))
+    sim.schedule(10, burst(-100))
+    sim.schedule((1 << 32) + 25, stopper(-300))
+    sim.schedule((1 << 32) + 60, burst(-200))
+    sim.run()
+    log.append(("stopped", sim.dispatched(), sim.next_uid()))
+    for i in range(5):                     # scheduled between the two Runs, at the Stop's time
+        ids.append(sim.schedule(rng.randrange(0, 30), make(-400 - i)))
+    sim.run()
+    return log
