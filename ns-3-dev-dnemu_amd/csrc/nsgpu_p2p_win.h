@@ -90,6 +90,21 @@ __device__ __forceinline__ uint32_t dense_rec(uint32_t d, uint32_t W, const uint
   }
   return region_base(lo) + (k - pre[lo]);
 }
+// The records at positions ka and kb (both < Lt) of the dense list, searched together: the two chains' LDS reads
+// are in flight at once, and every lane takes the same 7 steps (NLR <= 128).  The largest region r with
+// pre[r] <= k is dense_rec's: pre[] does not decrease, and past NLR the probe reads pre[NLR] = Lt > k.
+__device__ __forceinline__ void dense_rec2(uint32_t ka, uint32_t kb, const uint32_t *pre, uint32_t &ra, uint32_t &rb) {
+  uint32_t la = 0, lb = 0;
+#pragma unroll
+  for (uint32_t s = 64; s; s >>= 1) {
+    const uint32_t ma = la + s, mb = lb + s;
+    const uint32_t pa = pre[ma < (uint32_t)NLR ? ma : (uint32_t)NLR], pb = pre[mb < (uint32_t)NLR ? mb : (uint32_t)NLR];
+    la = pa <= ka ? ma : la;
+    lb = pb <= kb ? mb : lb;
+  }
+  ra = region_base(la) + (ka - pre[la]);
+  rb = region_base(lb) + (kb - pre[lb]);
+}
 
 // (HubEv, the node-part result of one hub event: nsgpu_p2p_dev.h)
 
@@ -2555,12 +2570,13 @@ __device__ __forceinline__ bool lk_before(const LKey &a, const LKey &b) {
 // levels with equal ts pairs).
 // The tiles that compare nothing but rel ts (gen-0 rows x local columns, local rows x gen-0 columns) read 4 B a
 // column and take RKCW columns in the deferred pipeline: a window at the full lookahead (config 4: N 5,888, W 3,840,
-// Lt 2,048) is then 15 x 8 + 8 x 32 + 8 x 15 = 496 tiles, one round of the 1,004 sub-tiles, where RKC columns
+// Lt 2,048) is then 15 x 8 + 8 x 32 + 8 x 15 = 496 tiles, one round of the 988 sub-tiles (NLIST, below), where RKC columns
 // everywhere made it 23 x 32 + 8 x 60 = 1,216 and a second round.
 constexpr int RKC = 64;    // columns per tile: rows with local records (16 B a column)
 constexpr int RKCW = 256;  // columns per tile: the rel-ts-only tiles of k2_rank<true>
 static_assert(RKCW <= RKT && RKCW % 4 == 0, "one thread loads a column; read four at a time");
 // (diagnostic build: the tiles' phase marks only with NSGPU_TILE_MARKS — their atomics distort the per-block times)
+// (marks 4, 6, 10, 12 of g_phase: slots no other kernel of the pipeline adds to)
 #ifdef NSGPU_TILE_MARKS
 #define TILE_MARK(i, win) BLK_MARK(i, win)
 #else
@@ -2623,7 +2639,17 @@ constexpr int RKT_DF = 1024;              // the deferred pipeline's k2_rank blo
 constexpr int NSDEF = 4;                  // blocks of the deferred accounting (df_sdef: each scans the whole
                                           // window, then resolves / logs / digests a quarter of its records)
 static_assert(NSDEF == 1 || NSDEF == 2 || NSDEF == 4 || NSDEF == 8, "a thread's NMAX / NT records split evenly");
-constexpr int RK_GRID_DF = 256;           // one 1024-thread block per CU (~150 KB of LDS each): bookkeeping, accounting, tiles
+// The list blocks (df_list, after the accounting blocks): what only the next kernels read — the window copy for the
+// next k2_pa, the dense list of the local records — so that
+// a tile block goes from the regions' prefix straight into its tiles.  A thread has one gen-0 slot and one local
+// record.  Config 4's full window is 496 tiles (above): the 256 - 1 - NSDEF - NLIST = 247 tile blocks hold
+// 247 x SUBS = 988 sub-tiles, one round.
+constexpr int NLIST = 4;
+static_assert(NLIST * RKT_DF >= WCAP && NLIST * RKT_DF >= LMAX, "one gen-0 slot and one local record a thread");
+template <int NT>
+__device__ void df_list(const P2PDev &M, Ctl &C, uint32_t b, uint32_t *pre);
+constexpr int RK_GRID_DF = 256;           // one 1024-thread block per CU (~150 KB of LDS each): bookkeeping, accounting, lists, tiles
+static_assert((RK_GRID_DF - 1 - NSDEF - NLIST) * (RKT_DF / RKT) >= 496, "a full window's tiles in one round");
 template <bool DF>
 __global__ __launch_bounds__(DF ? RKT_DF : RKT) void k2_rank(const P2PDev M) {
   constexpr int NT = DF ? RKT_DF : RKT, SUBS = NT / RKT;
@@ -2634,12 +2660,18 @@ __global__ __launch_bounds__(DF ? RKT_DF : RKT) void k2_rank(const P2PDev M) {
   const uint64_t c_win = DF ? C.rk_win : C.windows;  // (DF: block 0's bookkeeping advances C.windows)
   uint32_t n_tie = 0;
 #endif
+  __shared__ uint32_t pre[NLR + 1];
   // DF: blocks 1 .. NSDEF do the last window's dispatch accounting (k2_pa staged it) beside this window's
-  // ranking
+  // ranking, the NLIST blocks after them this window's lists
   if constexpr (DF) {
     if (blockIdx.x >= 1 && blockIdx.x <= (uint32_t)NSDEF) {
       df_sdef<NT>(M, C, blockIdx.x - 1, NSDEF);
       BLK_REC(2, c_win);  // (diagnostic build: k2_scan's per-block slot, unused by the deferred pipeline)
+      return;
+    }
+    if (blockIdx.x > (uint32_t)NSDEF && blockIdx.x <= (uint32_t)(NSDEF + NLIST)) {
+      df_list<NT>(M, C, blockIdx.x - 1 - NSDEF, pre);
+      BLK_REC(2, c_win);
       return;
     }
   }
@@ -2682,7 +2714,6 @@ __global__ __launch_bounds__(DF ? RKT_DF : RKT) void k2_rank(const P2PDev M) {
     return;
   }
   const bool ranked = (go & 1u) != 0;
-  __shared__ uint32_t pre[NLR + 1];
   __shared__ ulonglong2 cws[SUBS][RKC];
   // the columns' rel ts alone (the gen-0-row and local-row x gen-0 tiles compare nothing else): 4 B a column, read
   // 4 at a time — the tiles are bound by their per-column LDS reads and 64-bit compares
@@ -2693,7 +2724,8 @@ __global__ __launch_bounds__(DF ? RKT_DF : RKT) void k2_rank(const P2PDev M) {
   local_prefix<NT>((ranked && lim) ? lc : 0u, pre);
   const uint32_t Lt = pre[NLR], N = W + Lt;
   uint32_t *const wr = wrank_of(M, wn), *const lr = lrank_of(M, wn);
-  uint32_t b0 = blockIdx.x, nb = gridDim.x;  // (DF: block 0 keeps the books, 1 .. NSDEF account, the others rank)
+  // (DF: block 0 keeps the books, 1 .. NSDEF account, the NLIST after them make the lists, the others rank)
+  uint32_t b0 = blockIdx.x, nb = gridDim.x;
   if (DF) {
     if (blockIdx.x == 0) {
       df_book<NT>(M, C, ranked, W, Lt, s_fill[0], s_fill[1], wn, f_tot);
@@ -2701,11 +2733,7 @@ __global__ __launch_bounds__(DF ? RKT_DF : RKT) void k2_rank(const P2PDev M) {
       return;
     }
     if (!ranked) return;
-    b0 -= 1 + NSDEF, nb -= 1 + NSDEF;
-    for (uint32_t i = b0 * NT + threadIdx.x; i < W; i += nb * NT) {  // (the next k2_pa rewrites wkey / wctx)
-      M.pwkey[i] = M.wkey[i];
-      M.pwctx[i] = M.wctx[i];
-    }
+    b0 -= 1 + NSDEF + NLIST, nb -= 1 + NSDEF + NLIST;
   }
   if (Lt == 0 || N > (uint32_t)NMAX || Lt > (uint32_t)LMAX) return;  // (too many: the bookkeeping fails the run, error 64)
 #ifdef NSGPU_PHASE_PROF
@@ -2714,7 +2742,7 @@ __global__ __launch_bounds__(DF ? RKT_DF : RKT) void k2_rank(const P2PDev M) {
     g_phase[58] = Lt;
   }
 #endif
-  TILE_MARK(48, c_win);
+  TILE_MARK(4, c_win);
   // phase A: rows x local columns — the row tiles that hold gen-0 records only (the first nrg) at RKW columns a
   // tile, the others (the tile that straddles W, the local rows) at RKC; phase B: local rows x gen-0 columns, RKW
   const uint32_t nr = (N + RKT - 1) / RKT, nrg = W / RKT, ncl = (Lt + RKC - 1) / RKC, nclw = (Lt + RKW - 1) / RKW;
@@ -2733,7 +2761,52 @@ __global__ __launch_bounds__(DF ? RKT_DF : RKT) void k2_rank(const P2PDev M) {
     uint32_t ix = 0, rx = 0, tj = 0;
     bool g0rows = false;  // (tA: every row is a gen-0 record)
     uint64_t wx = ~0ull, wx2 = ~0ull, relx = 0;
-    if (tA) {  // rows: every record; columns: local records
+    if constexpr (DF) {
+      // One memory trip a tile: both record indices first (the column's and the row's searches step together), then
+      // the column's and the row's loads back to back at clamped indices (position 0 of the dense list exists:
+      // Lt > 0; slot 0 is inside wkey), the results selected afterwards; the first wait stands before the column's
+      // LDS store.  The dense list is the list blocks' (df_list).
+      if (tA) {  // rows: every record; columns: local records
+        g0rows = t < na0;
+        const uint32_t u = g0rows ? t : t - na0, nc = g0rows ? nclw : ncl, ti = u / nc + (g0rows ? 0u : nrg);
+        const uint32_t cwid = g0rows ? (uint32_t)RKW : (uint32_t)RKC;
+        tj = u % nc;
+        ix = ti * RKT + lt;
+        const uint32_t cy = tj * cwid + lt;
+        const bool cv = lt < cwid && cy < Lt, rg = ix < W, rl = !rg && ix < N;
+        uint32_t rc, rr;
+        dense_rec2(cv ? cy : 0u, rl ? ix - W : 0u, pre, rc, rr);
+        const ulonglong2 wc = M.lkw[rc - LBASE], wl = M.lkw[rr - LBASE];
+        const uint64_t kg = M.wkey[rg ? ix : 0u];
+        // (all three in registers here: otherwise the compiler sinks the row's search and load under the row's test,
+        // a second trip)
+        asm volatile("" ::"v"(wc.x), "v"(wc.y), "v"(wl.x), "v"(wl.y), "v"(kg));
+        if (lt < cwid) {
+          const ulonglong2 w = cv ? wc : make_ulonglong2(~0ull, ~0ull);  // (a padding column: after every row)
+          if (g0rows) cwh[lt] = (uint32_t)(w.x >> 32);  // (padding 0xffffffff: never below a row's rel ts)
+          else cw[lt] = w;
+        }
+        if (rg) {
+          rx = ix;
+          wx = (kg >> 32) << 32;  // (a local record of smaller rel ts comes first)
+          wx2 = 0;
+        } else if (rl) {
+          rx = rr;
+          wx = wl.x;
+          wx2 = wl.y;
+        }
+      } else if (tB) {  // rows: local records; columns: gen-0 records (rel ts <= the row's)
+        const uint32_t u = t - na, ti = u / ncg;
+        tj = u % ncg;
+        ix = ti * RKT + lt;
+        const uint32_t cy = tj * RKW + lt;
+        const bool rv = ix < Lt;
+        const uint32_t rr = dense_rec(W + (rv ? ix : 0u), W, pre);
+        const uint64_t kc = M.wkey[cy < W ? cy : 0u], kr = M.wkey[rr];
+        if (lt < (uint32_t)RKW) cwh[lt] = cy < W ? (uint32_t)(kc >> 32) : 0xffffffffu;  // (padding: counted out below)
+        if (rv) relx = kr >> 32;
+      }
+    } else if (tA) {  // rows: every record; columns: local records
       g0rows = t < na0;
       const uint32_t u = g0rows ? t : t - na0, nc = g0rows ? nclw : ncl, ti = u / nc + (g0rows ? 0u : nrg);
       const uint32_t cwid = g0rows ? (uint32_t)RKW : (uint32_t)RKC;
@@ -2748,7 +2821,6 @@ __global__ __launch_bounds__(DF ? RKT_DF : RKT) void k2_rank(const P2PDev M) {
           if (ti == 0) {  // the dense list k2_scan (ldat) and the next k2_pa (lrec) read; the local's context
             const uint32_t wp = M.wpar[r];
             M.ldat[cy] = make_uint4(r, M.nchild[r] | (M.ninl[r] << 16), (uint32_t)(w.x >> 32), wp);
-            if (DF) M.ldpd[cy] = dense_of(wp & 0xffffffu, W, pre) | (wp & 0xff000000u);
             M.lrec[cy] = r;
             M.pwctx[r] = M.wctx[r];
           }
@@ -2778,7 +2850,7 @@ __global__ __launch_bounds__(DF ? RKT_DF : RKT) void k2_rank(const P2PDev M) {
       if (ix < Lt) relx = M.wkey[dense_rec(W + ix, W, pre)] >> 32;
     }
     __syncthreads();
-    TILE_MARK(50, c_win);
+    TILE_MARK(6, c_win);
     const uint4 *const cwh4 = reinterpret_cast<const uint4 *>(cwh);
     if (tA && g0rows) {  // a local column precedes a gen-0 row iff its rel ts is smaller: one 32-bit compare
       const uint32_t tx = (uint32_t)(wx >> 32);
@@ -2825,10 +2897,10 @@ __global__ __launch_bounds__(DF ? RKT_DF : RKT) void k2_rank(const P2PDev M) {
       if (ix >= Lt) c = 0;
       slot = ix + LBASE;
     }
-    TILE_MARK(52, c_win);
+    TILE_MARK(10, c_win);
     if (c) atomicAdd(slot >= LBASE ? &lr[slot - LBASE] : &wr[slot], c);
     __syncthreads();
-    TILE_MARK(54, c_win);
+    TILE_MARK(12, c_win);
   }
   BLK_REC(2, c_win);
 #ifdef NSGPU_PHASE_PROF
@@ -3109,6 +3181,45 @@ __device__ void df_sdef(const P2PDev &M, Ctl &C, uint32_t b, uint32_t nsb) {
   for (uint32_t i = b * NT + tid; i < w.Lt; i += nsb * NT) M.lrank[(uint64_t)pn * LMAX + i] = 0;
 
   BLK_MARK(30, c_win);  // clears
+}
+
+// ---- df_list: what only the next kernels read (DF pipeline; k2_rank<true>'s list blocks) ----
+// NLIST blocks of NT threads; thread e = b * NT + tid has gen-0 slot e and local record e of the dense list.
+//  * The window's keys / contexts for the next k2_pa (pwkey / pwctx: it rewrites wkey / wctx), for every ranked
+//    window, also one without local records or with too many.  The slot is loaded with the run control, before W is
+//    known (e < WCAP: inside the arrays).
+//  * The dense list of the local records for k2_scan's flush (ldat), the next k2_pa (lrec, ldpd: a parent as a dense
+//    index) and the locals' contexts (pwctx[r]), for a ranked window whose size passes the tiles' test: a record's
+//    five loads in one batch, then its stores.
+// pre: the caller's NLR + 1 words of LDS (local_prefix).
+template <int NT>
+__device__ void df_list(const P2PDev &M, Ctl &C0, uint32_t b, uint32_t *pre) {
+  Ctl &C = *vec_ctl(&C0);  // (the run control through the vector path: in flight with the slot's loads)
+  const uint32_t e = b * NT + threadIdx.x;
+  const uint32_t go = C.rk_go, W = C.rk_W;
+  const uint64_t lim = C.rk_lim;
+  const uint32_t lc = threadIdx.x < (uint32_t)NLR ? M.lcnt[threadIdx.x] : 0u;
+  const uint32_t es = e < (uint32_t)WCAP ? e : 0u;
+  const uint64_t key = M.wkey[es];
+  const uint32_t ctx = M.wctx[es];
+  // (k2_rank's tests: no window was formed; a sorted run's chunk; an unranked window)
+  if (!(go & 2u) || (go & 4u) || !(go & 1u)) return;
+  if (e < W && e < (uint32_t)WCAP) {
+    M.pwkey[e] = key;
+    M.pwctx[e] = ctx;
+  }
+  local_prefix<NT>(lim ? lc : 0u, pre);
+  const uint32_t Lt = pre[NLR], N = W + Lt;
+  if (Lt == 0 || N > (uint32_t)NMAX || Lt > (uint32_t)LMAX) return;
+  if (e < Lt) {
+    const uint32_t r = dense_rec(W + e, W, pre);
+    const uint32_t rel = (uint32_t)(M.lkw[r - LBASE].x >> 32), wp = M.wpar[r], nc = M.nchild[r], ni = M.ninl[r];
+    const uint32_t cx = M.wctx[r];
+    M.ldat[e] = make_uint4(r, nc | (ni << 16), rel, wp);
+    M.ldpd[e] = dense_of(wp & 0xffffffu, W, pre) | (wp & 0xff000000u);
+    M.lrec[e] = r;
+    M.pwctx[r] = cx;
+  }
 }
 
 // ---- k2_scan: rank order; child / inline prefixes, same-ts groups, run bookkeeping ----

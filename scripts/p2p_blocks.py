@@ -1,5 +1,9 @@
 """Diagnostic: per-block start / end times of the three window kernels in one sampled window
-(lib/libnsgpu_prof.so, NSGPU_LIB): which roles finish last, how late blocks start."""
+(lib/libnsgpu_prof.so, NSGPU_LIB): which roles finish last, how late blocks start.  On a wide engine the third kernel
+is k2_rank<true>: its roles (bookkeeping, accounting, lists, tiles), df_sdef's marks and, from a build with
+-DNSGPU_TILE_MARKS, the tile marks.
+
+Usage: python scripts/p2p_blocks.py [grid side] [NSDEF] [NLIST]"""
 import os
 import sys
 
@@ -11,6 +15,10 @@ import nsgpu  # noqa: E402
 import p2p  # noqa: E402
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 128
+# k2_rank<true>'s blocks after the bookkeeping one: accounting (NSDEF), lists (NLIST), then the tiles (nsgpu_p2p_win.h;
+# a build without list blocks: 0)
+nsdef = int(sys.argv[2]) if len(sys.argv) > 2 else 4
+nlist = int(sys.argv[3]) if len(sys.argv) > 3 else 4
 eng = p2p.Engine(p2p.grid(n, n))
 eng.set_eager(True)
 eng.run()
@@ -22,7 +30,10 @@ nslot = (4096 + 4096) // 256 if eng.wide() else 16  # (wide: gen-0 slots + the l
 roles = {0: [("slot", 0, 16), ("lslot", 16, nslot), ("pool", nslot, 256)],
          1: [("holder", 0, 64), ("rank", 64, 1088), ("hub", 1088, 1120), ("maint", 1120, 1248)],
          2: [("scan", 0, 1)]}
-for k, name in enumerate(("k2_pa", "k2_handle", "k2_scan")):
+if eng.wide():  # (the deferred pipeline: the third kernel is k2_rank<true>, its blocks record in k2_scan's slot)
+    roles[2] = [("book", 0, 1), ("account", 1, 1 + nsdef), ("list", 1 + nsdef, 1 + nsdef + nlist),
+                ("tiles", 1 + nsdef + nlist, 256)]
+for k, name in enumerate(("k2_pa", "k2_handle", "k2_rank" if eng.wide() else "k2_scan")):
     b = blk[k]
     ok = b[:, 1] > 0
     t0 = b[ok, 0].min()
@@ -47,3 +58,14 @@ print("k2_pa pool blocks, mean per block (sampled window):")
 for i, nm in ((52, "run control + barrier"), (54, "pool sweep"), (62, "publish_min + digest")):
     c = max(int(buf[i + 1]), 1)
     print(f"  {nm:40s} {buf[i] * 0.01 / c:6.2f} us  (n={int(buf[i + 1])})")
+if eng.wide():
+    print("k2_rank accounting blocks (df_sdef), mean per block (sampled window; a hub block's marks share 22..27):")
+    for i, nm in ((22, "records arrive"), (24, "block scan"), (26, "LDS arrays, prefixes"), (28, "resolve, log, digest"),
+                  (30, "clears (and the stores' drain)")):
+        c = max(int(buf[i + 1]), 1)
+        print(f"  {nm:40s} {buf[i] * 0.01 / c:6.2f} us  (n={int(buf[i + 1])})")
+    print("k2_rank tile blocks (a build with NSGPU_TILE_MARKS), mean per block and mark (sampled window):")
+    for i, nm in ((4, "control, prefix -> first tile"), (6, "tile operands -> barrier"), (10, "compare loop"),
+                  (12, "rank atomic -> barrier")):
+        c = max(int(buf[i + 1]), 1)
+        print(f"  {nm:40s} {buf[i] * 0.01 / c:6.2f} us  (n={int(buf[i + 1])})")
